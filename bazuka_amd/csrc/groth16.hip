@@ -322,7 +322,8 @@ int32_t bzk_params_slot(bzk_ctx* ctx, const bzk_params* src, bzk_params** out) {
 //                                                        limit; BZK_PROVE_H_TABLE=0 switches the table off)
 // Memory policy: a resident form is only built when hipMemGetInfo shows its size plus a reserve for the provers' grow-only
 // workspaces free; anything that does not fit is simply not built (the per-call pipeline on the raw bases works without it), and
-// bzk_groth16_prove drops the table and retries once if a workspace allocation fails later while it is the CRS's only user.
+// bzk_groth16_prove drops the table and the resident sets and retries once if a workspace allocation fails later while it is the CRS's
+// only user.
 // env BZK_PROVE_MERGE_LB1=0: l and b_g1 as two MSMs (the round-2 form; A/B runs).  BZK_PROVE_LANES=4 implies it (b_g1 has its own lane there).
 static bool prove_merge_lb1() {
     static const bool on = [] {
@@ -569,21 +570,34 @@ static int32_t groth16_prove_entry(bzk_ctx* ctx, bzk_params* p, const bzk_assign
         (void)hipGetLastError();
     };
     if (st == BZK_E_ALLOC) {
-        // a grow-only workspace did not fit beside the resident h table: if this slot is the CRS's only user, give the table's memory
-        // back and prove once more through the per-call pipeline; a shared table cannot be pulled from under other slots
+        // a grow-only workspace did not fit beside the resident h table and base sets (crs_prepare's reserve is an estimate: at 2^26 the
+        // five MSMs' workspaces outgrow it): if this slot is the CRS's only user, give the table's and the resident sets' memory back,
+        // release the workspaces of the failed attempt and prove once more through the per-call pipeline on the raw bases;
+        // shared resident forms cannot be pulled from under other slots
         quiesce();
         CrsShared* c = p->crs;
         bool dropped = false;
         {
             std::lock_guard<std::mutex> lk(c->m);
-            bzk_msm_table* t = c->h_table.load(std::memory_order_acquire);
-            if (t && c->refs.load() == 1) {
-                c->h_table.store(nullptr, std::memory_order_release);
-                bzk_msm_table_free(ctx, t);
-                dropped = true;
+            if (c->refs.load() == 1) {
+                if (bzk_msm_table* t = c->h_table.load(std::memory_order_acquire)) {
+                    c->h_table.store(nullptr, std::memory_order_release);
+                    bzk_msm_table_free(ctx, t);
+                    dropped = true;
+                }
+                for (bzk_msm_bases** b : {&c->rl, &c->ra, &c->rb1, &c->rb2, &c->rh, &c->rlb1})
+                    if (*b) {
+                        bzk_msm_bases_free(ctx, *b);
+                        *b = nullptr;
+                        dropped = true;
+                    }
             }
         }
-        if (dropped) st = groth16_prove_impl(ctx, p, asg, dd, st_in, r32, s32, proof);
+        if (dropped) {
+            for (bzk_ctx* l : ctx->lanes) (void)bzk_ctx_trim(l, nullptr);
+            (void)bzk_ctx_trim(ctx, nullptr);
+            st = groth16_prove_impl(ctx, p, asg, dd, st_in, r32, s32, proof);
+        }
     }
     if (st != BZK_OK) quiesce();
     return st;

@@ -27,6 +27,12 @@ Other sections of the same JSON line (N = 1): `proofs` (full Groth16 proofs of t
             hands launches to its worker threads (AMD_DIRECT_DISPATCH=0: what a proving service sets; `proofs.process`).
 Options:    --scaling strong --log-n-total 24|26 (fixed job), --partition points (rank r owns points, not windows),
             --no-proofs / --no-others / --no-overlap / --no-cpu-baseline (shorter runs for profiling).
+--full      A plain run sets up, warms up, times the --steps MSM steps and prints the headline line (metric, value, ms_per_step, ...).
+            Everything else above - roofline, kernel_ms_per_step, cpu_baseline, proofs, other_configs, two_msms_in_flight and the
+            untimed parity checks of the timed result - runs only with --full.
+--dump-outputs DIR
+            writes the timed path's result of its last step as DIR/msm_g1_result.npy: the 97-byte packed affine point (x | y as
+            48-byte Montgomery limbs, infinity flag), one float64 per byte.  Inputs are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -955,6 +961,11 @@ def main():
                     help="internal: the second prover process of proofs.two_processes (proves until told to stop on stdin; prints no bench line)")
     ap.add_argument("--proofs-child", type=int, default=-1,
                     help="internal: run the proofs section on this device in a process of its own and print it as one BZK_PROOFS_JSON line (see proofs_in_child)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: proofs/s, other configurations, MSMs in flight, CPU baseline, per-kernel "
+                         "table, roofline and the untimed parity checks (a plain run times the headline MSM steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if args.proofs_child >= 0:
@@ -1008,7 +1019,7 @@ def main():
     # The proofs child runs BEFORE this process initialises the HIP runtime: two processes with 16 hardware queues each on one GPU are time-sliced by the
     # scheduler even when one of them idles (run 40: 69.7 proofs/s in a child beside the idle parent against 78.1 alone).
     early_proofs = None
-    if (not args.no_proofs and os.environ.get("BZK_BENCH_PROOFS_PROCESS", "1") != "0" and not os.environ.get("BZK_BENCH_SPAWN_ONLY")
+    if (args.full and not args.no_proofs and os.environ.get("BZK_BENCH_PROOFS_PROCESS", "1") != "0" and not os.environ.get("BZK_BENCH_SPAWN_ONLY")
             and int(os.environ.get("WORLD_SIZE", "1")) == args.gpus):
         try:
             import subprocess
@@ -1063,6 +1074,7 @@ def main():
     if dry:
         local_rank %= torch.cuda.device_count()
     torch.cuda.set_device(local_rank)
+    # also without --full, so that the headline MSM steps are timed in the same host-wait mode with or without the other sections
     if not args.no_proofs and "BZK_SYNC_BLOCKING" not in os.environ and quota_binds(cpu_quota(), world):
         os.environ["BZK_SYNC_BLOCKING"] = "1"  # read by libbzk when the first context is created (full_prove_section explains)
     dev = torch.device("cuda", local_rank)
@@ -1137,11 +1149,12 @@ def main():
     result = None
     for _ in range(args.warmup):
         result = step()
-    # HIP events on the ctx stream, inside the timed region, around the DOMINANT kernel only (two events per step): timing all
-    # ~25 launches of a step costs ~0.25 ms of event creation per step, i.e. it would be measured into `value`
-    pctx.prof_filter("msm_accumulate")
-    pctx.prof_enable(True)
-    pctx.prof_reset()
+    if args.full:
+        # HIP events on the ctx stream, inside the timed region, around the DOMINANT kernel only (two events per step): timing all
+        # ~25 launches of a step costs ~0.25 ms of event creation per step, i.e. it would be measured into `value`
+        pctx.prof_filter("msm_accumulate")
+        pctx.prof_enable(True)
+        pctx.prof_reset()
     if mg:
         mg.stats(reset=True)
     fence()
@@ -1150,41 +1163,50 @@ def main():
         result = step()
     fence()
     elapsed = time.perf_counter() - t0
-    pctx.prof_enable(False)
-    prof = pctx.prof_dump()
-    # the per-kernel breakdown comes from extra, untimed steps with every launch instrumented
-    pctx.prof_filter(None)
-    pctx.prof_enable(True)
-    pctx.prof_reset()
-    n_break = min(5, args.steps)
-    for _ in range(n_break):
-        step()
-    fence()
-    pctx.prof_enable(False)
-    prof_all = pctx.prof_dump()
+    if args.dump_outputs and rank == 0:
+        # the packed affine result (x | y, 48-byte Montgomery limbs each, then the infinity flag), one float64 per byte: exact
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "msm_g1_result.npy"), np.frombuffer(result, dtype=np.uint8).astype(np.float64))
+    prof, prof_all, n_break = {}, {}, 0
+    if args.full:
+        pctx.prof_enable(False)
+        prof = pctx.prof_dump()
+        # the per-kernel breakdown comes from extra, untimed steps with every launch instrumented
+        pctx.prof_filter(None)
+        pctx.prof_enable(True)
+        pctx.prof_reset()
+        n_break = min(5, args.steps)
+        for _ in range(n_break):
+            step()
+        fence()
+        pctx.prof_enable(False)
+        prof_all = pctx.prof_dump()
     elapsed_rank = elapsed
     acc_n_rank, acc_ms_rank = prof.get("msm_accumulate", (0, 0.0))
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        # every rank must hold the same folded result
-        r = torch.frombuffer(bytearray(result), dtype=torch.uint8).to(dev)
-        r0 = r.clone()
-        dist.broadcast(r0, 0)
-        assert bool((r == r0).all()), "ranks disagree on the MSM result"
-        # untimed: the window-sharded + folded result equals the unsharded MSM of the same points on one GPU
-        if rank == 0:
-            assert ctx.msm_g1_dev(bases, scalars, n) == result, "window-sharded MSM differs from the single-GPU MSM"
-    elif args.log_n <= 22:  # untimed: the resident-set call equals the per-call pipeline on the raw bases
-        assert ctx.msm_g1_dev(bases, scalars, n) == result, "resident-base MSM differs from the raw-base MSM"
+    if args.full:
+        if world > 1:
+            # every rank must hold the same folded result
+            r = torch.frombuffer(bytearray(result), dtype=torch.uint8).to(dev)
+            r0 = r.clone()
+            dist.broadcast(r0, 0)
+            assert bool((r == r0).all()), "ranks disagree on the MSM result"
+            # untimed: the window-sharded + folded result equals the unsharded MSM of the same points on one GPU
+            if rank == 0:
+                assert ctx.msm_g1_dev(bases, scalars, n) == result, "window-sharded MSM differs from the single-GPU MSM"
+        elif args.log_n <= 22:  # untimed: the resident-set call equals the per-call pipeline on the raw bases
+            assert ctx.msm_g1_dev(bases, scalars, n) == result, "resident-base MSM differs from the raw-base MSM"
 
     acc_n, acc_ms = prof.get("msm_accumulate", (0, 0.0))
     # Informational (N = 1): the same K MSMs issued from two host threads on two contexts (own stream + workspace each) -
     # what a prover with independent MSMs in flight sees: the latency-bound tail of one MSM (bucket reduction, window
     # sums, read-back, ~1.4 ms) overlaps the accumulation of the other.  `value` above stays the one-at-a-time rate.
     overlapped = None
-    if world == 1 and not args.no_overlap:
+    if args.full and world == 1 and not args.no_overlap:
         # Informational (N = 1): the same MSM issued from 2 and 4 host threads, each on a context of its own (stream + workspace), over the SAME resident
         # base set - what a prover with independent MSMs in flight sees (round 5 measured this over RAW bases, i.e. with a conversion per call: +1.8 %; the
         # resident-set figure is the comparable one).  `value` above stays the one-at-a-time rate.
@@ -1275,7 +1297,7 @@ def main():
                          "two ranks on one device): a rehearsal of the code path, NOT a measurement")
     # the other single-GPU configurations: before the proofs section (which may switch the process to blocking host waits)
     others = None
-    if world == 1 and rank == 0 and not args.no_others:
+    if args.full and world == 1 and rank == 0 and not args.no_others:
         try:
             others = other_configs_section(ctx, dev)
         except Exception as e:  # the headline line must still be printed
@@ -1288,7 +1310,7 @@ def main():
                 others["production_block"] = {"error": repr(e)}
     # Second half of the metric: full Groth16 proofs/s.  Every rank proves its own batches (replicas).
     proofs, rates, rates_live, host_cpu = None, [], [], []
-    if not args.no_proofs:
+    if args.full and not args.no_proofs:
         try:
             # N ranks share the host: split its cores between the ranks' witness producers
             # 8 producers x 8 worker threads measured best of the producer / thread sweeps (profiles/r02_run34_35_producer_sweep.txt:
@@ -1350,11 +1372,12 @@ def main():
                                           "frac": round(tmad / MAD_PEAK_T, 4),
                                           "how": f"{MADS_PER_MIXED_ADD} mads issued per mixed add (6 x 394 + 2 x 301 + 590 for the fused Y) against the "
                                                  "micro-benchmarked instruction ceiling (profiles/r04_ubench_int.txt)"}
-        out["kernel_ms_per_step"] = {k: round(v[1] / n_break, 4) for k, v in sorted(prof_all.items())}
-        out["kernel_ms_per_step_how"] = f"{n_break} extra untimed steps with every launch instrumented (HIP events)"
+        if args.full:
+            out["kernel_ms_per_step"] = {k: round(v[1] / n_break, 4) for k, v in sorted(prof_all.items())}
+            out["kernel_ms_per_step_how"] = f"{n_break} extra untimed steps with every launch instrumented (HIP events)"
         if overlapped:
             out["two_msms_in_flight"] = overlapped
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import coracle as co
             # threads = the CPUs this container may actually consume (the pool's boxes show 256 logical CPUs inside a 16-CPU quota; 256
             # threads on it were 16 x oversubscribed - VERDICT r3 weak 8); the all-threads figure is reported beside it

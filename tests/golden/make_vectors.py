@@ -3,6 +3,7 @@
   reference_vectors.json  vectors COPIED FROM THE REFERENCE'S OWN TESTS / CONFIG (the anchors the oracle is pinned on):
       - the 16 Poseidon known answers, inputs [0..k)             /root/reference/src/zk/poseidon/mod.rs:114-149
       - SHA-256 of each Poseidon parameter file (t = 2..17)      /root/reference/src/zk/poseidon/params/*.txt
+        and of its round constants and MDS entries as values  (fr_list_sha256)
       - the three hard-coded Groth16 verifying keys (bincode)    /root/reference/src/config/blockchain.rs:32-37
       - the Jubjub sign/verify case: seed b"ABC", message 123456 /root/reference/src/crypto/jubjub/mod.rs:180-192
         (the reference only asserts verify() == true; the key / signature values recorded here are the oracle's)
@@ -28,6 +29,12 @@ from oracle import pyref as pr  # noqa: E402
 from util import fr_bytes, fr_list, log2_ceil, r1cs_to_csr, rand_scalars_bytes, synth_r1cs  # noqa: E402
 
 
+def fr_list_sha256(vals):
+    """SHA-256 of a list of field elements as 32-byte little-endian canonical integers (how the parameter files' round constants and
+    MDS entries are recorded: tests/test_oracle_cpu.py compares the oracle's re-derivation with these digests)"""
+    return hashlib.sha256(b"".join(v.to_bytes(32, "little") for v in vals)).hexdigest()
+
+
 def reference_vectors():
     src = open(f"{REF}/src/zk/poseidon/mod.rs").read()
     kats = [int(h, 16) for h in re.findall(r'from_str_vartime\(\s*"(\d+)"', src)] or None
@@ -35,16 +42,21 @@ def reference_vectors():
         from test_oracle_cpu import POSEIDON_KAT
         kats = list(POSEIDON_KAT)
     assert len(kats) == 16 and all(pr.poseidon(list(range(k + 1))) == kats[k] for k in range(16))
-    params = {}
+    params, values = {}, {}
     for t in range(2, 18):
         p = f"{REF}/src/zk/poseidon/params/poseidon_params_n255_t{t}_alpha5_M128.txt"
         params[str(t)] = hashlib.sha256(open(p, "rb").read()).hexdigest()
+        lines = open(p).read().splitlines()
+        rc = [int(x, 16) for x in re.findall(r"0x[0-9a-f]+", lines[3])]
+        mds = [int(x, 16) for x in re.findall(r"0x[0-9a-f]+", lines[15])]
+        values[str(t)] = {"n_rc": len(rc), "rc_sha256": fr_list_sha256(rc), "n_mds": len(mds), "mds_sha256": fr_list_sha256(mds)}
     cfg = open(f"{REF}/src/config/blockchain.rs").read()
     vks = re.findall(r'"([0-9a-f]{2000,})"', cfg)[:3]
     sk = pr.jj_generate_keys(b"ABC")
     rr, s = pr.jj_sign(sk, 123456)
     assert pr.jj_verify(sk["pub"], 123456, (rr, s))
-    return {"poseidon_kat": [hex(x) for x in kats], "poseidon_param_files_sha256": params, "verifying_keys_bincode_hex": vks,
+    return {"poseidon_kat": [hex(x) for x in kats], "poseidon_param_files_sha256": params, "poseidon_params_values_sha256": values,
+            "verifying_keys_bincode_hex": vks,
             "jubjub_abc": {"pub": [hex(sk["pub"][0]), hex(sk["pub"][1])], "sig_r": [hex(rr[0]), hex(rr[1])], "sig_s": hex(s),
                            "message": 123456}}
 

@@ -229,6 +229,24 @@ BZK_HD Fr from29(const Fr29& a) {  // any k <= 35 -> canonical 8 x 32-bit Montgo
     return repack_to32(t);
 }
 
+// a^(r - 2) (Fermat): the inverse of a non-zero a, 0 for a = 0.  Left-to-right binary over the fixed exponent: 254 squares and 163
+// products, one dependent chain (the ladders of bzk_witfill.cuh invert once per ladder).  Any normalised a with k <= 8; result k 2.
+BZK_HD Fr29 inv(const Fr29& a) {
+    constexpr uint32_t E[8] = {0xffffffffu, 0xfffffffeu, 0xfffe5bfeu, 0x53bda402u, 0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};  // r - 2
+    const Fr29 b = mul(a, from_consts(ONE));  // k 2 whatever a's k: the chain below multiplies by it 163 times
+    Fr29 x = b;                               // bit 254 of r - 2 (word 7, bit 30) is its top bit
+#pragma unroll
+    for (int w = 7; w >= 0; --w) {            // unrolled over the words: each word is a constant, nothing is indexed at run time
+        const uint32_t e = E[w];
+#pragma unroll 1
+        for (int j = w == 7 ? 29 : 31; j >= 0; --j) {
+            x = sqr(x);
+            if ((e >> j) & 1u) x = mul(x, b);
+        }
+    }
+    return x;
+}
+
 // out = canonical 8 x 32-bit limbs of (a * s * 2^-261 mod r): with s = x * 2^256 this is Montgomery-256(a' * x) for
 // a = a' * 2^261; from29() is the case s = C_OUT.  Any ka <= 35, s < r.
 BZK_HD Fr from29_scaled(const Fr29& a, const Fr29& s_) {

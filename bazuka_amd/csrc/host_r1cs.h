@@ -141,7 +141,7 @@ struct DeferProgram {
     size_t hole_aux = 0, hole_con = 0;  // slots per transition left to the device
     void finalize() {
         v_ops.clear(); f_ops.clear();
-        for (const wf::Op& o : ops) (o.kind == wf::V_HASH || o.kind == wf::V_SEL ? v_ops : f_ops).push_back(o);
+        for (const wf::Op& o : ops) (o.kind == wf::V_HASH || o.kind == wf::V_SEL || o.kind == wf::V_LADDER ? v_ops : f_ops).push_back(o);
         // selections keep their EMISSION order inside a level (no key on Is / Not): the host executor runs them in list order, and a selection may read the
         // register of an earlier selection of the same level; hashes of a level only read lower levels, so their order is free
         std::stable_sort(v_ops.begin(), v_ops.end(), [](const wf::Op& a, const wf::Op& b) {
@@ -181,6 +181,7 @@ struct DeferProgram {
             } else if (o.kind == wf::F_MUX) { na = 1; nc = 1; }
             else if (o.kind == wf::F_ASSERT_EQ_IF) { na = 1; nc = 2; }
             else if (o.kind == wf::F_ENFORCE_EQ) { nc = 1; }
+            else if (o.kind == wf::F_LADDER) { na = nc = wf::ladder_slots(o.t); }
             hole_aux += na; hole_con += nc;
             if (nc) con_holes.push_back({o.con_off, nc});
         }
@@ -195,6 +196,7 @@ struct Defer {
     uint32_t n_in = 0;
     int32_t n_regs = 0;
     bool overflow = false;
+    bool sig = false;    // the EdDSA gadget's ladders and tail are deferred as well (BZK_SYNTH_DEFER_SIG): g_verify_eddsa
     std::vector<uint16_t> reg_level;  // plan pass: level of the op producing each register
     int32_t in_val(const Fr& v) {
         if (n_in < cap_inputs) inputs[n_in] = v;
@@ -204,6 +206,11 @@ struct Defer {
     int32_t new_reg(uint16_t level) {
         if (plan) reg_level.push_back(level);
         return n_regs++;
+    }
+    int32_t new_regs(uint32_t n, uint16_t level) {  // n consecutive registers, the first returned
+        const int32_t first = n_regs;
+        for (uint32_t i = 0; i < n; ++i) new_reg(level);
+        return first;
     }
     uint16_t level_of(int32_t operand) const { return plan && operand >= 0 ? reg_level[(size_t)operand] : (uint16_t)0; }
     void emit(const wf::Op& op) {
@@ -217,6 +224,7 @@ struct DeferData {
     size_t n_tx = 0;
     size_t base_aux = 0, base_con = 0;  // aux / constraint index of transition 0's window; transition t at base + t * stride
     size_t stride_aux = 0, stride_con = 0;
+    bool sig = false;                   // requested: the signature gadget is deferred too (Defer::sig; programs are kept per level)
     bool filled = false;                // the host arrays are complete (bzk_r1cs_fill_host ran)
     uint32_t flags = 0;                 // wf::FLAG_* of that fill
 };
@@ -958,9 +966,46 @@ static inline APoint g_mul_cofactor(ConstraintSystem& cs, const APoint& p) {  //
     return q;
 }
 
+// Defer::sig: one double-and-add ladder - for the variable base followed by the signature's tail (+ sig_r, mul_cofactor's three doublings) - left to the
+// device (bzk_witfill.cuh V_LADDER / F_LADDER).  The strict bit decomposition and the first bit's two muxes stay here, exactly as APoint::mul /
+// g_base_mul run them (bx / by: the second operand of those muxes); the steps' and the tail's slots are skipped.  Returns the point the gadget compares
+// (the fixed base's ladder result, the variable base's 8 (R + pk h)) as registers.
+static inline APoint g_ladder_deferred(ConstraintSystem& cs, uint8_t kind, const Number& bx, const Number& by, const Num& b, const APoint* sig_r) {
+    std::vector<Bit> le = num_to_bits_le_strict(cs, b);
+    if (le.size() != wf::LADDER_STEPS + 1) throw std::logic_error("a strict decomposition of other than 255 bits");
+    const Bool top = Bool::is(le.back());  // MSB
+    mux(cs, top, Number::zero(), bx);
+    mux(cs, top, Number::constant(Fr::one()), by);
+    Defer& D = *cs.defer;
+    wf::Op v{};
+    v.kind = wf::V_LADDER; v.t = kind; v.level = 0;
+    v.in[0] = D.in_val(bx.val); v.in[1] = D.in_val(by.val); v.in[2] = D.in_val(b.val); v.in[3] = D.in_val(jubjub_d().v);
+    if (sig_r) { v.in[4] = D.in_val(sig_r->x.val); v.in[5] = D.in_val(sig_r->y.val); }
+    v.out = D.new_regs(wf::ladder_regs(kind), 0);
+    wf::Op f = v;
+    f.kind = wf::F_LADDER; f.aux_off = (uint32_t)cs.win_n_aux; f.con_off = (uint32_t)cs.win_n_con;
+    D.emit(v);
+    D.emit(f);
+    const uint32_t n = wf::ladder_slots(kind);
+    cs.skip(n, n);
+    const int32_t r = v.out + (int32_t)wf::ladder_result_reg(kind);
+    APoint p;
+    p.x = {VAR_AUX | (Var)(cs.win_n_aux - 2), Fr::zero(), r};
+    p.y = {VAR_AUX | (Var)(cs.win_n_aux - 1), Fr::zero(), r + 1};
+    return p;
+}
+
 static inline void g_verify_eddsa(ConstraintSystem& cs, const Bool& enabled, const APoint& pk, const Number& msg,
                                   const APoint& sig_r, const Num& sig_s) {  // :249-280
     Num h = g_poseidon(cs, {Number::from(sig_r.x), Number::from(sig_r.y), Number::from(pk.x), Number::from(pk.y), msg}, true).compress(cs);
+    if (cs.defer && cs.defer->sig) {  // same order: g_base_mul(s), pk.mul(h) + the tail, the two checks (on the device: register operands)
+        const PointAffine& base = jubjub_base_cofactor();
+        const APoint sb = g_ladder_deferred(cs, 1, Number::constant(base.x.v), Number::constant(base.y.v), sig_s, nullptr);
+        const APoint rpha = g_ladder_deferred(cs, 0, Number::from(pk.x), Number::from(pk.y), h, &sig_r);
+        Number::from(rpha.x).assert_equal_if_enabled(cs, enabled, Number::from(sb.x));
+        Number::from(rpha.y).assert_equal_if_enabled(cs, enabled, Number::from(sb.y));
+        return;
+    }
     APoint sb = g_base_mul(cs, jubjub_base_cofactor(), sig_s);
     APoint rpha = pk.mul(cs, h);
     rpha = rpha.add(cs, sig_r);

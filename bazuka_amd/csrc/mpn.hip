@@ -94,6 +94,7 @@ struct bzk_mpn {
     int threads = host_default_threads();  // the CPUs this process may use (visible ones capped by the cgroup quota); bzk_mpn_set_threads overrides
     bzk_ctx* dev = nullptr;  // bzk_mpn_set_device: the witness builders hash their Merkle updates in batches on this context
     bool defer = false;      // bzk_mpn_set_defer: witness-only Update instances leave the hash-dependent values to the device (host_r1cs.h DeferProgram)
+    bool defer_sig = false;  // bzk_mpn_set_defer_sig: ... and the signature gadget's ladders (implies `defer`)
     std::string dev_error;
 
     bzk_mpn(int l, int t) : L(l), T(t) {
@@ -784,15 +785,16 @@ static void synthesize_update(ConstraintSystem& cs, int L, int T, const ZkScalar
         };
         if (dd) {
             static std::mutex mu;
-            static std::map<std::pair<int, int>, std::unique_ptr<DeferProgram>> progs;
+            static std::map<std::tuple<int, int, bool>, std::unique_ptr<DeferProgram>> progs;
             std::lock_guard<std::mutex> lk(mu);
-            auto it = progs.find({L, T});
+            auto it = progs.find(std::make_tuple(L, T, dd->sig));
             if (it == progs.end()) {
                 std::unique_ptr<DeferProgram> P(new DeferProgram());
                 std::vector<Fr> sa(size_hint_aux), sx(size_hint_cons), sy(size_hint_cons), sz(size_hint_cons), sin(1 << 14);
                 ConstraintSystem plan(false);
                 plan.set_window(sa.data(), size_hint_aux, sx.data(), sy.data(), sz.data(), size_hint_cons);
                 Defer D{P.get(), true, sin.data(), (uint32_t)sin.size()};
+                D.sig = dd->sig;
                 plan.defer = &D;
                 LcModeGuard g(false);
                 Num st0 = {VAR_ONE, state.v};
@@ -805,7 +807,7 @@ static void synthesize_update(ConstraintSystem& cs, int L, int T, const ZkScalar
                 P->n_aux = size_hint_aux;
                 P->n_con = size_hint_cons;
                 P->finalize();
-                it = progs.emplace(std::make_pair(L, T), std::move(P)).first;
+                it = progs.emplace(std::make_tuple(L, T, dd->sig), std::move(P)).first;
             }
             prog = it->second.get();
             dd->prog = prog;
@@ -842,6 +844,7 @@ static void synthesize_update(ConstraintSystem& cs, int L, int T, const ZkScalar
                 Num st_in = {VAR_ONE, state_in[t]};
                 const auto q0 = std::chrono::steady_clock::now();
                 Defer D{nullptr, false, dd ? dd->inputs.data() + t * (size_t)prog->n_inputs : nullptr, dd ? prog->n_inputs : 0u};
+                D.sig = dd && dd->sig;
                 if (dd) part.defer = &D;
                 outs[t] = synth_tx(part, L, T, accepted_fee_token, st_in, transitions[t]);
                 if (dd) chain_check(part, D, outs[t].state_out, state_in[t + 1]);
@@ -956,6 +959,7 @@ static Num run_tx_bodies(ConstraintSystem& cs, int nthreads, size_t n, std::pair
             static std::mutex mu;
             static std::map<uint64_t, std::unique_ptr<DeferProgram>> progs;
             std::lock_guard<std::mutex> lk(mu);
+            if (dd->sig) prog_key |= (uint64_t)1 << 40;  // a program per deferral level
             auto it = progs.find(prog_key);
             if (it == progs.end()) {
                 std::unique_ptr<DeferProgram> P(new DeferProgram());
@@ -963,6 +967,7 @@ static Num run_tx_bodies(ConstraintSystem& cs, int nthreads, size_t n, std::pair
                 ConstraintSystem plan(false);
                 plan.set_window(sa.data(), shape.first, sx.data(), sy.data(), sz.data(), shape.second);
                 Defer D{P.get(), true, sin.data(), (uint32_t)sin.size()};
+                D.sig = dd->sig;
                 plan.defer = &D;
                 LcModeGuard g(false);
                 const Num st_in = {VAR_ONE, state_in[0]};
@@ -999,6 +1004,7 @@ static Num run_tx_bodies(ConstraintSystem& cs, int nthreads, size_t n, std::pair
                                 cs.bz.data() + base_con + t * shape.second, cs.cz.data() + base_con + t * shape.second, shape.second);
                 const Num st_in = {VAR_ONE, state_in[t]};
                 Defer D{nullptr, false, dd ? dd->inputs.data() + t * (size_t)prog->n_inputs : nullptr, dd ? prog->n_inputs : 0u};
+                D.sig = dd && dd->sig;
                 if (dd) part.defer = &D;
                 const Num st_out = body(part, t, st_in);
                 if (dd) defer_chain_check(part, D, st_out, state_in[t + 1]);
@@ -1640,7 +1646,7 @@ int32_t bzk_mpn_update_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_t
         // or pure ProvingAssignment role (values only: no linear-combination bookkeeping at all)
         LcModeGuard guard(record_matrices != 0);
         r->cs.self_check = record_matrices != 0;
-        if (w->defer && !record_matrices) r->defer.reset(new DeferData());
+        if (w->defer && !record_matrices) { r->defer.reset(new DeferData()); r->defer->sig = w->defer_sig; }
         synthesize_update(r->cs, w->L, w->T, ZkScalar::from_bytes(commitment), w->height, state, aux, next_state, ft, trs, w->threads, r->defer.get());
         if (r->defer && !r->defer->prog) r->defer.reset();
         if (r->cs.check_failed_at >= 0) return BZK_E_INTERNAL;  // a gadget supplied a value that is not <LC, z>
@@ -1740,7 +1746,7 @@ int32_t bzk_mpn_deposit_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_
         std::unique_ptr<bzk_r1cs> r(new bzk_r1cs(record_matrices != 0));
         LcModeGuard guard(record_matrices != 0);
         r->cs.self_check = record_matrices != 0;
-        if (w->defer && !record_matrices) r->defer.reset(new DeferData());
+        if (w->defer && !record_matrices) { r->defer.reset(new DeferData()); r->defer->sig = w->defer_sig; }
         synthesize_deposit(r->cs, w->L, w->T, ZkScalar::from_bytes(commitment), w->height, state, aux, w->accounts->root(), trs, w->threads, r->defer.get());
         if (r->defer && !r->defer->prog) r->defer.reset();
         if (r->cs.check_failed_at >= 0) return BZK_E_INTERNAL;
@@ -1772,7 +1778,7 @@ int32_t bzk_mpn_withdraw_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8
         std::unique_ptr<bzk_r1cs> r(new bzk_r1cs(record_matrices != 0));
         LcModeGuard guard(record_matrices != 0);
         r->cs.self_check = record_matrices != 0;
-        if (w->defer && !record_matrices) r->defer.reset(new DeferData());
+        if (w->defer && !record_matrices) { r->defer.reset(new DeferData()); r->defer->sig = w->defer_sig; }
         synthesize_withdraw(r->cs, w->L, w->T, ZkScalar::from_bytes(commitment), w->height, state, aux, w->accounts->root(), trs, w->threads, r->defer.get());
         if (r->defer && !r->defer->prog) r->defer.reset();
         if (r->cs.check_failed_at >= 0) return BZK_E_INTERNAL;
@@ -1905,9 +1911,16 @@ const void* bzk_r1cs_data(const bzk_r1cs* r, int32_t which, uint64_t* bytes) {
 }
 
 // ---- deferred witness values (host_r1cs.h DeferProgram, bzk_witfill.cuh)
-int32_t bzk_mpn_set_defer(bzk_mpn* w, int32_t on) {
+int32_t bzk_mpn_set_defer(bzk_mpn* w, int32_t on) {  // 0 turns both levels off; non-zero: the hash-dependent values only (today's program)
     if (!w) return BZK_E_ARG;
     w->defer = on != 0;
+    w->defer_sig = false;
+    return BZK_OK;
+}
+int32_t bzk_mpn_set_defer_sig(bzk_mpn* w, int32_t on) {  // non-zero: deferral with the signature gadget (implies bzk_mpn_set_defer); 0: back to plain deferral
+    if (!w) return BZK_E_ARG;
+    if (on) w->defer = true;
+    w->defer_sig = on != 0;
     return BZK_OK;
 }
 // info: 0 deferred (1 / 0), 1 transitions, 2 ops, 3 registers, 4 inputs per transition, 5 levels of pass 1, 6 / 7 variable / constraint
@@ -2152,15 +2165,16 @@ int32_t bzk_mpn_work_synthesize(const bzk_mpn_work* h, const uint8_t prover_pub[
                                 int32_t record_matrices, bzk_r1cs** out) {
     if (!h || !prover_pub || !out) return BZK_E_ARG;
     *out = nullptr;
-    // 0 witness only, 1 with the CSR matrices, BZK_SYNTH_DEFER witness only with deferred values: anything else is a caller's mistake, not "non-zero = matrices"
-    if (record_matrices != 0 && record_matrices != 1 && record_matrices != (int32_t)BZK_SYNTH_DEFER) return BZK_E_ARG;
+    // 0 witness only, 1 with the CSR matrices, BZK_SYNTH_DEFER witness only with deferred values, BZK_SYNTH_DEFER_SIG the same with the signature
+    // gadget deferred as well: anything else is a caller's mistake, not "non-zero = matrices"
+    if (record_matrices != 0 && record_matrices != 1 && record_matrices != (int32_t)BZK_SYNTH_DEFER && record_matrices != (int32_t)BZK_SYNTH_DEFER_SIG) return BZK_E_ARG;
     try {
         const MpnWork& w = h->w;
         const int L = w.config.log4_tree, T = w.config.log4_token_tree, B = w.log4_batch();
         const size_t cap = (size_t)1 << (2 * B);
         const int nt = threads > 0 ? threads : host_default_threads();
         const ZkScalar commitment = mpn_work_commitment(prover_pub, w.reward);
-        const bool rec = record_matrices == 1, defer = record_matrices == BZK_SYNTH_DEFER;  // 0: witness only
+        const bool rec = record_matrices == 1, sig = record_matrices == BZK_SYNTH_DEFER_SIG, defer = record_matrices == BZK_SYNTH_DEFER || sig;  // 0: witness only
         std::unique_ptr<bzk_r1cs> r(new bzk_r1cs(rec));
         LcModeGuard guard(rec);
         r->cs.self_check = rec;
@@ -2168,19 +2182,19 @@ int32_t bzk_mpn_work_synthesize(const bzk_mpn_work* h, const uint8_t prover_pub[
             std::vector<UpdateTransition> trs = w.updates;
             while (trs.size() < cap) trs.push_back(UpdateTransition::null(L, T));
             const ZkScalar ft = fee_token ? ZkScalar::from_bytes(fee_token) : ZkScalar::one();
-            if (defer) r->defer.reset(new DeferData());
+            if (defer) { r->defer.reset(new DeferData()); r->defer->sig = sig; }
             synthesize_update(r->cs, L, T, commitment, w.height, w.state, w.aux_data, w.next_state, ft, trs, nt, r->defer.get());
             if (r->defer && !r->defer->prog) r->defer.reset();
         } else if (w.kind == 0) {
             std::vector<DepositTransition> trs = w.deposits;
             while (trs.size() < cap) trs.push_back(DepositTransition::null(L, T));
-            if (defer) r->defer.reset(new DeferData());
+            if (defer) { r->defer.reset(new DeferData()); r->defer->sig = sig; }
             synthesize_deposit(r->cs, L, T, commitment, w.height, w.state, w.aux_data, w.next_state, trs, nt, r->defer.get());
             if (r->defer && !r->defer->prog) r->defer.reset();
         } else {
             std::vector<WithdrawTransition> trs = w.withdraws;
             while (trs.size() < cap) trs.push_back(WithdrawTransition::null(L, T));
-            if (defer) r->defer.reset(new DeferData());
+            if (defer) { r->defer.reset(new DeferData()); r->defer->sig = sig; }
             synthesize_withdraw(r->cs, L, T, commitment, w.height, w.state, w.aux_data, w.next_state, trs, nt, r->defer.get());
             if (r->defer && !r->defer->prog) r->defer.reset();
         }

@@ -186,7 +186,8 @@ Schedule make_schedule(const DeferProgram& P) {
         stage(c);
     }
     std::vector<Seg> c;
-    for (const DeferGroup& g : P.f_groups) chunks_of(g, c);
+    for (const DeferGroup& g : P.f_groups)
+        if (g.kind != wf::F_LADDER) chunks_of(g, c);  // the ladders have launches of their own (wf_ladder_fill_kernel)
     stage(c);
     return S;
 }
@@ -308,6 +309,28 @@ __global__ void __launch_bounds__(256) wf_trace_all_kernel(TraceWidths W, TraceA
     else trace_coop<8>(W.ops[3], W.count[3], b - W.first_block[3], a, tab.dense[8], tab.rf[8], tab.rp[8]);
 }
 
+// ---- the signature gadget's ladders (Defer::sig, bzk_witfill.cuh V_LADDER / F_LADDER).  Pass 1: a lane per (ladder, transition) - a ladder is one dependent
+// chain of ~7 600 products (254 doublings and additions, the batch inversion) that reads no hash: it runs on a stream of its own beside the hash levels of
+// wf_pass1_coop_kernel.  Pass 2: a lane per (step or tail addition, ladder, transition), every slot written once.
+__global__ void __launch_bounds__(64) wf_ladder_kernel(const wf::Op* __restrict__ ops, uint32_t count, uint32_t n_tx, const Fr* __restrict__ inputs, uint32_t n_inputs,
+                                                     Fr* __restrict__ regs) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= count * n_tx) return;
+    const uint32_t tx = g % n_tx;
+    const wf::TxView v{inputs + (size_t)tx * n_inputs, regs + tx, n_tx, 0, 0, nullptr};
+    wf::v_ladder(ops[g / n_tx], v);
+}
+__global__ void __launch_bounds__(256) wf_ladder_fill_kernel(const wf::Op* __restrict__ ops, uint32_t count, uint32_t n_tx, const Fr* __restrict__ inputs,
+                                                           uint32_t n_inputs, Fr* __restrict__ regs, wf::Arrays A, size_t base_aux, size_t stride_aux, size_t base_con,
+                                                           size_t stride_con) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t lanes = wf::ladder_lanes(0);  // per (op, transition); the fixed base's lanes past its last step return at once
+    if (g >= (uint64_t)count * n_tx * lanes) return;
+    const uint32_t s = (uint32_t)(g % lanes), tx = (uint32_t)((g / lanes) % n_tx), o = (uint32_t)(g / ((uint64_t)lanes * n_tx));
+    const wf::TxView v{inputs + (size_t)tx * n_inputs, regs + tx, n_tx, base_aux + tx * stride_aux, base_con + tx * stride_con, nullptr};
+    wf::f_ladder(ops[o], v, A, s);
+}
+
 // pass-1 schedule of the cooperative form: per level and wave a run of segments (<= 8 hashes of one width = one wave-step), most expensive first
 struct CoopSchedule {
     std::vector<CSeg> segs;
@@ -363,6 +386,10 @@ struct CtxState {
     hipStream_t prio = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     bool prio_tried = false;
+    // the signature ladders (pass 1) on a stream of their own, forked after the input upload and joined before pass 2: they overlap the hash levels
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    bool side_tried = false;
 };
 
 int32_t tables(bzk_ctx* ctx, CtxState& S, int t) {
@@ -388,6 +415,7 @@ int32_t tables(bzk_ctx* ctx, CtxState& S, int t) {
 void witfill_quiesce(bzk_ctx* ctx) {  // a failed prove call: nothing of the program may still be reading the instance's input records
     CtxState* S = (CtxState*)ctx->wf_state;
     if (S && S->prio) (void)hipStreamSynchronize(S->prio);
+    if (S && S->side) (void)hipStreamSynchronize(S->side);
 }
 uint32_t witfill_flags(bzk_ctx* ctx) {  // after the stream of the last witfill_run_dev has been synchronised
     CtxState* S = (CtxState*)ctx->wf_state;
@@ -459,6 +487,7 @@ int32_t witfill_run_dev(bzk_ctx* ctx, const DeferData& dd, const wf::Arrays& A, 
         // the previous buffer may still be read by launches of an earlier call on this stream
         BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (S->prio) BZK_HIP(ctx, hipStreamSynchronize(S->prio));
+        if (S->side) BZK_HIP(ctx, hipStreamSynchronize(S->side));
         if (S->scratch) (void)hipFree(S->scratch);
         S->scratch = nullptr;
         S->scratch_bytes = 0;
@@ -501,12 +530,34 @@ int32_t witfill_run_dev(bzk_ctx* ctx, const DeferData& dd, const wf::Arrays& A, 
     StreamSwap swap(ctx, S->prio);
     const uint32_t ntx = (uint32_t)n_tx;
     const int32_t* dsel = it->second.sel;
+    // the signature ladders: their V ops lead v_ops (level 0), their F ops are one run of f_ops (finalize's order); none in a program without Defer::sig
+    uint32_t lv_start = 0, lv_count = 0, lf_start = 0, lf_count = 0;
+    for (const DeferGroup& g : P.v_groups)
+        if (g.kind == wf::V_LADDER) { if (!lv_count) lv_start = g.start; lv_count += g.count; }
+    for (const DeferGroup& g : P.f_groups)
+        if (g.kind == wf::F_LADDER) { if (!lf_count) lf_start = g.start; lf_count += g.count; }
+    auto ladders = [&]() -> int32_t {  // pass 1 of the ladders on ctx->stream
+        if (lv_count)
+            BZK_LAUNCH(ctx, "wf_ladder", wf_ladder_kernel, dim3((unsigned)(((uint64_t)lv_count * ntx + 63) / 64)), dim3(64), 0, (const wf::Op*)(it->second.v + lv_start),
+                       lv_count, ntx, (const Fr*)d_in, P.n_inputs, d_regs);
+        return BZK_OK;
+    };
+    auto ladder_fill = [&]() -> int32_t {  // pass 2 of the ladders on ctx->stream
+        if (lf_count) {
+            const uint64_t lanes = (uint64_t)lf_count * ntx * wf::ladder_lanes(0);
+            BZK_LAUNCH(ctx, "wf_ladder_fill", wf_ladder_fill_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (const wf::Op*)(it->second.f + lf_start), lf_count,
+                       ntx, (const Fr*)d_in, P.n_inputs, d_regs, A, dd.base_aux, dd.stride_aux, dd.base_con, dd.stride_con);
+        }
+        return BZK_OK;
+    };
     if (one_launch) {
         for (int t = 0; t < 9; ++t)
             if (t != 3 && t != 5 && t != 6 && t != 8 && S->tab.dense[t]) { ctx->last_error = "witfill: no device form for Poseidon width " + std::to_string(t); return BZK_E_INTERNAL; }
+        BZK_TRY(ladders());
         BZK_LAUNCH(ctx, "wf_tx", wf_tx_kernel, dim3(ntx), dim3(64 * WF_WAVES), 0, (const wf::Op*)it->second.v, (const wf::Op*)it->second.f, (const Seg*)it->second.segs,
                    (const uint32_t*)it->second.idx, it->second.n_stages, ntx, (const Fr*)d_in, P.n_inputs, d_regs, dsel, A, dd.base_aux, dd.stride_aux, dd.base_con,
                    dd.stride_con, S->tab, flags_dev);
+        BZK_TRY(ladder_fill());
         BZK_HIP(ctx, hipMemcpyAsync(flags_out, flags_dev, 4, hipMemcpyDeviceToHost, ctx->stream));
         if (S->prio) {
             BZK_HIP(ctx, hipEventRecord(S->ev_out, S->prio));
@@ -518,13 +569,40 @@ int32_t witfill_run_dev(bzk_ctx* ctx, const DeferData& dd, const wf::Arrays& A, 
     if (wf_mode == 2) {
         for (int t = 0; t < 9; ++t)
             if (t != 3 && t != 5 && t != 6 && t != 8 && S->tab.dense[t]) { ctx->last_error = "witfill: no device form for Poseidon width " + std::to_string(t); return BZK_E_INTERNAL; }
+        bool forked = false;
+        if (lv_count) {
+            if (!S->side_tried) {
+                S->side_tried = true;
+                if (hipStreamCreateWithFlags(&S->side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&S->ev_fork, hipEventDisableTiming) != hipSuccess ||
+                    hipEventCreateWithFlags(&S->ev_join, hipEventDisableTiming) != hipSuccess) {
+                    (void)hipGetLastError();
+                    if (S->side) (void)hipStreamDestroy(S->side);
+                    S->side = nullptr;  // no side stream: the ladders go in front of the hash levels on the program's stream
+                }
+            }
+            if (S->side) {
+                BZK_HIP(ctx, hipEventRecord(S->ev_fork, ctx->stream));
+                BZK_HIP(ctx, hipStreamWaitEvent(S->side, S->ev_fork, 0));
+                {
+                    StreamSwap on_side(ctx, S->side);
+                    BZK_TRY(ladders());
+                }
+                BZK_HIP(ctx, hipEventRecord(S->ev_join, S->side));
+                forked = true;
+            } else {
+                BZK_TRY(ladders());
+            }
+        }
         if (P.n_levels)
             BZK_LAUNCH(ctx, "wf_pass1", wf_pass1_coop_kernel, dim3(ntx), dim3(64 * WFC_WAVES), 0, (const wf::Op*)it->second.v, (const CSeg*)it->second.csegs,
                        (const uint32_t*)it->second.cidx, P.n_levels, ntx, (const Fr*)d_in, P.n_inputs, d_regs, dsel, S->tab);
+        if (forked) BZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, S->ev_join, 0));  // pass 2 reads the ladders' registers
+        BZK_TRY(ladder_fill());
         TraceWidths W{};
         const int width_of[4] = {3, 5, 6, 8};
         for (const DeferGroup& g : P.f_groups) {
             const wf::Op* o = it->second.f + g.start;
+            if (g.kind == wf::F_LADDER) continue;
             if (g.kind != wf::F_POSEIDON) {
                 BZK_LAUNCH(ctx, "wf_small", wf_small_kernel, blocks(g.count, 256), dim3(256), 0, o, g.count, ntx, (const Fr*)d_in, P.n_inputs, d_regs, dsel, A, dd.base_aux,
                            dd.stride_aux, dd.base_con, dd.stride_con, flags_dev);
@@ -555,9 +633,10 @@ int32_t witfill_run_dev(bzk_ctx* ctx, const DeferData& dd, const wf::Arrays& A, 
         return BZK_OK;
     }
     // pass 1
+    BZK_TRY(ladders());
     for (const DeferGroup& g : P.v_groups) {
         const wf::Op* o = it->second.v + g.start;
-        if (g.kind == wf::V_SEL) continue;  // resolved where they are read
+        if (g.kind == wf::V_SEL || g.kind == wf::V_LADDER) continue;  // selections: resolved where they are read
         const Fr29* c = S->tab.sparse[g.t];
         const int rf = S->tab.rf[g.t], rp = S->tab.rp[g.t];
         switch (g.t) {
@@ -569,8 +648,10 @@ int32_t witfill_run_dev(bzk_ctx* ctx, const DeferData& dd, const wf::Arrays& A, 
         }
     }
     // pass 2
+    BZK_TRY(ladder_fill());
     for (const DeferGroup& g : P.f_groups) {
         const wf::Op* o = it->second.f + g.start;
+        if (g.kind == wf::F_LADDER) continue;
         if (g.kind != wf::F_POSEIDON) {
             BZK_LAUNCH(ctx, "wf_small", wf_small_kernel, blocks(g.count, 256), dim3(256), 0, o, g.count, ntx, (const Fr*)d_in, P.n_inputs, d_regs, dsel, A, dd.base_aux,
                        dd.stride_aux, dd.base_con, dd.stride_con, flags_dev);
@@ -595,7 +676,8 @@ int32_t witfill_run_dev(bzk_ctx* ctx, const DeferData& dd, const wf::Arrays& A, 
 }
 
 // What the one-launch kernel will be handed for `P` (host-side check, no device needed): info = {stages, segments, V_HASH ops covered, F ops covered,
-// largest segment, violations}.  A violation: an op covered twice or not at all, a segment of more than 64 ops or of mixed kind / width, a hash segment in a
+// largest segment, violations}.  The signature ladders (V_LADDER / F_LADDER) are outside that schedule - they have launches of their own in every mode - and
+// are neither counted nor missed here.  A violation: an op covered twice or not at all, a segment of more than 64 ops or of mixed kind / width, a hash segment in a
 // stage other than its level's, an F segment before the last stage.
 void witfill_schedule_info(const DeferProgram& P, uint64_t info[6]) {
     const Schedule S = make_schedule(P);
@@ -623,7 +705,7 @@ void witfill_schedule_info(const DeferProgram& P, uint64_t info[6]) {
     for (size_t i = 0; i < P.v_ops.size(); ++i)
         if (P.v_ops[i].kind == wf::V_HASH && !seen_v[i]) ++bad;  // (selections are resolved where they are read: no segment of their own)
     for (size_t i = 0; i < P.f_ops.size(); ++i)
-        if (!seen_f[i]) ++bad;
+        if (!seen_f[i] && P.f_ops[i].kind != wf::F_LADDER) ++bad;
     if (P.max_sel_chain > (uint32_t)wf::MAX_SEL_CHAIN) ++bad;  // deeper than the device resolves where an operand is read
     if (env_on("BZK_WF_DUMP")) {  // the shape of the program on stderr: ops per (kind, width, level) - what a device schedule has to work with
         for (const DeferGroup& g : P.v_groups) fprintf(stderr, "[bzk] wf program: V kind %u width %u level %u: %u ops\n", g.kind, g.t, g.level, g.count);
@@ -655,6 +737,12 @@ void witfill_free(bzk_ctx* ctx) {  // bzk_ctx_destroy
     }
     if (S->ev_in) (void)hipEventDestroy(S->ev_in);
     if (S->ev_out) (void)hipEventDestroy(S->ev_out);
+    if (S->side) {
+        (void)hipStreamSynchronize(S->side);
+        (void)hipStreamDestroy(S->side);
+    }
+    if (S->ev_fork) (void)hipEventDestroy(S->ev_fork);
+    if (S->ev_join) (void)hipEventDestroy(S->ev_join);
     delete S;
     ctx->wf_state = nullptr;
 }
@@ -700,6 +788,7 @@ uint32_t witfill_run_host(const DeferData& dd, const wf::Arrays& A) {
             uint32_t f = 0;
             for (const wf::Op& op : P.v_ops) {
                 if (op.kind == wf::V_SEL) { wf::v_sel(op, v); continue; }
+                if (op.kind == wf::V_LADDER) { wf::v_ladder(op, v); continue; }
                 const Tab& T = tabs[op.t];
                 switch (op.t) {
                     case 3: wf::v_hash<3>(op, v, T.sparse.data(), T.rf, T.rp); break;
@@ -715,6 +804,9 @@ uint32_t witfill_run_host(const DeferData& dd, const wf::Arrays& A) {
                     case wf::F_ASSERT_EQ_IF: f |= wf::f_assert_eq_if(op, v, A); break;
                     case wf::F_ENFORCE_EQ: f |= wf::f_enforce_eq(op, v, A); break;
                     case wf::F_CHECK_EQ: f |= wf::f_check_eq(op, v); break;
+                    case wf::F_LADDER:
+                        for (uint32_t s = 0; s < wf::ladder_lanes(op.t); ++s) wf::f_ladder(op, v, A, s);
+                        break;
                     case wf::F_POSEIDON: {
                         const Tab& T = tabs[op.t];
                         switch (op.t) {

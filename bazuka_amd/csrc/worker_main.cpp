@@ -328,6 +328,7 @@ struct Options {
     long rounds = -1;
     bool self_check = false, dry_run = false;
     bool defer = false;  // --defer: BZK_SYNTH_DEFER + bzk_groth16_prove_r1cs (the hash-dependent witness values on the device: less host CPU per work)
+    bool defer_sig = false;  // --defer-sig: BZK_SYNTH_DEFER_SIG - the same and the EdDSA gadget's ladders (implies --defer)
     uint32_t flags = 0;
 };
 
@@ -385,7 +386,7 @@ uint64_t run_once(const Options& o, std::vector<Slot>& slots, Stats& st) {
         for (auto& w : works) {
             const auto t0 = clk::now();
             bzk_r1cs* r = nullptr;
-            const int32_t s = bzk_mpn_work_synthesize(w.w.get(), o.address, nullptr, o.threads, o.defer ? BZK_SYNTH_DEFER : 0, &r);
+            const int32_t s = bzk_mpn_work_synthesize(w.w.get(), o.address, nullptr, o.threads, o.defer_sig ? BZK_SYNTH_DEFER_SIG : o.defer ? BZK_SYNTH_DEFER : 0, &r);
             if (s != BZK_OK) {
                 failed("synthesis", w.id, bzk_strerror(s));
                 continue;
@@ -515,7 +516,7 @@ int usage(const char* why) {
     fprintf(stderr,
             "%s\nusage: bzk-worker --node HOST:PORT --address <64 hex> (--dev-toxic SEED | --params DEPOSIT WITHDRAW UPDATE)\n"
             "                  [--devices 0,1,..] [--slots-per-device N] [--threads N] [--poll S] [--rounds N] [--timeout S]\n"
-            "                  [--self-check] [--defer] [--sig-len-prefixed] [--dry-run]\n",
+            "                  [--self-check] [--defer] [--defer-sig] [--sig-len-prefixed] [--dry-run]\n",
             why);
     return 2;
 }
@@ -568,6 +569,8 @@ int main(int argc, char** argv) {
             o.timeout_s = atof(next());
         } else if (a == "--defer") {
             o.defer = true;
+        } else if (a == "--defer-sig") {
+            o.defer = o.defer_sig = true;
         } else if (a == "--self-check") {
             o.self_check = true;
         } else if (a == "--sig-len-prefixed") {

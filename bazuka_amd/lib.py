@@ -11,6 +11,8 @@ LIB_PATH = os.environ.get("BZK_LIBBZK") or os.path.join(_HERE, "libbzk.so")
 BZK_F_CANONICAL = 1
 BZK_F_DEDUP = 2
 BZK_F_THROUGHPUT = 4
+BZK_SYNTH_DEFER = 2        # bzk_mpn_work_synthesize's record_matrices: the hash-dependent values left to the device
+BZK_SYNTH_DEFER_SIG = 4    # ... and the EdDSA gadget's ladders
 
 
 def _flags(canonical=False, dedup=False, throughput=False) -> int:
@@ -121,6 +123,7 @@ SIGNATURES = {
     "bzk_r1cs_fill_host": (_i32, [_vp]),
     "bzk_r1cs_defer_schedule_info": (_i32, [_vp, C.POINTER(_u64)]),
     "bzk_mpn_set_defer": (_i32, [_vp, _i32]),
+    "bzk_mpn_set_defer_sig": (_i32, [_vp, _i32]),
     "bzk_r1cs_data": (_vp, [_vp, _i32, C.POINTER(_u64)]),
     "bzk_r1cs_free": (None, [_vp]),
     "bzk_host_poseidon": (_i32, [_vp, _u32, _vp]),
@@ -923,6 +926,10 @@ class MpnWorld:
         """witness-only update instances leave the hash-dependent values to the device (Bzk.groth16_prove_r1cs) or to R1cs.fill_host"""
         _st(self.lib.bzk_mpn_set_defer(self.h, 1 if on else 0), "set_defer")
 
+    def set_defer_sig(self, on: bool = True):
+        """set_defer and, beyond it, the EdDSA gadget's ladders (bzk_mpn_set_defer_sig); off: back to plain deferral"""
+        _st(self.lib.bzk_mpn_set_defer_sig(self.h, 1 if on else 0), "set_defer_sig")
+
     def set_device(self, ctx):
         """ctx: a Bzk context (kept alive by this object) whose GPU batches the builders' Merkle hashing; None: host path"""
         self._dev = ctx
@@ -1048,10 +1055,16 @@ class MpnWork:
         return buf.raw[: n.value]
 
     def synthesize(self, prover_pub: bytes, fee_token: bytes | None = None, threads: int = 0, record_matrices=False, defer=False) -> R1cs:
-        """defer: BZK_SYNTH_DEFER - a work's hash-dependent values (all three kinds: update, deposit, withdraw) are left to the device (Bzk.groth16_prove_r1cs) / R1cs.fill_host"""
+        """defer: BZK_SYNTH_DEFER - a work's hash-dependent values (all three kinds: update, deposit, withdraw) are left to the device (Bzk.groth16_prove_r1cs) / R1cs.fill_host;
+        defer="sig": BZK_SYNTH_DEFER_SIG - the same, and the EdDSA gadget of every update / withdraw transition as well"""
+        if defer == "sig":
+            mode = BZK_SYNTH_DEFER_SIG
+        elif isinstance(defer, str):
+            raise ValueError(f"defer={defer!r}: True, False or 'sig'")
+        else:
+            mode = BZK_SYNTH_DEFER if defer else int(record_matrices)
         h = C.c_void_p()
-        _st(self.lib.bzk_mpn_work_synthesize(self.h, _ptr(prover_pub), _ptr(fee_token), threads, 2 if defer else int(record_matrices), C.byref(h)),
-            "work_synthesize")
+        _st(self.lib.bzk_mpn_work_synthesize(self.h, _ptr(prover_pub), _ptr(fee_token), threads, mode, C.byref(h)), "work_synthesize")
         return R1cs(h)
 
 

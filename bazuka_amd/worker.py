@@ -234,7 +234,7 @@ class SlotKeys:
 # ---- the loop ----------------------------------------------------------------------------------------------------------
 class Worker:
     def __init__(self, bzk: L.Bzk, address: bytes, node: tuple[str, int], params_for, flags: int = 0, threads: int = 0,
-                 rng=os.urandom, timeout_s: float = 30.0, self_check: bool = False, extra_slots=(), defer: bool = False):
+                 rng=os.urandom, timeout_s: float = 30.0, self_check: bool = False, extra_slots=(), defer: bool | str = False):
         """self_check: verify every proof on the host with the work's own verifying key before posting it (bzk_groth16_verify =
         the check the node will run, src/mpn/mod.rs:281-295; ~20 ms of one core per proof) - a proof that fails is not posted.
         extra_slots: further (Bzk, params_for) prover slots - more slots on the same GPU (params_for = SlotKeys: shared CRS) and / or
@@ -245,7 +245,8 @@ class Worker:
         self.slots = [(bzk, params_for)] + list(extra_slots)
         self.flags, self.threads, self.rng, self.timeout_s, self.self_check = flags, threads, rng, timeout_s, self_check
         # defer: the host generator leaves the hash-dependent witness values to the device (BZK_SYNTH_DEFER + bzk_groth16_prove_r1cs: DESIGN.md 3.5) -
-        # fewer host CPU seconds per work, ~15 ms more GPU latency per proof; same proof statement, same acceptance test
+        # fewer host CPU seconds per work, ~15 ms more GPU latency per proof; same proof statement, same acceptance test.  "sig": the EdDSA gadget's
+        # ladders as well (BZK_SYNTH_DEFER_SIG)
         self.defer = defer
         self.stats = {"fetched": 0, "proved": 0, "accepted": 0, "unsat": 0, "self_check_failed": 0, "synth_s": 0.0, "prove_s": 0.0,
                       "proved_by_slot": [0] * len(self.slots)}
@@ -282,7 +283,7 @@ class Worker:
 
     def _synthesize(self, work: L.MpnWork):
         if self.defer:
-            return work.synthesize(self.address, threads=self.threads, defer=True)
+            return work.synthesize(self.address, threads=self.threads, defer=self.defer)
         return work.synthesize(self.address, threads=self.threads)
 
     def _prove_synthesized(self, work: L.MpnWork, r1cs, synth_s: float, slot: int = 0) -> bytes | None:
@@ -460,6 +461,7 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=None)
     ap.add_argument("--self-check", action="store_true", help="verify every proof on the host (pairing check) before posting it")
     ap.add_argument("--defer", action="store_true", help="leave the hash-dependent witness values to the GPU (less host CPU per work, ~15 ms more GPU latency per proof)")
+    ap.add_argument("--defer-sig", action="store_true", help="--defer, and the EdDSA gadget's ladders on the GPU as well (BZK_SYNTH_DEFER_SIG)")
     ap.add_argument("--sig-len-prefixed", action="store_true", help="node built against ed25519 < 1.3 (BZK_WORK_SIG_LEN_PREFIXED)")
     a = ap.parse_args(argv)
     host, port = a.node.rsplit(":", 1)
@@ -501,7 +503,7 @@ def main(argv=None):
             slots.append((bz, sk))
             closers = [sk, bz] + closers   # slots go before the keys they share
     w = Worker(slots[0][0], address, (host, int(port)), slots[0][1], flags=1 if a.sig_len_prefixed else 0, self_check=a.self_check,
-               extra_slots=slots[1:], defer=a.defer)
+               extra_slots=slots[1:], defer="sig" if a.defer_sig else a.defer)
     try:
         w.register()
         w.run_forever(a.poll, a.rounds)

@@ -403,12 +403,21 @@ void bzk_r1cs_free(bzk_r1cs* r);
  * wrote; the deferred rows are judged where they are computed (BZK_E_UNSAT from the prove call, info[9] after a host fill).
  *   defer_info: 0 deferred (1 / 0), 1 transitions, 2 ops of the program, 3 registers, 4 host-known values per transition, 5 dependency levels
  *               (a Merkle path is a chain of hashes), 6 / 7 variable / constraint slots per transition left to the device, 8 filled on the
- *               host (1 / 0), 9 flags of that fill (1 a deferred constraint does not hold, 2 a computed state differs from the builder's) */
+ *               host (1 / 0), 9 flags of that fill (1 a deferred constraint does not hold, 2 a computed state differs from the builder's)
+ * A second, opt-in level: bzk_mpn_set_defer_sig(w, 1) (or BZK_SYNTH_DEFER_SIG) defers the EdDSA gadget of every Update and Withdraw transition as well
+ * (src/zk/groth16/gadgets/eddsa/mod.rs:77-280): its two 254-step double-and-add ladders and the four additions of its tail, 254 x (20 + 14) + 36 = 8 672
+ * variables and as many constraints per signature, and its two final checks.  The hash of (R, pk, msg), both bit decompositions and the first bit's
+ * muxes stay on the host.  The device computes the ladders' points (one inversion per ladder) before it fills their slots; a signature that does not
+ * verify is reported like every deferred check (BZK_E_UNSAT, flags & 1).  It shows in defer_info's op, register, input and hole counts.  Deposit
+ * has no signature gadget: its instance equals the BZK_SYNTH_DEFER one.  bzk_mpn_set_defer_sig implies bzk_mpn_set_defer; bzk_mpn_set_defer(w, 0)
+ * turns both off, bzk_mpn_set_defer(w, 1) selects the first level alone - exactly the program it recorded before the second level existed. */
 int32_t bzk_mpn_set_defer(bzk_mpn* w, int32_t on);
+int32_t bzk_mpn_set_defer_sig(bzk_mpn* w, int32_t on);
 int32_t bzk_r1cs_defer_info(const bzk_r1cs* r, uint64_t info[10]);
 int32_t bzk_r1cs_fill_host(bzk_r1cs* r);
 /* the schedule of the instance's program for the one-launch device kernel, checked on the host (no device needed): stages, segments, hash ops
- * covered, fill ops covered, largest segment (<= 64), violations (0: every op exactly once, in a stage its operands are ready for) */
+ * covered, fill ops covered, largest segment (<= 64), violations (0: every op exactly once, in a stage its operands are ready for).  The signature
+ * ladders of BZK_SYNTH_DEFER_SIG are not part of that schedule (they run in launches of their own, before and after it): neither counted nor missed */
 int32_t bzk_r1cs_defer_schedule_info(const bzk_r1cs* r, uint64_t info[6]);
 /* bzk_groth16_prove over an instance of the host generator (z / A.z / B.z / C.z are the instance's own pinned arrays), completing deferred
  * witness values on the device first.  BZK_E_UNSAT: a deferred constraint does not hold or a transition's computed state differs from the
@@ -457,8 +466,10 @@ int32_t bzk_mpn_work_commitment(const bzk_mpn_work* work, const uint8_t prover_p
 int32_t bzk_mpn_work_verify(const bzk_mpn_work* work, const uint8_t prover_pub[32], const uint8_t proof[387]);
 /* the circuit instance to prove: transitions padded with null ones to 4^batch; fee_token NULL = Ziesha; threads 0 = all;
  * record_matrices: 0 witness only, 1 with the CSR matrices (setup), BZK_SYNTH_DEFER witness only with the hash-dependent values of the
- * work's transitions left to the device (see bzk_mpn_set_defer; all three kinds) */
+ * work's transitions left to the device (see bzk_mpn_set_defer; all three kinds), BZK_SYNTH_DEFER_SIG the same with the signature gadget deferred too
+ * (bzk_mpn_set_defer_sig; 4, not 3: every value but 0, 1 and 2 was refused with BZK_E_ARG before, and 3 stays refused) */
 #define BZK_SYNTH_DEFER 2
+#define BZK_SYNTH_DEFER_SIG 4
 int32_t bzk_mpn_work_synthesize(const bzk_mpn_work* work, const uint8_t prover_pub[32], const uint8_t fee_token[32],
                                 int32_t threads, int32_t record_matrices, bzk_r1cs** out);
 int32_t bzk_mpn_work_encode(const bzk_mpn_work* work, uint8_t* out, uint64_t cap, uint64_t* len); /* out NULL: size query */

@@ -359,6 +359,22 @@ pub fn synthesize_work_deferred(work: &MpnWork, prover: &Address) -> Result<Witn
     Ok(Witness(r1cs))
 }
 
+/// `synthesize_work_deferred` with the EdDSA gadget of every Update / Withdraw transition deferred as well (include/bzk.h: BZK_SYNTH_DEFER_SIG): its two
+/// 254-step ladders and the signature's tail are computed and filled in on the GPU by `groth16_prove_witness`.  A signature that does not verify arrives as
+/// `BZK_E_UNSAT` from the prove call.  Deposit works have no signature gadget: their instance is `synthesize_work_deferred`'s.
+pub fn synthesize_work_deferred_sig(work: &MpnWork, prover: &Address) -> Result<Witness, GpuError> {
+    let bytes = bincode::serialize(work)?;
+    let prover_pub = bincode::serialize(prover)?;
+    let mut w = ptr::null_mut();
+    let mut consumed = 0u64;
+    check(ptr::null_mut(), unsafe { sys::bzk_mpn_work_decode(bytes.as_ptr(), bytes.len() as u64, 0, &mut w, &mut consumed) })?;
+    let mut r1cs = ptr::null_mut();
+    let st = unsafe { sys::bzk_mpn_work_synthesize(w, prover_pub.as_ptr(), ptr::null(), 0, sys::BZK_SYNTH_DEFER_SIG as i32, &mut r1cs) };
+    unsafe { sys::bzk_mpn_work_free(w) };
+    check(ptr::null_mut(), st)?;
+    Ok(Witness(r1cs))
+}
+
 /// `groth16_prove` over the generator's own instance handle: a deferred instance is completed on the device first.  `BZK_E_UNSAT` (a
 /// deferred constraint does not hold) arrives as `GpuError::Status`, never as a panic.
 pub fn groth16_prove_witness(params: &ProvingParams, witness: &Witness, r: ZkScalar, s: ZkScalar) -> Result<Groth16Proof, GpuError> {

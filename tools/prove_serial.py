@@ -4,6 +4,7 @@ per-kernel table of ONE proof (what the rocPRIM sorts, the de-duplication and ev
 
     BZK_PROVE_SERIAL=1 rocprofv3 --kernel-trace --stats -d out -- python tools/prove_serial.py 6
 
+PROVE_DEFER=2: the same with the EdDSA gadget's ladders deferred as well (bzk_mpn_set_defer_sig: the wf_ladder / wf_ladder_fill kernels in a trace).
 PROVE_DEFER=1: the witness generator leaves the hash-dependent values to the device (bzk_mpn_set_defer) and the proofs go through
 bzk_groth16_prove_r1cs - the trace then also shows the witness-fill kernels (wf_hash / wf_poseidon / wf_small).
 
@@ -33,6 +34,8 @@ def main(n_proofs=6):
     ts = []
     defer = os.environ.get("PROVE_DEFER", "0") != "0"
     w.set_defer(defer)
+    if os.environ.get("PROVE_DEFER", "0") == "2":
+        w.set_defer_sig(True)
     for k in range(n_proofs):
         batch(k + 1)
         rk = w.update_synthesize(2, _fr(99), Z)

@@ -92,6 +92,7 @@ struct bzk_ctx {
     hipEvent_t ev_heavy_in = nullptr, ev_heavy_out = nullptr;
     bool heavy_tried = false;
     bool heavy_force = false;  // a later window range of a split call (msm_run_split, priority mode 2): HeavyScope applies whatever BZK_MSM_HEAVY_PRIO says
+    void* eddsa_tab = nullptr;  // eddsa.hip: the signature verifier's fixed-base table (multiples of Jubjub's BASE, 29-bit form), built on first use
     void* wf_state = nullptr;  // witfill.hip: device copies of the deferred-witness programs, dense Poseidon constants, scratch (witfill_free)
     // bzk_r1cs_stage: staged assignments handed back by bzk_staged_free (possibly from another thread: the prover's), kept for the next call
     std::mutex staged_mu;
@@ -143,6 +144,8 @@ struct WsCursor {
     }
 };
 void witfill_free(bzk_ctx* ctx);  // witfill.hip
+// eddsa.hip: ok_dev[i] = verdict of signature i; device pointers, enqueued on the context's stream under the launch label "jubjub_verify"
+int32_t jubjub_verify_launch(bzk_ctx* ctx, const void* pub_xy_dev, const void* msg_dev, const void* sig_dev, uint64_t n, void* ok_dev);
 int32_t ntt_run(bzk_ctx* ctx, void* data_dev, uint32_t log_n, int inverse, int coset);  // ntt.hip
 int32_t ntt_h_chain(bzk_ctx* ctx, void* a, void* b, void* c, uint32_t log_m);              // ntt.hip: the h polynomial's 7 transforms, fused
 // msm_g1.hip / msm_g2.hip: windows [w_begin, w_end) (w_end < 0: all) of an MSM over a resident base set (or raw bases when `bases` is

@@ -1312,7 +1312,50 @@ static void build_withdraws(bzk_mpn& w, int log4_batch, std::vector<WithdrawTran
     w.withdraw_queue.swap(rest);
 }
 
-// withdraw::withdraw (src/mpn/withdraw.rs:10-259) with the Merkle work batched on the device (see DevBatch)
+// The signature checks of a withdraw queue on the device: the sign messages H2(fingerprint, nonce) of the whole queue in one Poseidon batch (on first
+// use), the signatures in chunks of the batch capacity (bzk_jubjub_verify_batch, launch label "jubjub_verify"), each chunk when the builder's loop first asks for a verdict in it.
+// A verdict depends on the transaction alone, not on account state, so checking ahead of the loop changes nothing the loop decides.
+struct SigBatch {
+    bzk_ctx* ctx;
+    const std::vector<WithdrawTx>& queue;
+    size_t chunk;
+    std::vector<uint8_t> msgs, ok;  // msgs: queue x 32 once hashed
+    std::vector<bool> have;         // per chunk
+    SigBatch(bzk_ctx* c, const std::vector<WithdrawTx>& q, size_t cap) : ctx(c), queue(q), chunk(cap ? cap : 1) {}
+    int32_t verdict(size_t i, bool& out) {
+        const size_t n = queue.size();
+        if (msgs.empty()) {
+            std::vector<uint8_t> in(n * 64);
+            for (size_t k = 0; k < n; ++k) {
+                queue[k].fingerprint.to_bytes(&in[k * 64]);
+                ZkScalar::from_u64(queue[k].nonce).to_bytes(&in[k * 64 + 32]);
+            }
+            msgs.resize(n * 32);
+            BZK_TRY(bzk_poseidon_batch(ctx, in.data(), 2, n, msgs.data()));
+            ok.assign(n, 0);
+            have.assign((n + chunk - 1) / chunk, false);
+        }
+        const size_t c = i / chunk;
+        if (!have[c]) {
+            const size_t lo = c * chunk, m = (n - lo < chunk ? n - lo : chunk);
+            std::vector<uint8_t> pub(m * 64), sig(m * 96);
+            for (size_t k = 0; k < m; ++k) {
+                const WithdrawTx& tx = queue[lo + k];
+                tx.mpn_address.x.to_bytes(&pub[k * 64]);
+                tx.mpn_address.y.to_bytes(&pub[k * 64 + 32]);
+                tx.sig.r.x.to_bytes(&sig[k * 96]);
+                tx.sig.r.y.to_bytes(&sig[k * 96 + 32]);
+                tx.sig.s.to_bytes(&sig[k * 96 + 64]);
+            }
+            BZK_TRY(bzk_jubjub_verify_batch(ctx, pub.data(), &msgs[lo * 32], sig.data(), m, &ok[lo]));
+            have[c] = true;
+        }
+        out = ok[i] != 0;
+        return BZK_OK;
+    }
+};
+
+// withdraw::withdraw (src/mpn/withdraw.rs:10-259) with the Merkle work batched on the device (see DevBatch); the signatures likewise (SigBatch)
 static int32_t build_withdraws_dev(bzk_mpn& w, int log4_batch, std::vector<WithdrawTransition>& out, uint64_t& rejected) {
     const size_t cap = (size_t)1 << (2 * log4_batch);
     rejected = 0;
@@ -1321,7 +1364,10 @@ static int32_t build_withdraws_dev(bzk_mpn& w, int log4_batch, std::vector<Withd
     struct Rec { size_t ev_ti, ev_fi, leaf; };
     std::vector<Rec> recs;
     std::vector<WithdrawTx> rest;
+    SigBatch sigs(w.dev, w.withdraw_queue, cap);
+    size_t qi = 0;
     for (const WithdrawTx& tx : w.withdraw_queue) {
+        const size_t q = qi++;
         if (out.size() == cap) { rest.push_back(tx); continue; }
         long index = -1;
         for (auto& kv : w.acct)
@@ -1331,8 +1377,14 @@ static int32_t build_withdraws_dev(bzk_mpn& w, int log4_batch, std::vector<Withd
         long ti = acc.find_token_index(w.L, tx.amount.token_id, false), fi = acc.find_token_index(w.L, tx.fee.token_id, false);
         if (ti < 0 || fi < 0 || !acc.tokens.count(ti)) { ++rejected; continue; }
         const Money acc_token = acc.tokens[ti];
+        bool sig_ok = false;
+        if (const int32_t st = sigs.verdict(q, sig_ok); st != BZK_OK) {  // as when B.run fails below: nothing of the batch stays behind
+            undo.rollback();
+            out.resize(out.size() - recs.size());
+            return st;
+        }
         if ((!(acc.address == PointAffine()) && !(tx.mpn_address == acc.address)) ||
-            !jubjub_verify(tx.mpn_address, tx.sign_message(), tx.sig) || tx.nonce != acc.withdraw_nonce + 1 ||
+            !sig_ok || tx.nonce != acc.withdraw_nonce + 1 ||
             tx.amount.token_id != acc_token.token_id || tx.amount.amount > acc_token.amount) {
             ++rejected;
             continue;
@@ -1726,6 +1778,21 @@ int32_t bzk_mpn_push_withdraw(bzk_mpn* w, uint64_t account_index, const uint8_t 
         tx.sig = jubjub_sign(w->keys[account_index], tx.sign_message());
         tx.payment = default_contract_withdraw(w->contract_id, tx.amount, tx.fee, tx.calldata());
     }
+    w->withdraw_queue.push_back(tx);
+    return BZK_OK;
+}
+
+// a withdrawal signed elsewhere, queued as given (a validator's case): the builder is what checks the signature
+int32_t bzk_mpn_push_withdraw_signed(bzk_mpn* w, const uint8_t pub_xy[64], uint32_t nonce, const uint8_t token_id[32], uint64_t amount,
+                                     const uint8_t fee_token[32], uint64_t fee, const uint8_t fingerprint[32], const uint8_t sig[96]) {
+    if (!w || !pub_xy || !token_id || !fee_token || !fingerprint || !sig) return BZK_E_ARG;
+    WithdrawTx tx;
+    tx.mpn_address = {ZkScalar::from_bytes(pub_xy), ZkScalar::from_bytes(pub_xy + 32)};
+    tx.nonce = nonce;
+    tx.amount = Money{ZkScalar::from_bytes(token_id), amount};
+    tx.fee = Money{ZkScalar::from_bytes(fee_token), fee};
+    tx.fingerprint = ZkScalar::from_bytes(fingerprint);  // opaque: no wire form
+    tx.sig = {{ZkScalar::from_bytes(sig), ZkScalar::from_bytes(sig + 32)}, ZkScalar::from_bytes(sig + 64)};
     w->withdraw_queue.push_back(tx);
     return BZK_OK;
 }

@@ -43,6 +43,8 @@ SIGNATURES = {
     "bzk_prof_dump": (_i32, [_vp, _vp, _u64]),
     "bzk_poseidon_batch": (_i32, [_vp, _vp, _u32, _u64, _vp]),
     "bzk_poseidon_batch_dev": (_i32, [_vp, _vp, _u32, _u64, _vp]),
+    "bzk_jubjub_verify_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_jubjub_verify_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_merkle4_root": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_merkle4_root_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_state_compress": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
@@ -113,6 +115,7 @@ SIGNATURES = {
     "bzk_mpn_tree_prove_token": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_mpn_push_deposit": (_i32, [_vp, _u64, _vp, _u64]),
     "bzk_mpn_push_withdraw": (_i32, [_vp, _u64, _vp, _u64, _vp, _u64, _vp]),
+    "bzk_mpn_push_withdraw_signed": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
     "bzk_mpn_deposit_synthesize": (_i32, [_vp, _u32, _vp, _i32, C.POINTER(_vp)]),
     "bzk_mpn_withdraw_synthesize": (_i32, [_vp, _u32, _vp, _i32, C.POINTER(_vp)]),
     "bzk_mpn_circuit_empty": (_i32, [_i32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _i32, C.POINTER(_vp)]),
@@ -340,6 +343,15 @@ class Bzk:
         self._ck(self.lib.bzk_poseidon_batch(self.h, _ptr(inp), arity, n, out), "poseidon_batch")
         return out.raw[: 32 * n]
 
+    def jubjub_verify_batch(self, pub_xy: bytes, msg: bytes, sig: bytes) -> bytes:
+        """n = len(msg) / 32 signatures (pub_xy n x 64, sig n x 96 = r.x | r.y | s): one verdict byte each, 1 / 0"""
+        n = len(msg) // 32
+        if len(pub_xy) != 64 * n or len(sig) != 96 * n or len(msg) != 32 * n:
+            raise BzkError("jubjub_verify_batch: pub_xy, msg and sig describe different counts")
+        out = C.create_string_buffer(max(n, 1))
+        self._ck(self.lib.bzk_jubjub_verify_batch(self.h, _ptr(pub_xy), _ptr(msg), _ptr(sig), n, out), "jubjub_verify_batch")
+        return out.raw[:n]
+
     def merkle4_root(self, leaves: bytes, log4: int, want_nodes: bool = False):
         root = C.create_string_buffer(32)
         nn = (4 ** log4 - 1) // 3
@@ -367,6 +379,10 @@ class Bzk:
     # ---- device-pointer forms (x = torch tensor / int device address)
     def poseidon_batch_dev(self, inp, arity: int, n: int, out):
         self._ck(self.lib.bzk_poseidon_batch_dev(self.h, _ptr(inp), arity, n, _ptr(out)), "poseidon_batch_dev")
+
+    def jubjub_verify_batch_dev(self, pub_xy, msg, sig, n: int, ok):
+        """device buffers; ok: n verdict bytes, written in stream order"""
+        self._ck(self.lib.bzk_jubjub_verify_batch_dev(self.h, _ptr(pub_xy), _ptr(msg), _ptr(sig), n, _ptr(ok)), "jubjub_verify_batch_dev")
 
     def merkle4_root_dev(self, leaves, log4: int, nodes=None) -> bytes:
         root = C.create_string_buffer(32)
@@ -957,6 +973,11 @@ class MpnWorld:
     def push_withdraw(self, account: int, token_id: bytes, amount: int, fee_token: bytes, fee: int, fingerprint: bytes | None = None):
         """fingerprint None: derived from a synthetic L1 payment as the wallet does (the withdrawal can go on the wire)"""
         _st(self.lib.bzk_mpn_push_withdraw(self.h, account, _ptr(token_id), amount, _ptr(fee_token), fee, _ptr(fingerprint)), "push_withdraw")
+
+    def push_withdraw_signed(self, pub_xy: bytes, nonce: int, token_id: bytes, amount: int, fee_token: bytes, fee: int, fingerprint: bytes, sig: bytes):
+        """a withdrawal signed elsewhere (sig = r.x | r.y | s over H2(fingerprint, nonce)), queued as given; the builder checks it"""
+        _st(self.lib.bzk_mpn_push_withdraw_signed(self.h, _ptr(pub_xy), nonce, _ptr(token_id), amount, _ptr(fee_token), fee, _ptr(fingerprint),
+                                                  _ptr(sig)), "push_withdraw_signed")
 
     def make_work(self, kind: int, vks, reward: int, log4_batches=(1, 1, 1), num_batches=(1, 1, 1), state_size: int = 0) -> "MpnWork":
         """validator side (`prepare_works`): one work from the queued transactions.  kind 0 deposit / 1 withdraw / 2 update;

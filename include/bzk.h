@@ -101,6 +101,14 @@ int32_t bzk_prof_dump(bzk_ctx* ctx, char* buf, uint64_t cap);
 int32_t bzk_poseidon_batch(bzk_ctx* ctx, const uint8_t* in, uint32_t arity, uint64_t n, uint8_t* out);
 int32_t bzk_poseidon_batch_dev(bzk_ctx* ctx, const void* in_dev, uint32_t arity, uint64_t n, void* out_dev);
 
+/* ---- batched EdDSA verification -------------------------------------------------------------------
+ * JubJub::<ZkHasher>::verify (src/crypto/jubjub/mod.rs:151-167) for n independent (key, message, signature) triples.
+ * pub_xy: n x 64, msg: n x 32, sig: n x 96 (r.x | r.y | s) - the layouts of bzk_host_jubjub_verify.  ok: n bytes, 1 / 0.
+ * n = 0 is a no-op.  A 32-byte field that is not the limbs of a residue gives verdict 0 for its entry, not an error.  The host
+ * form stages through the context's workspace and synchronises; the _dev form enqueues on the context's stream. */
+int32_t bzk_jubjub_verify_batch(bzk_ctx* ctx, const uint8_t* pub_xy, const uint8_t* msg, const uint8_t* sig, uint64_t n, uint8_t* ok);
+int32_t bzk_jubjub_verify_batch_dev(bzk_ctx* ctx, const void* pub_xy_dev, const void* msg_dev, const void* sig_dev, uint64_t n, void* ok_dev);
+
 /* ---- K2: dense 4-ary ZkState tree re-hash ----------------------------------------------------
  * Root of `ZkStateModel::List{log4_size, Scalar}` with every leaf present, as
  * `ZkStateBuilder::compress` / `KvStoreStateManager::root` would give (src/zk/state/mod.rs:66-90,
@@ -376,6 +384,10 @@ int32_t bzk_mpn_push_deposit(bzk_mpn* w, uint64_t key_index, const uint8_t token
  * (src/wallet/tx_builder.rs:376-425); non-NULL: an opaque fingerprint (such a withdrawal cannot be put on the wire) */
 int32_t bzk_mpn_push_withdraw(bzk_mpn* w, uint64_t account_index, const uint8_t token_id[32], uint64_t amount,
                               const uint8_t fee_token[32], uint64_t fee, const uint8_t fingerprint[32]);
+/* a withdrawal signed elsewhere, queued as given: the key need not be one the world holds, the signature (r.x | r.y | s over
+ * H2(fingerprint, nonce)) is only checked by the builder.  Opaque fingerprint, so no wire form (see above). */
+int32_t bzk_mpn_push_withdraw_signed(bzk_mpn* w, const uint8_t pub_xy[64], uint32_t nonce, const uint8_t token_id[32], uint64_t amount,
+                                     const uint8_t fee_token[32], uint64_t fee, const uint8_t fingerprint[32], const uint8_t sig[96]);
 int32_t bzk_mpn_deposit_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_t commitment[32], int32_t record_matrices, bzk_r1cs** out);
 int32_t bzk_mpn_withdraw_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_t commitment[32], int32_t record_matrices, bzk_r1cs** out);
 /* all-disabled instances (kind 0 = deposit, 1 = withdraw), src/mpn/circuits/test.rs:151-229 */

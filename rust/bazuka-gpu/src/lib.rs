@@ -7,6 +7,7 @@
 //!
 //! Each public item names the reference interface it stands beside (paths relative to ziesha-network/bazuka v0.19.20):
 //!   * `GpuPoseidonHasher`      - `impl ZkHasher` (src/zk/mod.rs:152-155, 496-511) + the BULK path `hash_batch`
+//!   * `Gpu::jubjub_verify_batch` - `JubJub::<ZkHasher>::verify` (src/crypto/jubjub/mod.rs:151-167) for many signatures at once
 //!   * `groth16_prove`          - beside `groth16_verify` (src/zk/groth16/mod.rs:67-75), same argument order
 //!   * `compress`               - `ZkStateModel::compress::<H>(&data)` (src/zk/mod.rs:392-399)
 //!   * `DeviceStateManager`     - `KvStoreStateManager::{update_contract, root, get_data, prove}` (src/zk/state/mod.rs:218-438) for one
@@ -23,6 +24,7 @@
 //! Layout assumptions (already relied upon by the reference's own `transmute`s, src/zk/groth16/mod.rs:7-17): `ZkScalar` is
 //! `[u64; 4]` little-endian Montgomery limbs; bincode 1.3 with default options; `Groth16Proof` = 97 + 193 + 97 bytes under bincode.
 use bazuka::core::Address;
+use bazuka::crypto::jubjub::{PublicKey, Signature};
 use bazuka::mpn::MpnWork;
 use bazuka::zk::groth16::Groth16Proof;
 use bazuka::zk::{
@@ -74,6 +76,24 @@ impl Gpu {
         let mut out = vec![ZkScalar::default(); n];
         check(self.0, unsafe { sys::bzk_poseidon_batch(self.0, scalars_ptr(vals), arity as u32, n as u64, out.as_mut_ptr() as *mut u8) })?;
         Ok(out)
+    }
+
+    /// Bulk `JubJub::<PoseidonHasher>::verify(pk, msg, sig)` (src/crypto/jubjub/mod.rs:151-167): one verdict per (key, message, signature).
+    /// Keys are decompressed here, on the host (`PublicKey::decompress`, a square root each); everything else runs on the device.
+    pub fn jubjub_verify_batch(&self, items: &[(PublicKey, ZkScalar, Signature)]) -> Result<Vec<bool>, GpuError> {
+        let n = items.len();
+        let (mut pk, mut msg, mut sig) = (Vec::with_capacity(2 * n), Vec::with_capacity(n), Vec::with_capacity(3 * n));
+        for (k, m, s) in items {
+            let p = k.decompress();
+            pk.extend_from_slice(&[p.0, p.1]);
+            msg.push(*m);
+            sig.extend_from_slice(&[s.r.0, s.r.1, s.s]);
+        }
+        let mut ok = vec![0u8; n];
+        check(self.0, unsafe {
+            sys::bzk_jubjub_verify_batch(self.0, scalars_ptr(&pk), scalars_ptr(&msg), scalars_ptr(&sig), n as u64, ok.as_mut_ptr())
+        })?;
+        Ok(ok.into_iter().map(|b| b != 0).collect())
     }
 
     /// Root of a dense `ZkStateModel::List { log4_size, item_type: Scalar }` (what `ZkStateBuilder::compress` returns for it)

@@ -146,6 +146,20 @@ struct WsCursor {
 void witfill_free(bzk_ctx* ctx);  // witfill.hip
 // eddsa.hip: ok_dev[i] = verdict of signature i; device pointers, enqueued on the context's stream under the launch label "jubjub_verify"
 int32_t jubjub_verify_launch(bzk_ctx* ctx, const void* pub_xy_dev, const void* msg_dev, const void* sig_dev, uint64_t n, void* ok_dev);
+// eddsa.hip: xy_dev[i] = x | y of key i (zeros where it does not decompress), ok_dev[i] = 1 / 0; launch label "jubjub_decompress"
+int32_t jubjub_decompress_launch(bzk_ctx* ctx, const void* x_dev, const void* odd_dev, uint64_t n, void* xy_dev, void* ok_dev);
+// n parsed MpnTransactions as the arrays the device stages (host memory; mpn.hip fills them from bincode without any field arithmetic)
+struct TxSoA {
+    const uint8_t *src_x, *dst_x;      // n x 32: PointCompressed.0
+    const uint8_t *src_odd, *dst_odd;  // n: PointCompressed.1
+    const uint8_t* tok;                // n x 64: amount token id | fee token id as scalars
+    const uint64_t* nums;              // n x 3: nonce, amount, fee
+    const uint8_t* sig;                // n x 96: r.x | r.y | s
+};
+constexpr uint64_t MPN_TX_CHUNK = (uint64_t)1 << 16;  // transactions staged per round of launches: where the signature kernel's rate has levelled off
+// eddsa.hip: MpnTransaction::verify_signature for each; ok n bytes; hash_out n x 32, src_xy_out / dst_xy_out n x 64 (the decompressed keys) or null;
+// synchronises
+int32_t mpn_tx_verify_run(bzk_ctx* ctx, const TxSoA& t, uint64_t n, uint8_t* ok, uint8_t* hash_out, uint8_t* src_xy_out, uint8_t* dst_xy_out);
 int32_t ntt_run(bzk_ctx* ctx, void* data_dev, uint32_t log_n, int inverse, int coset);  // ntt.hip
 int32_t ntt_h_chain(bzk_ctx* ctx, void* a, void* b, void* c, uint32_t log_m);              // ntt.hip: the h polynomial's 7 transforms, fused
 // msm_g1.hip / msm_g2.hip: windows [w_begin, w_end) (w_end < 0: all) of an MSM over a resident base set (or raw bases when `bases` is

@@ -5,12 +5,13 @@
 // The hash is a quarter of a verification and shares its kernel with the ladders: its MDS matrix is re-read in every full round (scalar loads) instead of
 // being hoisted out of the round loop into 324 scalars the register file does not have (bzk_poseidon29.cuh)
 #define BZK_POSEIDON_MDS_RELOAD 1
-#include "bzk_eddsa.cuh"
+#include "bzk_decompress.cuh"
 #include "bzk_internal.h"
 
 namespace bzk {
 
 int32_t poseidon_consts_dev_shared(bzk_ctx* ctx, int t, const void** out, int* rf, int* rp);  // poseidon.hip
+int32_t poseidon_launch(bzk_ctx* ctx, const void* in_dev, uint32_t arity, uint64_t n, void* out_dev);       // poseidon.hip
 
 // One wave per block: the lanes share nothing but the block's LDS, where lane l keeps its table {1, 2, 3, 4} pk in column l (word k at lds[64 k + l]:
 // consecutive lanes, consecutive banks).  27 KB per block, five blocks per CU.
@@ -22,6 +23,40 @@ __global__ void __launch_bounds__(EDDSA_BLOCK) jubjub_verify_kernel(const Fr* __
     const uint64_t i = (uint64_t)blockIdx.x * EDDSA_BLOCK + threadIdx.x;
     if (i >= n) return;
     ok[i] = eddsa::verify_one(pub + 2 * i, msg + i, sig + 3 * i, pconsts, rf, rp, base_tab, lds + threadIdx.x, EDDSA_BLOCK);
+}
+
+// Key decompression, one lane per key (bzk_decompress.cuh decompress_one): a dependent chain of about a thousand products in some sixty registers
+// and no LDS, so blocks of four waves and as many waves per SIMD as the register count allows hide the chain's latency.
+constexpr int DECOMPRESS_BLOCK = 256;
+__global__ void __launch_bounds__(DECOMPRESS_BLOCK) jubjub_decompress_kernel(const Fr* __restrict__ x, const uint8_t* __restrict__ odd, uint64_t n,
+                                                                             Fr* __restrict__ xy, uint8_t* __restrict__ ok) {
+    const uint64_t i = (uint64_t)blockIdx.x * DECOMPRESS_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    Fr o[2];
+    ok[i] = eddsa::decompress_one(x[i], odd[i] != 0, o);
+    xy[2 * i] = o[0];
+    xy[2 * i + 1] = o[1];
+}
+
+// The hash inputs of m parsed transactions (tuples: m x 7 scalars) from their integers, token ids and the decompressed dst keys; fit[i] = whether
+// record i can verify at all (tx_tuple_one)
+__global__ void __launch_bounds__(256) mpn_tx_tuple_kernel(const uint64_t* __restrict__ nums, const Fr* __restrict__ tok, const Fr* __restrict__ dst_xy,
+                                                           const uint8_t* __restrict__ dst_ok, uint64_t m, Fr* __restrict__ tuples,
+                                                           uint8_t* __restrict__ fit) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    Fr t[7];
+    fit[i] = eddsa::tx_tuple_one(nums + 3 * i, tok + 2 * i, dst_xy + 2 * i, dst_ok[i], t) ? 1 : 0;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) tuples[7 * i + k] = t[k];
+}
+// ok[i] = verified and src decompressed and the record fit; the hash of a record that did not fit is zeros
+__global__ void __launch_bounds__(256) mpn_tx_verdict_kernel(const uint8_t* __restrict__ verified, const uint8_t* __restrict__ src_ok,
+                                                             const uint8_t* __restrict__ fit, uint64_t m, Fr* __restrict__ hash, uint8_t* __restrict__ ok) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    ok[i] = (verified[i] && src_ok[i] && fit[i]) ? 1 : 0;
+    if (!fit[i]) hash[i] = Fr::zero();
 }
 
 static int32_t eddsa_table_dev(bzk_ctx* ctx, const Fr29** out) {
@@ -59,6 +94,62 @@ int32_t jubjub_verify_launch(bzk_ctx* ctx, const void* pub_xy_dev, const void* m
     return BZK_OK;
 }
 
+int32_t jubjub_decompress_launch(bzk_ctx* ctx, const void* x_dev, const void* odd_dev, uint64_t n, void* xy_dev, void* ok_dev) {
+    for (uint64_t off = 0; off < n; off += EDDSA_LAUNCH_MAX) {
+        const uint64_t m = n - off < EDDSA_LAUNCH_MAX ? n - off : EDDSA_LAUNCH_MAX;
+        BZK_LAUNCH(ctx, "jubjub_decompress", jubjub_decompress_kernel, dim3((unsigned)((m + DECOMPRESS_BLOCK - 1) / DECOMPRESS_BLOCK)),
+                   dim3(DECOMPRESS_BLOCK), 0, (const Fr*)x_dev + off, (const uint8_t*)odd_dev + off, m, (Fr*)xy_dev + 2 * off, (uint8_t*)ok_dev + off);
+    }
+    return BZK_OK;
+}
+
+// MpnTransaction::verify_signature for n parsed transactions (mpn.hip parses; TxSoA is what it hands over): per chunk one decompress launch over
+// the 2 m keys (src keys first, so that their points are the verifier's key array as they stand), the hash inputs, the arity-7 Poseidon batch, the
+// signature kernel, the verdicts.  No field arithmetic on the host.  685 bytes of workspace per transaction.
+int32_t mpn_tx_verify_run(bzk_ctx* ctx, const TxSoA& t, uint64_t n, uint8_t* ok, uint8_t* hash_out, uint8_t* src_xy_out, uint8_t* dst_xy_out) {
+    if (n == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    const uint64_t cap = n < MPN_TX_CHUNK ? n : MPN_TX_CHUNK;
+    BZK_TRY(ws_reserve(ctx, ws_pad(cap * 64) + ws_pad(cap * 2) + ws_pad(cap * 128) + ws_pad(cap * 2) + ws_pad(cap * 64) + ws_pad(cap * 24) +
+                                ws_pad(cap * 96) + ws_pad(cap * 224) + ws_pad(cap * 32) + 3 * ws_pad(cap) + 4096));
+    WsCursor cur(ctx->ws);
+    uint8_t* dkx = cur.take<uint8_t>(cap * 64);
+    uint8_t* dodd = cur.take<uint8_t>(cap * 2);
+    uint8_t* dxy = cur.take<uint8_t>(cap * 128);
+    uint8_t* dkok = cur.take<uint8_t>(cap * 2);
+    uint8_t* dtok = cur.take<uint8_t>(cap * 64);
+    uint8_t* dnums = cur.take<uint8_t>(cap * 24);
+    uint8_t* dsig = cur.take<uint8_t>(cap * 96);
+    uint8_t* dtup = cur.take<uint8_t>(cap * 224);
+    uint8_t* dmsg = cur.take<uint8_t>(cap * 32);
+    uint8_t* dfit = cur.take<uint8_t>(cap);
+    uint8_t* dver = cur.take<uint8_t>(cap);
+    uint8_t* dok = cur.take<uint8_t>(cap);
+    for (uint64_t off = 0; off < n; off += MPN_TX_CHUNK) {  // one stream: a chunk's uploads follow the previous chunk's kernels
+        const uint64_t m = n - off < MPN_TX_CHUNK ? n - off : MPN_TX_CHUNK;
+        BZK_HIP(ctx, hipMemcpyAsync(dkx, t.src_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dkx + m * 32, t.dst_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dodd, t.src_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dodd + m, t.dst_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dtok, t.tok + off * 64, m * 64, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dnums, t.nums + off * 3, m * 24, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dsig, t.sig + off * 96, m * 96, hipMemcpyHostToDevice, ctx->stream));
+        BZK_TRY(jubjub_decompress_launch(ctx, dkx, dodd, 2 * m, dxy, dkok));
+        const dim3 grid((unsigned)((m + 255) / 256));
+        BZK_LAUNCH(ctx, "mpn_tx_tuple", mpn_tx_tuple_kernel, grid, dim3(256), 0, (const uint64_t*)dnums, (const Fr*)dtok, (const Fr*)(dxy + m * 64),
+                   dkok + m, m, (Fr*)dtup, dfit);
+        BZK_TRY(poseidon_launch(ctx, dtup, 7, m, dmsg));
+        BZK_TRY(jubjub_verify_launch(ctx, dxy, dmsg, dsig, m, dver));
+        BZK_LAUNCH(ctx, "mpn_tx_verdict", mpn_tx_verdict_kernel, grid, dim3(256), 0, dver, dkok, dfit, m, (Fr*)dmsg, dok);
+        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
+        if (hash_out) BZK_HIP(ctx, hipMemcpyAsync(hash_out + off * 32, dmsg, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (src_xy_out) BZK_HIP(ctx, hipMemcpyAsync(src_xy_out + off * 64, dxy, m * 64, hipMemcpyDeviceToHost, ctx->stream));
+        if (dst_xy_out) BZK_HIP(ctx, hipMemcpyAsync(dst_xy_out + off * 64, dxy + m * 64, m * 64, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
 }  // namespace bzk
 
 using namespace bzk;
@@ -90,6 +181,82 @@ int32_t bzk_jubjub_verify_batch(bzk_ctx* ctx, const uint8_t* pub_xy, const uint8
         BZK_HIP(ctx, hipMemcpyAsync(dmsg, msg + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
         BZK_HIP(ctx, hipMemcpyAsync(dsig, sig + off * 96, m * 96, hipMemcpyHostToDevice, ctx->stream));
         BZK_TRY(jubjub_verify_launch(ctx, dpub, dmsg, dsig, m, dok));
+        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
+int32_t bzk_jubjub_decompress_batch_dev(bzk_ctx* ctx, const void* x_dev, const void* odd_dev, uint64_t n, void* xy_out_dev, void* ok_dev) {
+    if (!ctx || (n && (!x_dev || !odd_dev || !xy_out_dev || !ok_dev))) return BZK_E_ARG;
+    if (n == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    return jubjub_decompress_launch(ctx, x_dev, odd_dev, n, xy_out_dev, ok_dev);
+}
+
+int32_t bzk_jubjub_decompress_batch(bzk_ctx* ctx, const uint8_t* x, const uint8_t* odd, uint64_t n, uint8_t* xy_out, uint8_t* ok) {
+    if (!ctx || (n && (!x || !odd || !xy_out || !ok))) return BZK_E_ARG;
+    if (n == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    constexpr uint64_t CHUNK = (uint64_t)1 << 20;  // 98 bytes per key
+    const uint64_t cap = n < CHUNK ? n : CHUNK;
+    BZK_TRY(ws_reserve(ctx, ws_pad(cap * 32) + ws_pad(cap * 64) + 2 * ws_pad(cap) + 1024));
+    WsCursor cur(ctx->ws);
+    uint8_t* dx = cur.take<uint8_t>(cap * 32);
+    uint8_t* dodd = cur.take<uint8_t>(cap);
+    uint8_t* dxy = cur.take<uint8_t>(cap * 64);
+    uint8_t* dok = cur.take<uint8_t>(cap);
+    for (uint64_t off = 0; off < n; off += CHUNK) {
+        const uint64_t m = n - off < CHUNK ? n - off : CHUNK;
+        BZK_HIP(ctx, hipMemcpyAsync(dx, x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dodd, odd + off, m, hipMemcpyHostToDevice, ctx->stream));
+        BZK_TRY(jubjub_decompress_launch(ctx, dx, dodd, m, dxy, dok));
+        BZK_HIP(ctx, hipMemcpyAsync(xy_out + off * 64, dxy, m * 64, hipMemcpyDeviceToHost, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
+// decompress, then verify: a key that does not decompress leaves (0, 0), which is off the curve, so the verifier's verdict is already 0.  The
+// decompressed keys go through the context's workspace (97 bytes per key); its users are ordered by the context's stream
+int32_t bzk_jubjub_verify_batch_compressed_dev(bzk_ctx* ctx, const void* pk_x_dev, const void* pk_odd_dev, const void* msg_dev, const void* sig_dev,
+                                               uint64_t n, void* ok_dev) {
+    if (!ctx || (n && (!pk_x_dev || !pk_odd_dev || !msg_dev || !sig_dev || !ok_dev))) return BZK_E_ARG;
+    if (n == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    BZK_TRY(ws_reserve(ctx, ws_pad(n * 64) + ws_pad(n) + 512));
+    WsCursor cur(ctx->ws);
+    uint8_t* dxy = cur.take<uint8_t>(n * 64);
+    uint8_t* dkok = cur.take<uint8_t>(n);
+    BZK_TRY(jubjub_decompress_launch(ctx, pk_x_dev, pk_odd_dev, n, dxy, dkok));
+    return jubjub_verify_launch(ctx, dxy, msg_dev, sig_dev, n, ok_dev);
+}
+
+int32_t bzk_jubjub_verify_batch_compressed(bzk_ctx* ctx, const uint8_t* pk_x, const uint8_t* pk_odd, const uint8_t* msg, const uint8_t* sig, uint64_t n,
+                                           uint8_t* ok) {
+    if (!ctx || (n && (!pk_x || !pk_odd || !msg || !sig || !ok))) return BZK_E_ARG;
+    if (n == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    constexpr uint64_t CHUNK = (uint64_t)1 << 20;  // 227 bytes per signature
+    const uint64_t cap = n < CHUNK ? n : CHUNK;
+    BZK_TRY(ws_reserve(ctx, 2 * ws_pad(cap * 32) + ws_pad(cap * 64) + ws_pad(cap * 96) + 3 * ws_pad(cap) + 2048));
+    WsCursor cur(ctx->ws);
+    uint8_t* dx = cur.take<uint8_t>(cap * 32);
+    uint8_t* dodd = cur.take<uint8_t>(cap);
+    uint8_t* dxy = cur.take<uint8_t>(cap * 64);
+    uint8_t* dkok = cur.take<uint8_t>(cap);
+    uint8_t* dmsg = cur.take<uint8_t>(cap * 32);
+    uint8_t* dsig = cur.take<uint8_t>(cap * 96);
+    uint8_t* dok = cur.take<uint8_t>(cap);
+    for (uint64_t off = 0; off < n; off += CHUNK) {
+        const uint64_t m = n - off < CHUNK ? n - off : CHUNK;
+        BZK_HIP(ctx, hipMemcpyAsync(dx, pk_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dodd, pk_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dmsg, msg + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dsig, sig + off * 96, m * 96, hipMemcpyHostToDevice, ctx->stream));
+        BZK_TRY(jubjub_decompress_launch(ctx, dx, dodd, m, dxy, dkok));
+        BZK_TRY(jubjub_verify_launch(ctx, dxy, dmsg, dsig, m, dok));
         BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
     }
     BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));

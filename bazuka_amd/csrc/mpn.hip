@@ -2406,3 +2406,179 @@ int32_t bzk_host_jubjub_verify(const uint8_t pub_xy[64], const uint8_t msg[32], 
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Wire-form transactions: bincode(MpnTransaction) records in, signature verdicts out (bzk_mpn_tx_verify_batch), accepted ones queued
+// (bzk_mpn_push_txs).  The parser below only cuts byte ranges, reads integers and maps ContractId tags: no field arithmetic, so that the device
+// path (eddsa.hip mpn_tx_verify_run) leaves none on the host.
+// ------------------------------------------------------------------------------------------------
+namespace bzk {
+namespace {
+struct TxParsed {
+    std::vector<uint8_t> src_x, dst_x, src_odd, dst_odd, tok, sig;
+    std::vector<uint64_t> nums;
+    TxSoA soa() const { return {src_x.data(), dst_x.data(), src_odd.data(), dst_odd.data(), tok.data(), nums.data(), sig.data()}; }
+};
+// ContractId as the scalar the circuits use, copied as bytes (Null = 0, Ziesha = 1: constants)
+void parse_contract_id(BinReader& r, uint8_t out[32]) {
+    const uint32_t tag = r.u32("ContractId tag");
+    memset(out, 0, 32);
+    if (tag == 0) return;
+    if (tag == 1) return ZkScalar::one().to_bytes(out);
+    if (tag == 2) {
+        if (const uint8_t* b = r.bytes(32, "ContractId::Custom")) memcpy(out, b, 32);
+        return;
+    }
+    r.fail("ContractId variant");
+}
+bool parse_txs(const uint8_t* txs, uint64_t len, uint64_t n, TxParsed& P, std::string& err) {
+    if (n > len / 190) {  // the shortest record: 4 + 2 x 33 + 2 x 12 + 96
+        err = "fewer bytes than " + std::to_string(n) + " MpnTransaction records need";
+        return false;
+    }
+    P.src_x.resize(n * 32); P.dst_x.resize(n * 32); P.src_odd.resize(n); P.dst_odd.resize(n);
+    P.tok.resize(n * 64); P.sig.resize(n * 96); P.nums.resize(n * 3);
+    BinReader r(txs, (size_t)len);
+    for (uint64_t i = 0; i < n && r.ok; ++i) {
+        P.nums[3 * i] = r.u32("MpnTransaction.nonce");
+        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.src_x[32 * i], b, 32);
+        P.src_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
+        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.dst_x[32 * i], b, 32);
+        P.dst_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
+        parse_contract_id(r, &P.tok[64 * i]);
+        P.nums[3 * i + 1] = r.u64("Amount");
+        parse_contract_id(r, &P.tok[64 * i + 32]);
+        P.nums[3 * i + 2] = r.u64("Amount");
+        if (const uint8_t* b = r.bytes(96, "Signature")) memcpy(&P.sig[96 * i], b, 96);
+        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
+    }
+    if (r.ok && r.pos != len) r.fail("bytes after the last record");
+    err = r.err;
+    return r.ok;
+}
+bool limbs_of_a_residue(const uint8_t b[32]) {  // value < r (`from_repr` refuses anything else)
+    uint32_t l[8];
+    memcpy(l, b, 32);
+    uint64_t borrow = 0;
+    for (int i = 0; i < 8; ++i) borrow = (((uint64_t)l[i] - FrParams::MOD[i] - borrow) >> 63) & 1;
+    return borrow != 0;
+}
+// PointCompressed::decompress with the reference's panic (no square root) and a non-residue's limbs reported as false
+bool decompress_checked(const uint8_t x[32], bool odd, PointAffine& out) {
+    out = PointAffine();
+    if (!limbs_of_a_residue(x)) return false;
+    const ZkScalar xs = ZkScalar::from_bytes(x), xx = xs.square();
+    ZkScalar y;
+    if (!((ZkScalar::one() - jubjub_d() * xx).invert() * (ZkScalar::one() + xx)).sqrt(&y)) return false;
+    if (y.is_odd() != odd) y = -y;
+    out = {xs, y};
+    return true;
+}
+// record i on the host: the verdict, and the transaction with its keys decompressed (hash_ok: dst decompressed and the token ids are residues)
+bool tx_verify_host(const TxParsed& P, uint64_t i, MpnTx& tx, bool& hash_ok) {
+    const bool src_ok = decompress_checked(&P.src_x[32 * i], P.src_odd[i] != 0, tx.src_pub);
+    const bool dst_ok = decompress_checked(&P.dst_x[32 * i], P.dst_odd[i] != 0, tx.dst_pub);
+    hash_ok = dst_ok && limbs_of_a_residue(&P.tok[64 * i]) && limbs_of_a_residue(&P.tok[64 * i + 32]);
+    bool sig_ok = true;
+    for (int k = 0; k < 3; ++k) sig_ok = sig_ok && limbs_of_a_residue(&P.sig[96 * i + 32 * k]);
+    tx.nonce = (uint32_t)P.nums[3 * i];
+    tx.amount = Money{ZkScalar::from_bytes(&P.tok[64 * i]), P.nums[3 * i + 1]};
+    tx.fee = Money{ZkScalar::from_bytes(&P.tok[64 * i + 32]), P.nums[3 * i + 2]};
+    tx.sig = {{ZkScalar::from_bytes(&P.sig[96 * i]), ZkScalar::from_bytes(&P.sig[96 * i + 32])}, ZkScalar::from_bytes(&P.sig[96 * i + 64])};
+    return src_ok && hash_ok && sig_ok && jubjub_verify(tx.src_pub, tx.hash(), tx.sig);
+}
+// all records: on the device when ctx is set, else on `threads` host threads.  txs_out (may be null): the transactions with decompressed keys
+int32_t tx_verify_all(bzk_ctx* ctx, int threads, const TxParsed& P, uint64_t n, uint8_t* ok, uint8_t* hash_out, std::vector<MpnTx>* txs_out) {
+    if (txs_out) txs_out->assign(n, MpnTx());
+    if (ctx) {
+        std::vector<uint8_t> sxy, dxy;
+        if (txs_out) { sxy.resize(n * 64); dxy.resize(n * 64); }
+        BZK_TRY(mpn_tx_verify_run(ctx, P.soa(), n, ok, hash_out, txs_out ? sxy.data() : nullptr, txs_out ? dxy.data() : nullptr));
+        for (uint64_t i = 0; txs_out && i < n; ++i) {
+            if (!ok[i]) continue;  // only verified records are looked at again
+            MpnTx& tx = (*txs_out)[i];
+            tx.nonce = (uint32_t)P.nums[3 * i];
+            tx.src_pub = {ZkScalar::from_bytes(&sxy[64 * i]), ZkScalar::from_bytes(&sxy[64 * i + 32])};
+            tx.dst_pub = {ZkScalar::from_bytes(&dxy[64 * i]), ZkScalar::from_bytes(&dxy[64 * i + 32])};
+            tx.amount = Money{ZkScalar::from_bytes(&P.tok[64 * i]), P.nums[3 * i + 1]};
+            tx.fee = Money{ZkScalar::from_bytes(&P.tok[64 * i + 32]), P.nums[3 * i + 2]};
+            tx.sig = {{ZkScalar::from_bytes(&P.sig[96 * i]), ZkScalar::from_bytes(&P.sig[96 * i + 32])}, ZkScalar::from_bytes(&P.sig[96 * i + 64])};
+        }
+        return BZK_OK;
+    }
+    std::atomic<uint64_t> next(0);
+    auto worker = [&] {
+        for (;;) {
+            const uint64_t i = next.fetch_add(1);
+            if (i >= n) break;
+            MpnTx local;
+            MpnTx& tx = txs_out ? (*txs_out)[i] : local;
+            bool hash_ok;
+            ok[i] = tx_verify_host(P, i, tx, hash_ok) ? 1 : 0;
+            if (hash_out) {
+                if (hash_ok) tx.hash().to_bytes(hash_out + 32 * i);
+                else memset(hash_out + 32 * i, 0, 32);
+            }
+        }
+    };
+    std::vector<std::thread> th;
+    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(threads, 1), n);
+    for (int k = 1; k < nt; ++k) th.emplace_back(worker);
+    worker();
+    for (auto& x : th) x.join();
+    return BZK_OK;
+}
+}  // namespace
+}  // namespace bzk
+
+extern "C" {
+
+int32_t bzk_mpn_tx_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* hash_out) {
+    if (n && (!txs || !ok)) return BZK_E_ARG;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        TxParsed P;
+        if (!parse_txs(txs, len, n, P, g_work_error)) return BZK_E_ARG;
+        return tx_verify_all(ctx, host_default_threads(), P, n, ok, hash_out, nullptr);
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+int32_t bzk_mpn_push_txs(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out) {
+    if (!w || (n && !txs)) return BZK_E_ARG;
+    if (accepted_out) *accepted_out = 0;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        TxParsed P;
+        if (!parse_txs(txs, len, n, P, g_work_error)) return BZK_E_ARG;
+        std::vector<uint8_t> ok(n);
+        std::vector<MpnTx> parsed;
+        if (const int32_t st = tx_verify_all(w->dev, w->threads, P, n, ok.data(), nullptr, &parsed); st != BZK_OK) {
+            if (w->dev) w->dev_error = bzk_last_error(w->dev);
+            return st;
+        }
+        uint64_t accepted = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (!ok[i]) continue;
+            w->mempool.push_back(parsed[i]);
+            ++accepted;
+        }
+        if (ok_out) memcpy(ok_out, ok.data(), n);
+        if (accepted_out) *accepted_out = accepted;
+        return BZK_OK;
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+int32_t bzk_host_jubjub_decompress(const uint8_t x[32], int32_t odd, uint8_t xy_out[64]) {
+    if (!x || !xy_out) return BZK_E_ARG;
+    PointAffine p;
+    const bool ok = decompress_checked(x, odd != 0, p);
+    p.x.to_bytes(xy_out);
+    p.y.to_bytes(xy_out + 32);
+    return ok ? 1 : 0;
+}
+
+}  // extern "C"

@@ -45,6 +45,11 @@ SIGNATURES = {
     "bzk_poseidon_batch_dev": (_i32, [_vp, _vp, _u32, _u64, _vp]),
     "bzk_jubjub_verify_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_jubjub_verify_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_jubjub_decompress_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_jubjub_decompress_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_jubjub_verify_batch_compressed": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_jubjub_verify_batch_compressed_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_mpn_tx_verify_batch": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "bzk_merkle4_root": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_merkle4_root_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_state_compress": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
@@ -113,6 +118,7 @@ SIGNATURES = {
     "bzk_mpn_tree_get_accounts": (_i32, [_vp, _vp, _vp, _u64, _vp]),
     "bzk_mpn_tree_prove": (_i32, [_vp, _vp, _vp, _u64, _vp]),
     "bzk_mpn_tree_prove_token": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_mpn_push_txs": (_i32, [_vp, _vp, _u64, _u64, _vp, C.POINTER(_u64)]),
     "bzk_mpn_push_deposit": (_i32, [_vp, _u64, _vp, _u64]),
     "bzk_mpn_push_withdraw": (_i32, [_vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "bzk_mpn_push_withdraw_signed": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
@@ -134,6 +140,7 @@ SIGNATURES = {
     "bzk_host_jubjub_keys": (_i32, [_vp, _u32, _vp]),
     "bzk_host_jubjub_sign": (_i32, [_vp, _vp, _vp]),
     "bzk_host_jubjub_verify": (_i32, [_vp, _vp, _vp]),
+    "bzk_host_jubjub_decompress": (_i32, [_vp, _i32, _vp]),
     "bzk_msm_g1_table_build": (_i32, [_vp, _vp, _u64, C.POINTER(_vp)]),
     "bzk_msm_g2_table_build": (_i32, [_vp, _vp, _u64, C.POINTER(_vp)]),
     "bzk_msm_g1_table_build_c": (_i32, [_vp, _vp, _u64, _u32, C.POINTER(_vp)]),
@@ -352,6 +359,29 @@ class Bzk:
         self._ck(self.lib.bzk_jubjub_verify_batch(self.h, _ptr(pub_xy), _ptr(msg), _ptr(sig), n, out), "jubjub_verify_batch")
         return out.raw[:n]
 
+    def jubjub_decompress_batch(self, x: bytes, odd: bytes):
+        """n = len(odd) compressed keys (x n x 32, odd one byte each): (xy n x 64, ok n bytes); zeros and 0 where a key does not decompress"""
+        n = len(odd)
+        if len(x) != 32 * n:
+            raise BzkError("jubjub_decompress_batch: x and odd describe different counts")
+        xy, ok = C.create_string_buffer(max(64 * n, 1)), C.create_string_buffer(max(n, 1))
+        self._ck(self.lib.bzk_jubjub_decompress_batch(self.h, _ptr(x), _ptr(odd), n, xy, ok), "jubjub_decompress_batch")
+        return xy.raw[: 64 * n], ok.raw[:n]
+
+    def jubjub_verify_batch_compressed(self, pk_x: bytes, pk_odd: bytes, msg: bytes, sig: bytes) -> bytes:
+        """jubjub_verify_batch on compressed keys (pk_x n x 32, pk_odd n bytes): decompressed on the device first"""
+        n = len(msg) // 32
+        if len(pk_x) != 32 * n or len(pk_odd) != n or len(sig) != 96 * n or len(msg) != 32 * n:
+            raise BzkError("jubjub_verify_batch_compressed: the arrays describe different counts")
+        out = C.create_string_buffer(max(n, 1))
+        self._ck(self.lib.bzk_jubjub_verify_batch_compressed(self.h, _ptr(pk_x), _ptr(pk_odd), _ptr(msg), _ptr(sig), n, out),
+                 "jubjub_verify_batch_compressed")
+        return out.raw[:n]
+
+    def mpn_tx_verify_batch(self, txs: bytes, n: int, want_hash: bool = True):
+        """n consecutive bincode(MpnTransaction): (verdict bytes, tx hashes n x 32 or None); a malformed record raises"""
+        return _mpn_tx_verify_batch(self.h, txs, n, want_hash)
+
     def merkle4_root(self, leaves: bytes, log4: int, want_nodes: bool = False):
         root = C.create_string_buffer(32)
         nn = (4 ** log4 - 1) // 3
@@ -383,6 +413,14 @@ class Bzk:
     def jubjub_verify_batch_dev(self, pub_xy, msg, sig, n: int, ok):
         """device buffers; ok: n verdict bytes, written in stream order"""
         self._ck(self.lib.bzk_jubjub_verify_batch_dev(self.h, _ptr(pub_xy), _ptr(msg), _ptr(sig), n, _ptr(ok)), "jubjub_verify_batch_dev")
+
+    def jubjub_decompress_batch_dev(self, x, odd, n: int, xy, ok):
+        """device buffers; xy n x 64 and ok n bytes are written in stream order"""
+        self._ck(self.lib.bzk_jubjub_decompress_batch_dev(self.h, _ptr(x), _ptr(odd), n, _ptr(xy), _ptr(ok)), "jubjub_decompress_batch_dev")
+
+    def jubjub_verify_batch_compressed_dev(self, pk_x, pk_odd, msg, sig, n: int, ok):
+        self._ck(self.lib.bzk_jubjub_verify_batch_compressed_dev(self.h, _ptr(pk_x), _ptr(pk_odd), _ptr(msg), _ptr(sig), n, _ptr(ok)),
+                 "jubjub_verify_batch_compressed_dev")
 
     def merkle4_root_dev(self, leaves, log4: int, nodes=None) -> bytes:
         root = C.create_string_buffer(32)
@@ -967,6 +1005,15 @@ class MpnWorld:
     def push_tx(self, src: int, dst: int, token_id: bytes, amount: int, fee_token: bytes, fee: int):
         _st(self.lib.bzk_mpn_push_tx(self.h, src, dst, _ptr(token_id), amount, _ptr(fee_token), fee), "push_tx")
 
+    def push_txs(self, txs: bytes, n: int):
+        """mempool admission of n wire-form transactions (consecutive bincode(MpnTransaction)): (verdict bytes, number queued).  Checked on the
+        device when set_device was given a context, else on host threads; those that verify are queued in input order"""
+        ok, acc = C.create_string_buffer(max(n, 1)), _u64()
+        st = self.lib.bzk_mpn_push_txs(self.h, _ptr(txs), len(txs), n, ok, C.byref(acc))
+        if st != 0:
+            raise BzkError(f"push_txs: {self.lib.bzk_strerror(st).decode()} [{self.lib.bzk_mpn_work_last_error().decode()}]")
+        return ok.raw[:n], acc.value
+
     def push_deposit(self, key_index: int, token_id: bytes, amount: int):
         _st(self.lib.bzk_mpn_push_deposit(self.h, key_index, _ptr(token_id), amount), "push_deposit")
 
@@ -1275,3 +1322,27 @@ def host_jubjub_verify(pub_xy: bytes, msg: bytes, sig: bytes) -> bool:
     if r < 0:
         raise BzkError("jubjub_verify: bad argument")
     return bool(r)
+
+
+def host_jubjub_decompress(x: bytes, odd: bool):
+    """PointCompressed::decompress on the host: x | y (64 bytes), or None where the reference panics or x is not a residue's limbs"""
+    out = C.create_string_buffer(64)
+    r = load_library().bzk_host_jubjub_decompress(_ptr(x), 1 if odd else 0, out)
+    if r < 0:
+        raise BzkError("jubjub_decompress: bad argument")
+    return out.raw if r else None
+
+
+def _mpn_tx_verify_batch(ctx_handle, txs: bytes, n: int, want_hash: bool):
+    lib = load_library()
+    ok = C.create_string_buffer(max(n, 1))
+    hashes = C.create_string_buffer(max(32 * n, 1)) if want_hash else None
+    st = lib.bzk_mpn_tx_verify_batch(ctx_handle, _ptr(txs), len(txs), n, ok, hashes)
+    if st != 0:
+        raise BzkError(f"mpn_tx_verify_batch: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+    return ok.raw[:n], (hashes.raw[: 32 * n] if want_hash else None)
+
+
+def host_mpn_tx_verify_batch(txs: bytes, n: int, want_hash: bool = True):
+    """Bzk.mpn_tx_verify_batch without a device: the same verdicts and hashes on host threads"""
+    return _mpn_tx_verify_batch(None, txs, n, want_hash)

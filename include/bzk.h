@@ -109,6 +109,28 @@ int32_t bzk_poseidon_batch_dev(bzk_ctx* ctx, const void* in_dev, uint32_t arity,
 int32_t bzk_jubjub_verify_batch(bzk_ctx* ctx, const uint8_t* pub_xy, const uint8_t* msg, const uint8_t* sig, uint64_t n, uint8_t* ok);
 int32_t bzk_jubjub_verify_batch_dev(bzk_ctx* ctx, const void* pub_xy_dev, const void* msg_dev, const void* sig_dev, uint64_t n, void* ok_dev);
 
+/* ---- batched key decompression ----------------------------------------------------------------------
+ * PointCompressed::decompress (src/crypto/jubjub/curve.rs:78-88) for n keys, one lane each: y = sqrt((1 + x^2) / (1 - d x^2)) with the
+ * parity of its canonical integer equal to odd.  x: n x 32 (Montgomery), odd: n bytes (0 / non-zero), xy_out: n x 64 (x | y), ok: n bytes.
+ * ok = 0 and xy_out = zeros where the reference panics (the radicand has no square root) or x is not the limbs of a residue; y = 0
+ * (x^2 = -1) is accepted for either parity.  n = 0 is a no-op.  The host form stages through the context's workspace and synchronises;
+ * the _dev form enqueues on the context's stream. */
+int32_t bzk_jubjub_decompress_batch(bzk_ctx* ctx, const uint8_t* x, const uint8_t* odd, uint64_t n, uint8_t* xy_out, uint8_t* ok);
+int32_t bzk_jubjub_decompress_batch_dev(bzk_ctx* ctx, const void* x_dev, const void* odd_dev, uint64_t n, void* xy_out_dev, void* ok_dev);
+/* JubJub::verify as the reference calls it, on a compressed PublicKey: decompress, then bzk_jubjub_verify_batch.  ok = 0 where the key
+ * does not decompress.  The _dev form keeps the decompressed keys in the context's workspace (97 bytes per key). */
+int32_t bzk_jubjub_verify_batch_compressed(bzk_ctx* ctx, const uint8_t* pk_x, const uint8_t* pk_odd, const uint8_t* msg, const uint8_t* sig,
+                                           uint64_t n, uint8_t* ok);
+int32_t bzk_jubjub_verify_batch_compressed_dev(bzk_ctx* ctx, const void* pk_x_dev, const void* pk_odd_dev, const void* msg_dev,
+                                               const void* sig_dev, uint64_t n, void* ok_dev);
+/* MpnTransaction::verify_signature (src/zk/mod.rs:610-627) for n transactions given as n consecutive bincode(MpnTransaction) (nonce u32,
+ * two PointCompressed, two Money, Signature: 190 - 254 bytes each, len bytes in all).  ok: n bytes.  hash_out (n x 32, may be NULL) =
+ * tx.hash(), zeros where dst does not decompress.  BZK_E_ARG with bzk_mpn_work_last_error() set when the bytes are not n well-formed
+ * records; a record whose keys do not decompress, or whose scalars are not residues' limbs, is a verdict 0 (hash zeros), not an error.
+ * The host only parses: both keys are decompressed, the integers brought into Montgomery form, the message hashed and the signature
+ * checked on the device, in rounds of 2^16 transactions; synchronises.  ctx = NULL: the same on host threads (bzk_host_default_threads). */
+int32_t bzk_mpn_tx_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* hash_out);
+
 /* ---- K2: dense 4-ary ZkState tree re-hash ----------------------------------------------------
  * Root of `ZkStateModel::List{log4_size, Scalar}` with every leaf present, as
  * `ZkStateBuilder::compress` / `KvStoreStateManager::root` would give (src/zk/state/mod.rs:66-90,
@@ -370,6 +392,11 @@ int32_t bzk_mpn_root(bzk_mpn* w, uint8_t root[32]);
 /* queue a signed MpnTransaction src -> dst (nonce = sender nonce + 1 + already queued from that sender) */
 int32_t bzk_mpn_push_tx(bzk_mpn* w, uint64_t src_index, uint64_t dst_index, const uint8_t token_id[32], uint64_t amount,
                         const uint8_t fee_token[32], uint64_t fee);
+/* Mempool admission (src/blockchain/mempool.rs:258): verifies the n wire-form transactions (bzk_mpn_tx_verify_batch's input) and queues
+ * those that verify, in input order, exactly as bzk_mpn_push_tx would have queued them.  With a context set (bzk_mpn_set_device) the
+ * checks run on the device in one batch; without, on host threads (bzk_mpn_set_threads).  ok_out (n bytes, may be NULL), *accepted_out
+ * (may be NULL).  Nothing is queued on BZK_E_ARG (bytes that are not n well-formed records: bzk_mpn_work_last_error). */
+int32_t bzk_mpn_push_txs(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out);
 /* applies up to 4^log4_batch queued txs (update::update), pads with UpdateTransition::null, synthesizes the
  * circuit.  Public inputs = [commitment, height, state, aux_data, next_state]. */
 int32_t bzk_mpn_update_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_t commitment[32], const uint8_t fee_token[32],
@@ -505,6 +532,9 @@ int32_t bzk_host_sha3_256(const uint8_t* in, uint64_t len, uint8_t out[32]);
 int32_t bzk_host_jubjub_keys(const uint8_t* seed, uint32_t len, uint8_t out[128]); /* pub.x|pub.y|randomness|scalar */
 int32_t bzk_host_jubjub_sign(const uint8_t key[128], const uint8_t msg[32], uint8_t sig_out[96]); /* r.x|r.y|s */
 int32_t bzk_host_jubjub_verify(const uint8_t pub_xy[64], const uint8_t msg[32], const uint8_t sig[96]); /* 1 / 0 */
+/* PointCompressed::decompress (src/crypto/jubjub/curve.rs:78-88) on the host.  x: 32 B Montgomery, odd: 0 / 1.  Returns 1 / 0; 0 (and
+ * xy_out = zeros) where the reference panics (no square root) or x is not a residue's limbs.  Negative on bad arguments. */
+int32_t bzk_host_jubjub_decompress(const uint8_t x[32], int32_t odd, uint8_t xy_out[64]);
 
 /* ---- static-base tables (the Groth16 CRS queries are fixed point sets) -------------------------------------------
  * build: tab[w][i] = 2^(c w) * base_i for every window, kept in HBM (W x the base memory, internal limb form).  With a

@@ -8,6 +8,7 @@
 //! Each public item names the reference interface it stands beside (paths relative to ziesha-network/bazuka v0.19.20):
 //!   * `GpuPoseidonHasher`      - `impl ZkHasher` (src/zk/mod.rs:152-155, 496-511) + the BULK path `hash_batch`
 //!   * `Gpu::jubjub_verify_batch` - `JubJub::<ZkHasher>::verify` (src/crypto/jubjub/mod.rs:151-167) for many signatures at once
+//!   * `Gpu::mpn_tx_verify_batch` - `MpnTransaction::verify_signature` (src/zk/mod.rs:610-627) for many wire-form transactions at once
 //!   * `groth16_prove`          - beside `groth16_verify` (src/zk/groth16/mod.rs:67-75), same argument order
 //!   * `compress`               - `ZkStateModel::compress::<H>(&data)` (src/zk/mod.rs:392-399)
 //!   * `DeviceStateManager`     - `KvStoreStateManager::{update_contract, root, get_data, prove}` (src/zk/state/mod.rs:218-438) for one
@@ -28,7 +29,8 @@ use bazuka::crypto::jubjub::{PublicKey, Signature};
 use bazuka::mpn::MpnWork;
 use bazuka::zk::groth16::Groth16Proof;
 use bazuka::zk::{
-    StateManagerError, ZkCompressedState, ZkDataLocator, ZkDataPairs, ZkDeltaPairs, ZkHasher, ZkLocatorError, ZkProof, ZkScalar, ZkStateModel,
+    MpnTransaction, StateManagerError, ZkCompressedState, ZkDataLocator, ZkDataPairs, ZkDeltaPairs, ZkHasher, ZkLocatorError, ZkProof, ZkScalar,
+    ZkStateModel,
 };
 use bzk_sys as sys;
 use std::ffi::CStr;
@@ -79,20 +81,39 @@ impl Gpu {
     }
 
     /// Bulk `JubJub::<PoseidonHasher>::verify(pk, msg, sig)` (src/crypto/jubjub/mod.rs:151-167): one verdict per (key, message, signature).
-    /// Keys are decompressed here, on the host (`PublicKey::decompress`, a square root each); everything else runs on the device.
+    /// The keys go to the device as they are held, compressed (`PointCompressed(x, y_is_odd)`): the square root of `PublicKey::decompress` runs there
+    /// too.  A key the reference's `decompress` would panic on gives `false`.
     pub fn jubjub_verify_batch(&self, items: &[(PublicKey, ZkScalar, Signature)]) -> Result<Vec<bool>, GpuError> {
         let n = items.len();
-        let (mut pk, mut msg, mut sig) = (Vec::with_capacity(2 * n), Vec::with_capacity(n), Vec::with_capacity(3 * n));
+        let (mut x, mut odd, mut msg, mut sig) = (Vec::with_capacity(n), Vec::with_capacity(n), Vec::with_capacity(n), Vec::with_capacity(3 * n));
         for (k, m, s) in items {
-            let p = k.decompress();
-            pk.extend_from_slice(&[p.0, p.1]);
+            x.push(k.0 .0);
+            odd.push(k.0 .1 as u8);
             msg.push(*m);
             sig.extend_from_slice(&[s.r.0, s.r.1, s.s]);
         }
         let mut ok = vec![0u8; n];
         check(self.0, unsafe {
-            sys::bzk_jubjub_verify_batch(self.0, scalars_ptr(&pk), scalars_ptr(&msg), scalars_ptr(&sig), n as u64, ok.as_mut_ptr())
+            sys::bzk_jubjub_verify_batch_compressed(self.0, scalars_ptr(&x), odd.as_ptr(), scalars_ptr(&msg), scalars_ptr(&sig), n as u64, ok.as_mut_ptr())
         })?;
+        Ok(ok.into_iter().map(|b| b != 0).collect())
+    }
+
+    /// Bulk `MpnTransaction::verify_signature` (src/zk/mod.rs:610-627), what mempool admission asks per transaction
+    /// (src/blockchain/mempool.rs:258): the transactions travel as bincode, like the state entries; keys are decompressed, messages hashed and
+    /// signatures checked on the device.
+    pub fn mpn_tx_verify_batch(&self, txs: &[MpnTransaction]) -> Result<Vec<bool>, GpuError> {
+        let mut bytes = Vec::with_capacity(254 * txs.len());
+        for tx in txs {
+            bytes.extend_from_slice(&bincode::serialize(tx)?);
+        }
+        let mut ok = vec![0u8; txs.len()];
+        let st = unsafe { sys::bzk_mpn_tx_verify_batch(self.0, bytes.as_ptr(), bytes.len() as u64, txs.len() as u64, ok.as_mut_ptr(), ptr::null_mut()) };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(self.0, st)?;
         Ok(ok.into_iter().map(|b| b != 0).collect())
     }
 

@@ -160,6 +160,27 @@ constexpr uint64_t MPN_TX_CHUNK = (uint64_t)1 << 16;  // transactions staged per
 // eddsa.hip: MpnTransaction::verify_signature for each; ok n bytes; hash_out n x 32, src_xy_out / dst_xy_out n x 64 (the decompressed keys) or null;
 // synchronises
 int32_t mpn_tx_verify_run(bzk_ctx* ctx, const TxSoA& t, uint64_t n, uint8_t* ok, uint8_t* hash_out, uint8_t* src_xy_out, uint8_t* dst_xy_out);
+// eddsa.hip: SHA3-256 of message i = data_dev[begin[i] - base .. end[i] - base), the 32 bytes at blank[i] inside it (blank_dev may be null) absorbed
+// as zeros; digest_dev (n x 32) and scalar_dev (n x 32: hash_to_scalar) may each be null; launch label "sha3_256"
+int32_t sha3_256_launch(bzk_ctx* ctx, const void* data_dev, const void* begin_dev, const void* end_dev, uint64_t base, const void* blank_dev,
+                        uint64_t n, void* digest_dev, void* scalar_dev);
+// n parsed MpnWithdraws (host memory; mpn.hip cuts them out of the bincode without hashing or field arithmetic)
+struct WdSoA {
+    const uint8_t* txs;        // the records as received
+    const uint64_t* rec_off;   // n + 1: where record i starts in txs
+    const uint64_t* pay_off;   // n: where its ContractWithdraw starts in txs
+    const uint32_t* pay_len;   // n: the payment's length
+    const uint32_t* cd_off;    // n: calldata's offset inside the payment
+    const uint8_t* key_x;      // n x 32: PointCompressed.0
+    const uint8_t* key_odd;    // n: PointCompressed.1
+    const uint32_t* nonce;     // n
+    const uint8_t* sig;        // n x 96: r.x | r.y | s
+};
+constexpr uint64_t MPN_WD_PAYMENT_MAX = (uint64_t)1 << 16;    // a longer ContractWithdraw is refused as malformed (its memo is unbounded on the wire)
+constexpr uint64_t MPN_WD_CHUNK_BYTES = (uint64_t)64 << 20;   // payment bytes staged per round of launches
+// eddsa.hip: ok n bytes (bit 0 verify_signature, bit 1 verify_calldata); fp_out n x 32 (payment.fingerprint()), xy_out n x 64 (the decompressed
+// keys) or null; synchronises
+int32_t mpn_withdraw_verify_run(bzk_ctx* ctx, const WdSoA& t, uint64_t n, uint8_t* ok, uint8_t* fp_out, uint8_t* xy_out);
 int32_t ntt_run(bzk_ctx* ctx, void* data_dev, uint32_t log_n, int inverse, int coset);  // ntt.hip
 int32_t ntt_h_chain(bzk_ctx* ctx, void* a, void* b, void* c, uint32_t log_m);              // ntt.hip: the h polynomial's 7 transforms, fused
 // msm_g1.hip / msm_g2.hip: windows [w_begin, w_end) (w_end < 0: all) of an MSM over a resident base set (or raw bases when `bases` is

@@ -6,6 +6,7 @@
 // being hoisted out of the round loop into 324 scalars the register file does not have (bzk_poseidon29.cuh)
 #define BZK_POSEIDON_MDS_RELOAD 1
 #include "bzk_decompress.cuh"
+#include "bzk_keccak.cuh"
 #include "bzk_internal.h"
 
 namespace bzk {
@@ -57,6 +58,69 @@ __global__ void __launch_bounds__(256) mpn_tx_verdict_kernel(const uint8_t* __re
     if (i >= m) return;
     ok[i] = (verified[i] && src_ok[i] && fit[i]) ? 1 : 0;
     if (!fit[i]) hash[i] = Fr::zero();
+}
+
+// SHA3-256, one lane per message (bzk_keccak.cuh sha3_256_one): message i = data[begin[i] - base .. end[i] - base); blank (may be null): the
+// offset inside message i of 32 bytes absorbed as zeros.  The state is 50 registers and the rounds are integer work with no memory traffic, so
+// blocks of four waves; a lane's loads are its own message's bytes (neighbouring lanes are a message apart: nothing coalesces, and at about ten
+// thousand instructions per 136 bytes nothing needs to).  digest (n x 8 words) and scalar (n, hash_to_scalar) may each be null.
+constexpr int SHA3_BLOCK = 256;
+__global__ void __launch_bounds__(SHA3_BLOCK) sha3_256_kernel(const uint8_t* __restrict__ data, const uint64_t* __restrict__ begin,
+                                                              const uint64_t* __restrict__ end, uint64_t base, const uint32_t* __restrict__ blank,
+                                                              uint64_t n, uint32_t* __restrict__ digest, Fr* __restrict__ scalar) {
+    const uint64_t i = (uint64_t)blockIdx.x * SHA3_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t b = begin[i], e = end[i];
+    const uint64_t len = e > b ? e - b : 0;
+    const keccak::Digest d = keccak::sha3_256_one(data + (b - base), len, blank ? (uint64_t)blank[i] : keccak::NO_BLANK);
+    if (digest) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) digest[8 * i + k] = d.w[k];
+    }
+    if (scalar) scalar[i] = keccak::fr_from_le_bytes_mod(d);
+}
+
+// The two hash inputs of m parsed MpnWithdraws: h2 = (fingerprint, nonce) for the signed message (transaction.rs:183-189), h6 = (address.x,
+// address.y, nonce, r.x, r.y, s) for the calldata (:177-182); the nonce is brought into Montgomery form here.  fit[i] = whether record i can
+// verify at all: the key decompressed and the signature's scalars are residues' limbs; zeros are hashed otherwise.
+__global__ void __launch_bounds__(256) mpn_withdraw_inputs_kernel(const Fr* __restrict__ fp, const uint32_t* __restrict__ nonce,
+                                                                  const Fr* __restrict__ xy, const uint8_t* __restrict__ key_ok,
+                                                                  const Fr* __restrict__ sig, uint64_t m, Fr* __restrict__ h2, Fr* __restrict__ h6,
+                                                                  uint8_t* __restrict__ fit) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const Fr r_x = sig[3 * i], r_y = sig[3 * i + 1], s = sig[3 * i + 2];
+    const bool ok = key_ok[i] != 0 && eddsa::canonical(r_x) && eddsa::canonical(r_y) && eddsa::canonical(s);
+    Fr c = Fr::zero();
+    c.l[0] = nonce[i];
+    const Fr nm = fe_to_mont<FrParams>(c), z = Fr::zero();
+    h2[2 * i] = fp[i];
+    h2[2 * i + 1] = nm;
+    h6[6 * i] = eddsa::fr_sel(ok, xy[2 * i], z);
+    h6[6 * i + 1] = eddsa::fr_sel(ok, xy[2 * i + 1], z);
+    h6[6 * i + 2] = eddsa::fr_sel(ok, nm, z);
+    h6[6 * i + 3] = eddsa::fr_sel(ok, r_x, z);
+    h6[6 * i + 4] = eddsa::fr_sel(ok, r_y, z);
+    h6[6 * i + 5] = eddsa::fr_sel(ok, s, z);
+    fit[i] = ok ? 1 : 0;
+}
+// ok[i]: bit 0 = the signature verified, bit 1 = the payment's 32 calldata bytes (at data[begin[i] + cd[i]], any alignment) equal the limbs of
+// H6's output as bytes; 0 where the record did not fit
+__global__ void __launch_bounds__(256) mpn_withdraw_verdict_kernel(const uint8_t* __restrict__ verified, const uint8_t* __restrict__ fit,
+                                                                   const Fr* __restrict__ h6, const uint8_t* __restrict__ data,
+                                                                   const uint64_t* __restrict__ begin, const uint32_t* __restrict__ cd, uint64_t m,
+                                                                   uint8_t* __restrict__ ok) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const uint8_t* p = data + begin[i] + cd[i];
+    const Fr h = h6[i];
+    uint32_t diff = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t w = (uint32_t)p[4 * k] | ((uint32_t)p[4 * k + 1] << 8) | ((uint32_t)p[4 * k + 2] << 16) | ((uint32_t)p[4 * k + 3] << 24);
+        diff |= w ^ h.l[k];
+    }
+    ok[i] = fit[i] ? (uint8_t)((verified[i] ? 1 : 0) | (diff == 0 ? 2 : 0)) : 0;
 }
 
 static int32_t eddsa_table_dev(bzk_ctx* ctx, const Fr29** out) {
@@ -145,6 +209,89 @@ int32_t mpn_tx_verify_run(bzk_ctx* ctx, const TxSoA& t, uint64_t n, uint8_t* ok,
         if (hash_out) BZK_HIP(ctx, hipMemcpyAsync(hash_out + off * 32, dmsg, m * 32, hipMemcpyDeviceToHost, ctx->stream));
         if (src_xy_out) BZK_HIP(ctx, hipMemcpyAsync(src_xy_out + off * 64, dxy, m * 64, hipMemcpyDeviceToHost, ctx->stream));
         if (dst_xy_out) BZK_HIP(ctx, hipMemcpyAsync(dst_xy_out + off * 64, dxy + m * 64, m * 64, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
+int32_t sha3_256_launch(bzk_ctx* ctx, const void* data_dev, const void* begin_dev, const void* end_dev, uint64_t base, const void* blank_dev,
+                        uint64_t n, void* digest_dev, void* scalar_dev) {
+    for (uint64_t off = 0; off < n; off += EDDSA_LAUNCH_MAX) {
+        const uint64_t m = n - off < EDDSA_LAUNCH_MAX ? n - off : EDDSA_LAUNCH_MAX;
+        BZK_LAUNCH(ctx, "sha3_256", sha3_256_kernel, dim3((unsigned)((m + SHA3_BLOCK - 1) / SHA3_BLOCK)), dim3(SHA3_BLOCK), 0,
+                   (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off, base,
+                   blank_dev ? (const uint32_t*)blank_dev + off : nullptr, m, digest_dev ? (uint32_t*)digest_dev + 8 * off : nullptr,
+                   scalar_dev ? (Fr*)scalar_dev + off : nullptr);
+    }
+    return BZK_OK;
+}
+
+// MpnWithdraw::verify_signature and verify_calldata for n parsed records (mpn.hip parses; WdSoA is what it hands over).  A chunk ends at
+// MPN_TX_CHUNK records or MPN_WD_CHUNK_BYTES of payment bytes, whichever comes first (a payment is at most MPN_WD_PAYMENT_MAX bytes, so a chunk
+// always holds a record); its records' bytes go up as they stand, headers included, and the kernels index the payments inside them.  Per chunk:
+// fingerprints (SHA3 with the calldata blanked, then ZkScalar::new), one decompress launch, the hash inputs, H2, H6, the signature kernel, the
+// verdicts.  No hashing and no field arithmetic on the host.
+int32_t mpn_withdraw_verify_run(bzk_ctx* ctx, const WdSoA& t, uint64_t n, uint8_t* ok, uint8_t* fp_out, uint8_t* xy_out) {
+    if (n == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    std::vector<uint64_t> chunk_at(1, 0), begin(n), end(n);  // payment ranges relative to their chunk's first byte
+    uint64_t cap = 0, cap_bytes = 0;
+    for (uint64_t a = 0; a < n;) {
+        uint64_t b = a, pay = 0;
+        while (b < n && b - a < MPN_TX_CHUNK && (b == a || pay + t.pay_len[b] <= MPN_WD_CHUNK_BYTES)) pay += t.pay_len[b++];
+        for (uint64_t i = a; i < b; ++i) {
+            begin[i] = t.pay_off[i] - t.rec_off[a];
+            end[i] = begin[i] + t.pay_len[i];
+        }
+        cap = std::max(cap, b - a);
+        cap_bytes = std::max(cap_bytes, t.rec_off[b] - t.rec_off[a]);
+        chunk_at.push_back(b);
+        a = b;
+    }
+    BZK_TRY(ws_reserve(ctx, ws_pad(cap_bytes) + 2 * ws_pad(cap * 8) + 2 * ws_pad(cap * 4) + 4 * ws_pad(cap * 32) + 2 * ws_pad(cap * 64) +
+                                ws_pad(cap * 96) + ws_pad(cap * 192) + 5 * ws_pad(cap) + 8192));
+    WsCursor cur(ctx->ws);
+    uint8_t* dbytes = cur.take<uint8_t>(cap_bytes);
+    uint8_t* dbeg = cur.take<uint8_t>(cap * 8);
+    uint8_t* dend = cur.take<uint8_t>(cap * 8);
+    uint8_t* dcd = cur.take<uint8_t>(cap * 4);
+    uint8_t* dnonce = cur.take<uint8_t>(cap * 4);
+    uint8_t* dkx = cur.take<uint8_t>(cap * 32);
+    uint8_t* dfp = cur.take<uint8_t>(cap * 32);
+    uint8_t* dmsg = cur.take<uint8_t>(cap * 32);
+    uint8_t* dcall = cur.take<uint8_t>(cap * 32);
+    uint8_t* dxy = cur.take<uint8_t>(cap * 64);
+    uint8_t* dh2 = cur.take<uint8_t>(cap * 64);
+    uint8_t* dsig = cur.take<uint8_t>(cap * 96);
+    uint8_t* dh6 = cur.take<uint8_t>(cap * 192);
+    uint8_t* dodd = cur.take<uint8_t>(cap);
+    uint8_t* dkok = cur.take<uint8_t>(cap);
+    uint8_t* dfit = cur.take<uint8_t>(cap);
+    uint8_t* dver = cur.take<uint8_t>(cap);
+    uint8_t* dok = cur.take<uint8_t>(cap);
+    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {  // one stream: a chunk's uploads follow the previous chunk's kernels
+        const uint64_t off = chunk_at[c], m = chunk_at[c + 1] - off;
+        BZK_HIP(ctx, hipMemcpyAsync(dbytes, t.txs + t.rec_off[off], t.rec_off[off + m] - t.rec_off[off], hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dbeg, begin.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dend, end.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dcd, t.cd_off + off, m * 4, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dnonce, t.nonce + off, m * 4, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dkx, t.key_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dodd, t.key_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dsig, t.sig + off * 96, m * 96, hipMemcpyHostToDevice, ctx->stream));
+        BZK_TRY(sha3_256_launch(ctx, dbytes, dbeg, dend, 0, dcd, m, nullptr, dfp));
+        BZK_TRY(jubjub_decompress_launch(ctx, dkx, dodd, m, dxy, dkok));
+        const dim3 grid((unsigned)((m + 255) / 256));
+        BZK_LAUNCH(ctx, "mpn_withdraw_inputs", mpn_withdraw_inputs_kernel, grid, dim3(256), 0, (const Fr*)dfp, (const uint32_t*)dnonce, (const Fr*)dxy,
+                   dkok, (const Fr*)dsig, m, (Fr*)dh2, (Fr*)dh6, dfit);
+        BZK_TRY(poseidon_launch(ctx, dh2, 2, m, dmsg));
+        BZK_TRY(poseidon_launch(ctx, dh6, 6, m, dcall));
+        BZK_TRY(jubjub_verify_launch(ctx, dxy, dmsg, dsig, m, dver));
+        BZK_LAUNCH(ctx, "mpn_withdraw_verdict", mpn_withdraw_verdict_kernel, grid, dim3(256), 0, dver, dfit, (const Fr*)dcall, dbytes,
+                   (const uint64_t*)dbeg, (const uint32_t*)dcd, m, dok);
+        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
+        if (fp_out) BZK_HIP(ctx, hipMemcpyAsync(fp_out + off * 32, dfp, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (xy_out) BZK_HIP(ctx, hipMemcpyAsync(xy_out + off * 64, dxy, m * 64, hipMemcpyDeviceToHost, ctx->stream));
     }
     BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return BZK_OK;
@@ -258,6 +405,49 @@ int32_t bzk_jubjub_verify_batch_compressed(bzk_ctx* ctx, const uint8_t* pk_x, co
         BZK_TRY(jubjub_decompress_launch(ctx, dx, dodd, m, dxy, dkok));
         BZK_TRY(jubjub_verify_launch(ctx, dxy, dmsg, dsig, m, dok));
         BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
+int32_t bzk_sha3_256_batch_dev(bzk_ctx* ctx, const void* data_dev, const void* off_dev, uint64_t n, void* digest_out_dev, void* scalar_out_dev) {
+    if (!ctx || (n && (!data_dev || !off_dev || (!digest_out_dev && !scalar_out_dev)))) return BZK_E_ARG;
+    if (n == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    return sha3_256_launch(ctx, data_dev, off_dev, (const uint64_t*)off_dev + 1, 0, nullptr, n, digest_out_dev, scalar_out_dev);
+}
+
+int32_t bzk_sha3_256_batch(bzk_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n, uint8_t* digest_out, uint8_t* scalar_out) {
+    if (!ctx || (n && (!data || !off || (!digest_out && !scalar_out)))) return BZK_E_ARG;
+    if (n == 0) return BZK_OK;
+    if (off[0] != 0) return BZK_E_ARG;
+    for (uint64_t i = 0; i < n; ++i)
+        if (off[i + 1] < off[i]) return BZK_E_ARG;
+    (void)hipSetDevice(ctx->device);
+    constexpr uint64_t CHUNK = (uint64_t)1 << 20, CHUNK_BYTES = (uint64_t)64 << 20;  // a chunk: so many messages or bytes, and at least one message
+    std::vector<uint64_t> chunk_at(1, 0);
+    uint64_t cap = 0, cap_bytes = 0;
+    for (uint64_t a = 0; a < n;) {
+        uint64_t b = a + 1;
+        while (b < n && b - a < CHUNK && off[b + 1] - off[a] <= CHUNK_BYTES) ++b;
+        cap = std::max(cap, b - a);
+        cap_bytes = std::max(cap_bytes, off[b] - off[a]);
+        chunk_at.push_back(b);
+        a = b;
+    }
+    BZK_TRY(ws_reserve(ctx, ws_pad(cap_bytes + 1) + ws_pad((cap + 1) * 8) + 2 * ws_pad(cap * 32) + 2048));
+    WsCursor cur(ctx->ws);
+    uint8_t* ddata = cur.take<uint8_t>(cap_bytes ? cap_bytes : 1);
+    uint8_t* doff = cur.take<uint8_t>((cap + 1) * 8);
+    uint8_t* ddig = cur.take<uint8_t>(cap * 32);
+    uint8_t* dsc = cur.take<uint8_t>(cap * 32);
+    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {
+        const uint64_t a = chunk_at[c], m = chunk_at[c + 1] - a, bytes = off[a + m] - off[a];
+        if (bytes) BZK_HIP(ctx, hipMemcpyAsync(ddata, data + off[a], bytes, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(doff, off + a, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        BZK_TRY(sha3_256_launch(ctx, ddata, doff, doff + 8, off[a], nullptr, m, digest_out ? ddig : nullptr, scalar_out ? dsc : nullptr));
+        if (digest_out) BZK_HIP(ctx, hipMemcpyAsync(digest_out + a * 32, ddig, m * 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (scalar_out) BZK_HIP(ctx, hipMemcpyAsync(scalar_out + a * 32, dsc, m * 32, hipMemcpyDeviceToHost, ctx->stream));
     }
     BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return BZK_OK;

@@ -2582,3 +2582,167 @@ int32_t bzk_host_jubjub_decompress(const uint8_t x[32], int32_t odd, uint8_t xy_
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Wire-form withdrawals: bincode(MpnWithdraw) records in, verdicts and fingerprints out (bzk_mpn_withdraw_verify_batch), accepted ones queued with
+// their payment bytes (bzk_mpn_push_withdraws).  As above the parser only cuts byte ranges, reads integers and maps ContractId tags: no hashing
+// and no field arithmetic, so that the device path (eddsa.hip mpn_withdraw_verify_run) leaves none on the host.
+// ------------------------------------------------------------------------------------------------
+namespace bzk {
+namespace {
+struct WdParsed {
+    const uint8_t* txs = nullptr;
+    std::vector<uint64_t> rec_off, pay_off, amounts;  // amounts n x 2: amount, fee
+    std::vector<uint32_t> pay_len, cd_off, nonce, circuit;
+    std::vector<uint8_t> key_x, key_odd, sig, cid, tok;  // cid n x 32: payment.contract_id as a scalar; tok n x 64: amount | fee token ids
+    WdSoA soa() const {
+        return {txs, rec_off.data(), pay_off.data(), pay_len.data(), cd_off.data(), key_x.data(), key_odd.data(), nonce.data(), sig.data()};
+    }
+};
+bool parse_withdraws(const uint8_t* txs, uint64_t len, uint64_t n, WdParsed& P, std::string& err) {
+    if (n > len / 245) {  // the shortest record: 33 + 4 + 96 + (8 + 4 + 4 + 32 + 40 + 2 x 12)
+        err = "fewer bytes than " + std::to_string(n) + " MpnWithdraw records need";
+        return false;
+    }
+    P.txs = txs;
+    P.rec_off.resize(n + 1); P.pay_off.resize(n); P.amounts.resize(2 * n);
+    P.pay_len.resize(n); P.cd_off.resize(n); P.nonce.resize(n); P.circuit.resize(n);
+    P.key_x.resize(n * 32); P.key_odd.resize(n); P.sig.resize(n * 96); P.cid.resize(n * 32); P.tok.resize(n * 64);
+    BinReader r(txs, (size_t)len);
+    for (uint64_t i = 0; i < n && r.ok; ++i) {
+        P.rec_off[i] = r.pos;
+        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.key_x[32 * i], b, 32);
+        P.key_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
+        P.nonce[i] = r.u32("MpnWithdraw.mpn_withdraw_nonce");
+        if (const uint8_t* b = r.bytes(96, "Signature")) memcpy(&P.sig[96 * i], b, 96);
+        P.pay_off[i] = r.pos;
+        skip_string(r);
+        parse_contract_id(r, &P.cid[32 * i]);
+        P.circuit[i] = r.u32("withdraw_circuit_id");
+        P.cd_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
+        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail("ContractWithdraw longer than 65536 bytes");
+        r.bytes(32, "calldata");
+        skip_l1_pub(r);
+        parse_contract_id(r, &P.tok[64 * i]);
+        P.amounts[2 * i] = r.u64("Amount");
+        parse_contract_id(r, &P.tok[64 * i + 32]);
+        P.amounts[2 * i + 1] = r.u64("Amount");
+        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail("ContractWithdraw longer than 65536 bytes");
+        P.pay_len[i] = (uint32_t)(r.pos - P.pay_off[i]);
+        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
+    }
+    if (r.ok) P.rec_off[n] = r.pos;
+    if (r.ok && r.pos != len) r.fail("bytes after the last record");
+    err = r.err;
+    return r.ok;
+}
+// record i on the host: the two verdict bits, the fingerprint, and the withdrawal with its key decompressed
+uint8_t withdraw_verify_host(const WdParsed& P, uint64_t i, WithdrawTx& tx) {
+    const bool key_ok = decompress_checked(&P.key_x[32 * i], P.key_odd[i] != 0, tx.mpn_address);
+    bool sig_ok = true;
+    for (int k = 0; k < 3; ++k) sig_ok = sig_ok && limbs_of_a_residue(&P.sig[96 * i + 32 * k]);
+    tx.nonce = P.nonce[i];
+    tx.sig = {{ZkScalar::from_bytes(&P.sig[96 * i]), ZkScalar::from_bytes(&P.sig[96 * i + 32])}, ZkScalar::from_bytes(&P.sig[96 * i + 64])};
+    tx.amount = Money{ZkScalar::from_bytes(&P.tok[64 * i]), P.amounts[2 * i]};
+    tx.fee = Money{ZkScalar::from_bytes(&P.tok[64 * i + 32]), P.amounts[2 * i + 1]};
+    tx.payment.assign(P.txs + P.pay_off[i], P.txs + P.pay_off[i] + P.pay_len[i]);
+    std::vector<uint8_t> blanked = tx.payment;
+    memset(blanked.data() + P.cd_off[i], 0, 32);
+    tx.fingerprint = hash_to_scalar(blanked.data(), blanked.size());
+    if (!key_ok || !sig_ok) return 0;
+    uint8_t calldata[32];
+    tx.calldata().to_bytes(calldata);
+    return (uint8_t)((jubjub_verify(tx.mpn_address, tx.sign_message(), tx.sig) ? 1 : 0) |
+                     (memcmp(calldata, tx.payment.data() + P.cd_off[i], 32) == 0 ? 2 : 0));
+}
+// all records: on the device when ctx is set, else on `threads` host threads.  out (may be null): the withdrawals as they would be queued
+int32_t withdraw_verify_all(bzk_ctx* ctx, int threads, const WdParsed& P, uint64_t n, uint8_t* ok, uint8_t* fp_out, std::vector<WithdrawTx>* out) {
+    if (out) out->assign(n, WithdrawTx());
+    if (ctx) {
+        std::vector<uint8_t> xy, fp;
+        if (out) { xy.resize(n * 64); fp.resize(n * 32); }
+        uint8_t* fpp = out ? fp.data() : fp_out;
+        BZK_TRY(mpn_withdraw_verify_run(ctx, P.soa(), n, ok, fpp, out ? xy.data() : nullptr));
+        if (out && fp_out) memcpy(fp_out, fp.data(), n * 32);
+        for (uint64_t i = 0; out && i < n; ++i) {
+            if (ok[i] != 3) continue;  // only admissible records are looked at again
+            WithdrawTx& tx = (*out)[i];
+            tx.mpn_address = {ZkScalar::from_bytes(&xy[64 * i]), ZkScalar::from_bytes(&xy[64 * i + 32])};
+            tx.nonce = P.nonce[i];
+            tx.sig = {{ZkScalar::from_bytes(&P.sig[96 * i]), ZkScalar::from_bytes(&P.sig[96 * i + 32])}, ZkScalar::from_bytes(&P.sig[96 * i + 64])};
+            tx.amount = Money{ZkScalar::from_bytes(&P.tok[64 * i]), P.amounts[2 * i]};
+            tx.fee = Money{ZkScalar::from_bytes(&P.tok[64 * i + 32]), P.amounts[2 * i + 1]};
+            tx.fingerprint = ZkScalar::from_bytes(&fp[32 * i]);
+            tx.payment.assign(P.txs + P.pay_off[i], P.txs + P.pay_off[i] + P.pay_len[i]);
+        }
+        return BZK_OK;
+    }
+    std::atomic<uint64_t> next(0);
+    auto worker = [&] {
+        for (;;) {
+            const uint64_t i = next.fetch_add(1);
+            if (i >= n) break;
+            WithdrawTx local;
+            WithdrawTx& tx = out ? (*out)[i] : local;
+            ok[i] = withdraw_verify_host(P, i, tx);
+            if (fp_out) tx.fingerprint.to_bytes(fp_out + 32 * i);
+        }
+    };
+    std::vector<std::thread> th;
+    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(threads, 1), n);
+    for (int k = 1; k < nt; ++k) th.emplace_back(worker);
+    worker();
+    for (auto& x : th) x.join();
+    return BZK_OK;
+}
+}  // namespace
+}  // namespace bzk
+
+extern "C" {
+
+int32_t bzk_mpn_withdraw_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* fingerprint_out) {
+    if (n && (!txs || !ok)) return BZK_E_ARG;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        WdParsed P;
+        if (!parse_withdraws(txs, len, n, P, g_work_error)) return BZK_E_ARG;
+        return withdraw_verify_all(ctx, host_default_threads(), P, n, ok, fingerprint_out, nullptr);
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+int32_t bzk_mpn_push_withdraws(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out) {
+    if (!w || (n && !txs)) return BZK_E_ARG;
+    if (accepted_out) *accepted_out = 0;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        WdParsed P;
+        if (!parse_withdraws(txs, len, n, P, g_work_error)) return BZK_E_ARG;
+        std::vector<uint8_t> ok(n);
+        std::vector<WithdrawTx> parsed;
+        if (const int32_t st = withdraw_verify_all(w->dev, w->threads, P, n, ok.data(), nullptr, &parsed); st != BZK_OK) {
+            if (w->dev) w->dev_error = bzk_last_error(w->dev);
+            return st;
+        }
+        uint8_t world_id[32];
+        w->contract_id.to_bytes(world_id);
+        uint64_t accepted = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            // mempool.rs:246-258 for a withdrawal: the payment is for this contract's withdraw circuit 0 and signed; calldata as withdraw.rs:77 checks it
+            const bool admit = ok[i] == 3 && memcmp(&P.cid[32 * i], world_id, 32) == 0 && P.circuit[i] == 0 &&
+                               limbs_of_a_residue(&P.tok[64 * i]) && limbs_of_a_residue(&P.tok[64 * i + 32]);
+            ok[i] = admit ? 1 : 0;
+            if (!admit) continue;
+            w->withdraw_queue.push_back(std::move(parsed[i]));
+            ++accepted;
+        }
+        if (ok_out) memcpy(ok_out, ok.data(), n);
+        if (accepted_out) *accepted_out = accepted;
+        return BZK_OK;
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+}  // extern "C"

@@ -50,6 +50,9 @@ SIGNATURES = {
     "bzk_jubjub_verify_batch_compressed": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_jubjub_verify_batch_compressed_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_mpn_tx_verify_batch": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp]),
+    "bzk_sha3_256_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_sha3_256_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_mpn_withdraw_verify_batch": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "bzk_merkle4_root": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_merkle4_root_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_state_compress": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
@@ -119,6 +122,7 @@ SIGNATURES = {
     "bzk_mpn_tree_prove": (_i32, [_vp, _vp, _vp, _u64, _vp]),
     "bzk_mpn_tree_prove_token": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_mpn_push_txs": (_i32, [_vp, _vp, _u64, _u64, _vp, C.POINTER(_u64)]),
+    "bzk_mpn_push_withdraws": (_i32, [_vp, _vp, _u64, _u64, _vp, C.POINTER(_u64)]),
     "bzk_mpn_push_deposit": (_i32, [_vp, _u64, _vp, _u64]),
     "bzk_mpn_push_withdraw": (_i32, [_vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "bzk_mpn_push_withdraw_signed": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
@@ -382,6 +386,23 @@ class Bzk:
         """n consecutive bincode(MpnTransaction): (verdict bytes, tx hashes n x 32 or None); a malformed record raises"""
         return _mpn_tx_verify_batch(self.h, txs, n, want_hash)
 
+    def sha3_256_batch(self, msgs, want_digest: bool = True, want_scalar: bool = True):
+        """SHA3-256 of each of the byte strings in msgs on the device: (digests n x 32 or None, hash_to_scalar n x 32 Montgomery or None)"""
+        n = len(msgs)
+        off = (_u64 * (n + 1))()
+        for i, m in enumerate(msgs):
+            off[i + 1] = off[i] + len(m)
+        data = b"".join(msgs)
+        dig = C.create_string_buffer(max(32 * n, 1)) if want_digest else None
+        sc = C.create_string_buffer(max(32 * n, 1)) if want_scalar else None
+        self._ck(self.lib.bzk_sha3_256_batch(self.h, _ptr(data) if data else _ptr(b"\0"), off, n, dig, sc), "sha3_256_batch")
+        return (dig.raw[: 32 * n] if want_digest else None), (sc.raw[: 32 * n] if want_scalar else None)
+
+    def mpn_withdraw_verify_batch(self, txs: bytes, n: int, want_fingerprint: bool = True):
+        """n consecutive bincode(MpnWithdraw): (verdict bytes: bit 0 signature, bit 1 calldata; fingerprints n x 32 or None); a malformed
+        record raises"""
+        return _mpn_withdraw_verify_batch(self.h, txs, n, want_fingerprint)
+
     def merkle4_root(self, leaves: bytes, log4: int, want_nodes: bool = False):
         root = C.create_string_buffer(32)
         nn = (4 ** log4 - 1) // 3
@@ -421,6 +442,10 @@ class Bzk:
     def jubjub_verify_batch_compressed_dev(self, pk_x, pk_odd, msg, sig, n: int, ok):
         self._ck(self.lib.bzk_jubjub_verify_batch_compressed_dev(self.h, _ptr(pk_x), _ptr(pk_odd), _ptr(msg), _ptr(sig), n, _ptr(ok)),
                  "jubjub_verify_batch_compressed_dev")
+
+    def sha3_256_batch_dev(self, data, off, n: int, digest=None, scalar=None):
+        """device buffers: data bytes, off n + 1 u64; digest n x 32 and / or scalar n x 32 are written in stream order"""
+        self._ck(self.lib.bzk_sha3_256_batch_dev(self.h, _ptr(data), _ptr(off), n, _ptr(digest), _ptr(scalar)), "sha3_256_batch_dev")
 
     def merkle4_root_dev(self, leaves, log4: int, nodes=None) -> bytes:
         root = C.create_string_buffer(32)
@@ -1014,6 +1039,15 @@ class MpnWorld:
             raise BzkError(f"push_txs: {self.lib.bzk_strerror(st).decode()} [{self.lib.bzk_mpn_work_last_error().decode()}]")
         return ok.raw[:n], acc.value
 
+    def push_withdraws(self, txs: bytes, n: int):
+        """mempool admission of n wire-form withdrawals (consecutive bincode(MpnWithdraw)): (1 / 0 per record, number queued).  Checked on the
+        device when set_device was given a context, else on host threads; the accepted ones are queued in input order with their payments"""
+        ok, acc = C.create_string_buffer(max(n, 1)), _u64()
+        st = self.lib.bzk_mpn_push_withdraws(self.h, _ptr(txs), len(txs), n, ok, C.byref(acc))
+        if st != 0:
+            raise BzkError(f"push_withdraws: {self.lib.bzk_strerror(st).decode()} [{self.lib.bzk_mpn_work_last_error().decode()}]")
+        return ok.raw[:n], acc.value
+
     def push_deposit(self, key_index: int, token_id: bytes, amount: int):
         _st(self.lib.bzk_mpn_push_deposit(self.h, key_index, _ptr(token_id), amount), "push_deposit")
 
@@ -1346,3 +1380,18 @@ def _mpn_tx_verify_batch(ctx_handle, txs: bytes, n: int, want_hash: bool):
 def host_mpn_tx_verify_batch(txs: bytes, n: int, want_hash: bool = True):
     """Bzk.mpn_tx_verify_batch without a device: the same verdicts and hashes on host threads"""
     return _mpn_tx_verify_batch(None, txs, n, want_hash)
+
+
+def _mpn_withdraw_verify_batch(ctx_handle, txs: bytes, n: int, want_fingerprint: bool):
+    lib = load_library()
+    ok = C.create_string_buffer(max(n, 1))
+    fps = C.create_string_buffer(max(32 * n, 1)) if want_fingerprint else None
+    st = lib.bzk_mpn_withdraw_verify_batch(ctx_handle, _ptr(txs), len(txs), n, ok, fps)
+    if st != 0:
+        raise BzkError(f"mpn_withdraw_verify_batch: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+    return ok.raw[:n], (fps.raw[: 32 * n] if want_fingerprint else None)
+
+
+def host_mpn_withdraw_verify_batch(txs: bytes, n: int, want_fingerprint: bool = True):
+    """Bzk.mpn_withdraw_verify_batch without a device: the same verdicts and fingerprints on host threads"""
+    return _mpn_withdraw_verify_batch(None, txs, n, want_fingerprint)

@@ -131,6 +131,26 @@ int32_t bzk_jubjub_verify_batch_compressed_dev(bzk_ctx* ctx, const void* pk_x_de
  * checked on the device, in rounds of 2^16 transactions; synchronises.  ctx = NULL: the same on host threads (bzk_host_default_threads). */
 int32_t bzk_mpn_tx_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* hash_out);
 
+/* ---- batched SHA3-256 and hash_to_scalar -----------------------------------------------------------------
+ * n messages: message i = data[off[i] .. off[i+1]), off has n + 1 entries, off[0] = 0, non-decreasing.  One lane per message, which loops
+ * over as many 136-byte blocks as its own length needs (FIPS 202: rate 136, suffix 0x06, final 0x80).
+ * digest_out (n x 32, may be NULL) = SHA3-256; scalar_out (n x 32, may be NULL) = hash_to_scalar (src/zk/mod.rs:218-220), i.e.
+ * ZkScalar::new of the digest read as a little-endian integer, Montgomery.  At least one of the two outputs must be given.  n = 0 is a
+ * no-op.  The host form checks off, stages through the context's workspace (in rounds of 2^20 messages or 64 MiB) and synchronises; the
+ * _dev form enqueues on the context's stream and trusts off (digest_out_dev 4-byte, scalar_out_dev 16-byte aligned). */
+int32_t bzk_sha3_256_batch(bzk_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n, uint8_t* digest_out, uint8_t* scalar_out);
+int32_t bzk_sha3_256_batch_dev(bzk_ctx* ctx, const void* data_dev, const void* off_dev, uint64_t n, void* digest_out_dev, void* scalar_out_dev);
+/* MpnWithdraw's two checks for n withdrawals given as n consecutive bincode(MpnWithdraw) (PointCompressed, u32 nonce, Signature,
+ * ContractWithdraw: 245 bytes and up, len bytes in all).  ok[i]: bit 0 = MpnWithdraw::verify_signature (src/core/transaction.rs:183-189),
+ * bit 1 = verify_calldata (:177-182; the payment's 32 calldata bytes are compared as bytes with the limbs of H6's output).
+ * fingerprint_out (n x 32, may be NULL) = payment.fingerprint() (:204-211): SHA3-256 of the payment with its calldata read as zeros, then
+ * ZkScalar::new.  BZK_E_ARG with bzk_mpn_work_last_error() naming the record when the bytes are not n well-formed records, nothing written;
+ * a payment longer than 65 536 bytes is refused as malformed too (its memo is unbounded on the wire), on both paths.  A key that does not
+ * decompress, or key / signature scalars that are not residues' limbs, give ok = 0 for that record, not an error.  The host only parses:
+ * fingerprint, key decompression, both Poseidon hashes and the signature check run on the device, in rounds that end at 2^16 records or
+ * 64 MiB of payment bytes, whichever comes first; synchronises.  ctx = NULL: the same on host threads (bzk_host_default_threads). */
+int32_t bzk_mpn_withdraw_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* fingerprint_out);
+
 /* ---- K2: dense 4-ary ZkState tree re-hash ----------------------------------------------------
  * Root of `ZkStateModel::List{log4_size, Scalar}` with every leaf present, as
  * `ZkStateBuilder::compress` / `KvStoreStateManager::root` would give (src/zk/state/mod.rs:66-90,
@@ -397,6 +417,15 @@ int32_t bzk_mpn_push_tx(bzk_mpn* w, uint64_t src_index, uint64_t dst_index, cons
  * checks run on the device in one batch; without, on host threads (bzk_mpn_set_threads).  ok_out (n bytes, may be NULL), *accepted_out
  * (may be NULL).  Nothing is queued on BZK_E_ARG (bytes that are not n well-formed records: bzk_mpn_work_last_error). */
 int32_t bzk_mpn_push_txs(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out);
+/* Mempool admission of withdrawals (src/blockchain/mempool.rs:246-258, plus the calldata check the reference makes in its builder,
+ * src/mpn/withdraw.rs:77): checks the n wire-form withdrawals (bzk_mpn_withdraw_verify_batch's input) and queues, in input order, those
+ * whose payment.contract_id is the world's, whose withdraw_circuit_id is 0, whose token ids are residues' limbs and whose two verdict bits
+ * are set.  They are queued with their payment bytes and the fingerprint derived from them, so bzk_mpn_make_work and the builders treat
+ * them exactly like withdrawals queued by bzk_mpn_push_withdraw(..., fingerprint = NULL).  With a context set (bzk_mpn_set_device) the
+ * checks run on the device; without, on host threads (bzk_mpn_set_threads).  ok_out (n bytes of 1 / 0, may be NULL), *accepted_out (may
+ * be NULL).  Nothing is queued on BZK_E_ARG (bytes that are not n well-formed records, or a payment over 65 536 bytes:
+ * bzk_mpn_work_last_error). */
+int32_t bzk_mpn_push_withdraws(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out);
 /* applies up to 4^log4_batch queued txs (update::update), pads with UpdateTransition::null, synthesizes the
  * circuit.  Public inputs = [commitment, height, state, aux_data, next_state]. */
 int32_t bzk_mpn_update_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_t commitment[32], const uint8_t fee_token[32],
@@ -412,7 +441,8 @@ int32_t bzk_mpn_push_deposit(bzk_mpn* w, uint64_t key_index, const uint8_t token
 int32_t bzk_mpn_push_withdraw(bzk_mpn* w, uint64_t account_index, const uint8_t token_id[32], uint64_t amount,
                               const uint8_t fee_token[32], uint64_t fee, const uint8_t fingerprint[32]);
 /* a withdrawal signed elsewhere, queued as given: the key need not be one the world holds, the signature (r.x | r.y | s over
- * H2(fingerprint, nonce)) is only checked by the builder.  Opaque fingerprint, so no wire form (see above). */
+ * H2(fingerprint, nonce)) is only checked by the builder.  Opaque fingerprint, so no wire form (see above); a withdrawal received on the wire
+ * goes through bzk_mpn_push_withdraws, which keeps its payment. */
 int32_t bzk_mpn_push_withdraw_signed(bzk_mpn* w, const uint8_t pub_xy[64], uint32_t nonce, const uint8_t token_id[32], uint64_t amount,
                                      const uint8_t fee_token[32], uint64_t fee, const uint8_t fingerprint[32], const uint8_t sig[96]);
 int32_t bzk_mpn_deposit_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_t commitment[32], int32_t record_matrices, bzk_r1cs** out);

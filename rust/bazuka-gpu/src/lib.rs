@@ -9,6 +9,9 @@
 //!   * `GpuPoseidonHasher`      - `impl ZkHasher` (src/zk/mod.rs:152-155, 496-511) + the BULK path `hash_batch`
 //!   * `Gpu::jubjub_verify_batch` - `JubJub::<ZkHasher>::verify` (src/crypto/jubjub/mod.rs:151-167) for many signatures at once
 //!   * `Gpu::mpn_tx_verify_batch` - `MpnTransaction::verify_signature` (src/zk/mod.rs:610-627) for many wire-form transactions at once
+//!   * `Gpu::mpn_withdraw_verify_batch` - `MpnWithdraw::verify_signature` and `verify_calldata` (src/core/transaction.rs:177-189) for many
+//!                                wire-form withdrawals at once, with `payment.fingerprint()` (:204-211, a SHA3-256) taken on the device
+//!   * `Gpu::sha3_256_batch`    - `hash_to_scalar` (src/zk/mod.rs:218-220) for many messages at once
 //!   * `groth16_prove`          - beside `groth16_verify` (src/zk/groth16/mod.rs:67-75), same argument order
 //!   * `compress`               - `ZkStateModel::compress::<H>(&data)` (src/zk/mod.rs:392-399)
 //!   * `DeviceStateManager`     - `KvStoreStateManager::{update_contract, root, get_data, prove}` (src/zk/state/mod.rs:218-438) for one
@@ -24,7 +27,7 @@
 //!
 //! Layout assumptions (already relied upon by the reference's own `transmute`s, src/zk/groth16/mod.rs:7-17): `ZkScalar` is
 //! `[u64; 4]` little-endian Montgomery limbs; bincode 1.3 with default options; `Groth16Proof` = 97 + 193 + 97 bytes under bincode.
-use bazuka::core::Address;
+use bazuka::core::{Address, MpnWithdraw};
 use bazuka::crypto::jubjub::{PublicKey, Signature};
 use bazuka::mpn::MpnWork;
 use bazuka::zk::groth16::Groth16Proof;
@@ -115,6 +118,42 @@ impl Gpu {
         }
         check(self.0, st)?;
         Ok(ok.into_iter().map(|b| b != 0).collect())
+    }
+
+    /// Bulk `MpnWithdraw::verify_signature` / `verify_calldata` (src/core/transaction.rs:177-189), what mempool admission
+    /// (src/blockchain/mempool.rs:246-258) and the withdraw builder (src/mpn/withdraw.rs:77) ask per withdrawal: `(signature ok, calldata ok)`.
+    /// The withdrawals travel as bincode; the fingerprint (SHA3-256 of the payment with its calldata blanked), the key decompression, both Poseidon
+    /// hashes and the signature check run on the device.  A payment longer than 65 536 bytes is refused (`GpuError::Status`).
+    pub fn mpn_withdraw_verify_batch(&self, txs: &[MpnWithdraw]) -> Result<Vec<(bool, bool)>, GpuError> {
+        let mut bytes = Vec::with_capacity(277 * txs.len());
+        for tx in txs {
+            bytes.extend_from_slice(&bincode::serialize(tx)?);
+        }
+        let mut ok = vec![0u8; txs.len()];
+        let st =
+            unsafe { sys::bzk_mpn_withdraw_verify_batch(self.0, bytes.as_ptr(), bytes.len() as u64, txs.len() as u64, ok.as_mut_ptr(), ptr::null_mut()) };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(self.0, st)?;
+        Ok(ok.into_iter().map(|b| (b & 1 != 0, b & 2 != 0)).collect())
+    }
+
+    /// Bulk `hash_to_scalar` (src/zk/mod.rs:218-220): `ZkScalar::new(sha3_256(msg))` per message, one device lane each.
+    pub fn sha3_256_batch(&self, msgs: &[&[u8]]) -> Result<Vec<ZkScalar>, GpuError> {
+        let mut off = Vec::with_capacity(msgs.len() + 1);
+        let mut data = Vec::new();
+        off.push(0u64);
+        for m in msgs {
+            data.extend_from_slice(m);
+            off.push(data.len() as u64);
+        }
+        let mut out = vec![ZkScalar::default(); msgs.len()];
+        check(self.0, unsafe {
+            sys::bzk_sha3_256_batch(self.0, data.as_ptr(), off.as_ptr(), msgs.len() as u64, ptr::null_mut(), out.as_mut_ptr() as *mut u8)
+        })?;
+        Ok(out)
     }
 
     /// Root of a dense `ZkStateModel::List { log4_size, item_type: Scalar }` (what `ZkStateBuilder::compress` returns for it)

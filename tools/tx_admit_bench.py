@@ -134,7 +134,7 @@ def transactions(ctx, sizes, host1_rate):
     rows = []
     for n in sizes:
         rep = (n + base_n - 1) // base_n
-        blob, w = b"".join((recs * rep)[:n]), ((want[0] * rep)[:n], (want[1] * rep)[:n])
+        blob, w = b"".join((recs * rep)[:n]), ((want[0] * rep)[:n], (want[1] * rep)[:32 * n])
         assert ctx.mpn_tx_verify_batch(blob, n) == w
         new = timed(lambda: ctx.mpn_tx_verify_batch(blob, n))
         kx, kodd = (sx * rep)[:32 * n] + (dx * rep)[:32 * n], (sodd * rep)[:n] + (dodd * rep)[:n]

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/bzk.h"
+#include "bzk_ws.h"
 
 struct bzk_prof_rec {
     const char* name;
@@ -40,9 +41,10 @@ struct bzk_ctx {
     bool prof = false;
     std::string prof_only;  // non-empty: only launches whose label contains it get event pairs (bzk_prof_filter)
     std::vector<bzk_prof_rec> recs;
-    // grow-only scratch buffer reused across calls
+    // grow-only scratch buffer reused across calls: carved by one bzk::WsLayout per call (bzk_ws.h), never addressed directly
     void* ws = nullptr;
     size_t ws_bytes = 0;
+    const char* ws_live = nullptr;  // the call whose committed WsLayout is in scope (the slab must not move under it); cleared by its destructor
     // pinned host staging (small results)
     void* pinned = nullptr;
     size_t pinned_bytes = 0;
@@ -121,7 +123,6 @@ void bzk_params_set_vk_internal(bzk_params* p, const uint8_t vk[870]);
 
 namespace bzk {
 
-int32_t ws_reserve(bzk_ctx* ctx, size_t bytes);           // ensures ctx->ws has >= bytes
 bzk_ctx* ctx_lane(bzk_ctx* ctx, size_t i);                // i-th child context (nullptr on failure)
 bzk_ctx* ctx_part(bzk_ctx* ctx, size_t i, bool high_prio); // i-th window-range child of a split MSM call (nullptr on failure)
 int32_t pinned_reserve(bzk_ctx* ctx, size_t bytes);
@@ -130,19 +131,6 @@ int32_t pinned_reserve(bzk_ctx* ctx, size_t bytes);
 void lane_post(bzk_ctx* ctx, size_t i, std::function<void()> job);
 void lane_wait(bzk_ctx* ctx, size_t i);
 
-// bump allocator over ctx->ws
-struct WsCursor {
-    char* base;
-    size_t off = 0;
-    explicit WsCursor(void* b) : base((char*)b) {}
-    template <class T>
-    T* take(size_t count) {
-        off = (off + 255) & ~(size_t)255;
-        T* p = (T*)(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
 void witfill_free(bzk_ctx* ctx);  // witfill.hip
 // eddsa.hip: ok_dev[i] = verdict of signature i; device pointers, enqueued on the context's stream under the launch label "jubjub_verify"
 int32_t jubjub_verify_launch(bzk_ctx* ctx, const void* pub_xy_dev, const void* msg_dev, const void* sig_dev, uint64_t n, void* ok_dev);
@@ -195,7 +183,6 @@ int msm_g1_window_terms(uint64_t n);  // 0: a window-range G1 call leaves window
 int32_t g1_horner_terms_packed(const void* T, int count, int c, int w0, uint8_t* out);
 int32_t g1_horner_packed(const void* S, int count, int c, int w0, uint8_t* out);
 int32_t g2_horner_packed(const void* S, int count, int c, int w0, uint8_t* out);
-static inline size_t ws_pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 // an environment switch: set and not "0" (one getenv: the value is read from the pointer it was tested on)
 static inline bool env_on(const char* name) {
     const char* e = getenv(name);

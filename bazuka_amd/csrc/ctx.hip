@@ -16,7 +16,11 @@ namespace bzk {
 
 void ntt_free_tables(bzk_ctx* ctx);  // ntt.hip
 
-int32_t ws_reserve(bzk_ctx* ctx, size_t bytes) {
+int32_t ws_reserve(bzk_ctx* ctx, size_t bytes, const char* who) {
+    if (ctx->ws_live) {
+        ctx->last_error = std::string(who) + ": workspace reserved while the layout of " + ctx->ws_live + " is live";
+        return BZK_E_INTERNAL;
+    }
     if (bytes <= ctx->ws_bytes) return BZK_OK;
     if (ctx->ws) {
         BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -32,6 +36,17 @@ int32_t ws_reserve(bzk_ctx* ctx, size_t bytes) {
         return BZK_E_ALLOC;
     }
     ctx->ws_bytes = want;
+    return BZK_OK;
+}
+
+int32_t WsLayout::commit(bzk_ctx* ctx) {
+    if (ok()) BZK_TRY(ws_reserve(ctx, bytes(), who_));
+    if (!bind(ctx->ws, ctx->ws_bytes)) {  // refuses a layout that is not ok() as well
+        ctx->last_error = std::string(who_) + (ok() ? ": workspace layout exceeds the reserved slab" : ": workspace layout overflows");
+        return BZK_E_INTERNAL;
+    }
+    live_ = &ctx->ws_live;
+    *live_ = who_;
     return BZK_OK;
 }
 

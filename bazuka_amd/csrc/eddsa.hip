@@ -169,26 +169,17 @@ int32_t jubjub_decompress_launch(bzk_ctx* ctx, const void* x_dev, const void* od
 
 // MpnTransaction::verify_signature for n parsed transactions (mpn.hip parses; TxSoA is what it hands over): per chunk one decompress launch over
 // the 2 m keys (src keys first, so that their points are the verifier's key array as they stand), the hash inputs, the arity-7 Poseidon batch, the
-// signature kernel, the verdicts.  No field arithmetic on the host.  685 bytes of workspace per transaction.
+// signature kernel, the verdicts.  No field arithmetic on the host.  639 bytes of workspace per transaction.
 int32_t mpn_tx_verify_run(bzk_ctx* ctx, const TxSoA& t, uint64_t n, uint8_t* ok, uint8_t* hash_out, uint8_t* src_xy_out, uint8_t* dst_xy_out) {
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
     const uint64_t cap = n < MPN_TX_CHUNK ? n : MPN_TX_CHUNK;
-    BZK_TRY(ws_reserve(ctx, ws_pad(cap * 64) + ws_pad(cap * 2) + ws_pad(cap * 128) + ws_pad(cap * 2) + ws_pad(cap * 64) + ws_pad(cap * 24) +
-                                ws_pad(cap * 96) + ws_pad(cap * 224) + ws_pad(cap * 32) + 3 * ws_pad(cap) + 4096));
-    WsCursor cur(ctx->ws);
-    uint8_t* dkx = cur.take<uint8_t>(cap * 64);
-    uint8_t* dodd = cur.take<uint8_t>(cap * 2);
-    uint8_t* dxy = cur.take<uint8_t>(cap * 128);
-    uint8_t* dkok = cur.take<uint8_t>(cap * 2);
-    uint8_t* dtok = cur.take<uint8_t>(cap * 64);
-    uint8_t* dnums = cur.take<uint8_t>(cap * 24);
-    uint8_t* dsig = cur.take<uint8_t>(cap * 96);
-    uint8_t* dtup = cur.take<uint8_t>(cap * 224);
-    uint8_t* dmsg = cur.take<uint8_t>(cap * 32);
-    uint8_t* dfit = cur.take<uint8_t>(cap);
-    uint8_t* dver = cur.take<uint8_t>(cap);
-    uint8_t* dok = cur.take<uint8_t>(cap);
+    WsLayout ws("mpn_tx_verify_run");
+    uint8_t *dkx, *dodd, *dxy, *dkok, *dtok, *dnums, *dsig, *dtup, *dmsg, *dfit, *dver, *dok;
+    ws.take(dkx, cap * 64); ws.take(dodd, cap * 2); ws.take(dxy, cap * 128); ws.take(dkok, cap * 2);  // both keys of every transaction
+    ws.take(dtok, cap * 64); ws.take(dnums, cap * 24); ws.take(dsig, cap * 96); ws.take(dtup, cap * 224); ws.take(dmsg, cap * 32);
+    ws.take(dfit, cap); ws.take(dver, cap); ws.take(dok, cap);
+    BZK_TRY(ws.commit(ctx));
     for (uint64_t off = 0; off < n; off += MPN_TX_CHUNK) {  // one stream: a chunk's uploads follow the previous chunk's kernels
         const uint64_t m = n - off < MPN_TX_CHUNK ? n - off : MPN_TX_CHUNK;
         BZK_HIP(ctx, hipMemcpyAsync(dkx, t.src_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
@@ -248,27 +239,13 @@ int32_t mpn_withdraw_verify_run(bzk_ctx* ctx, const WdSoA& t, uint64_t n, uint8_
         chunk_at.push_back(b);
         a = b;
     }
-    BZK_TRY(ws_reserve(ctx, ws_pad(cap_bytes) + 2 * ws_pad(cap * 8) + 2 * ws_pad(cap * 4) + 4 * ws_pad(cap * 32) + 2 * ws_pad(cap * 64) +
-                                ws_pad(cap * 96) + ws_pad(cap * 192) + 5 * ws_pad(cap) + 8192));
-    WsCursor cur(ctx->ws);
-    uint8_t* dbytes = cur.take<uint8_t>(cap_bytes);
-    uint8_t* dbeg = cur.take<uint8_t>(cap * 8);
-    uint8_t* dend = cur.take<uint8_t>(cap * 8);
-    uint8_t* dcd = cur.take<uint8_t>(cap * 4);
-    uint8_t* dnonce = cur.take<uint8_t>(cap * 4);
-    uint8_t* dkx = cur.take<uint8_t>(cap * 32);
-    uint8_t* dfp = cur.take<uint8_t>(cap * 32);
-    uint8_t* dmsg = cur.take<uint8_t>(cap * 32);
-    uint8_t* dcall = cur.take<uint8_t>(cap * 32);
-    uint8_t* dxy = cur.take<uint8_t>(cap * 64);
-    uint8_t* dh2 = cur.take<uint8_t>(cap * 64);
-    uint8_t* dsig = cur.take<uint8_t>(cap * 96);
-    uint8_t* dh6 = cur.take<uint8_t>(cap * 192);
-    uint8_t* dodd = cur.take<uint8_t>(cap);
-    uint8_t* dkok = cur.take<uint8_t>(cap);
-    uint8_t* dfit = cur.take<uint8_t>(cap);
-    uint8_t* dver = cur.take<uint8_t>(cap);
-    uint8_t* dok = cur.take<uint8_t>(cap);
+    WsLayout ws("mpn_withdraw_verify_run");
+    uint8_t *dbytes, *dbeg, *dend, *dcd, *dnonce, *dkx, *dfp, *dmsg, *dcall, *dxy, *dh2, *dsig, *dh6, *dodd, *dkok, *dfit, *dver, *dok;
+    ws.take(dbytes, cap_bytes); ws.take(dbeg, cap * 8); ws.take(dend, cap * 8); ws.take(dcd, cap * 4); ws.take(dnonce, cap * 4);
+    ws.take(dkx, cap * 32); ws.take(dfp, cap * 32); ws.take(dmsg, cap * 32); ws.take(dcall, cap * 32);
+    ws.take(dxy, cap * 64); ws.take(dh2, cap * 64); ws.take(dsig, cap * 96); ws.take(dh6, cap * 192);
+    ws.take(dodd, cap); ws.take(dkok, cap); ws.take(dfit, cap); ws.take(dver, cap); ws.take(dok, cap);
+    BZK_TRY(ws.commit(ctx));
     for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {  // one stream: a chunk's uploads follow the previous chunk's kernels
         const uint64_t off = chunk_at[c], m = chunk_at[c + 1] - off;
         BZK_HIP(ctx, hipMemcpyAsync(dbytes, t.txs + t.rec_off[off], t.rec_off[off + m] - t.rec_off[off], hipMemcpyHostToDevice, ctx->stream));
@@ -316,12 +293,10 @@ int32_t bzk_jubjub_verify_batch(bzk_ctx* ctx, const uint8_t* pub_xy, const uint8
     (void)hipSetDevice(ctx->device);
     constexpr uint64_t CHUNK = (uint64_t)1 << 20;  // 193 bytes per signature: at most 193 MB of workspace
     const uint64_t cap = n < CHUNK ? n : CHUNK;
-    BZK_TRY(ws_reserve(ctx, ws_pad(cap * 64) + ws_pad(cap * 32) + ws_pad(cap * 96) + ws_pad(cap) + 1024));
-    WsCursor cur(ctx->ws);
-    uint8_t* dpub = cur.take<uint8_t>(cap * 64);
-    uint8_t* dmsg = cur.take<uint8_t>(cap * 32);
-    uint8_t* dsig = cur.take<uint8_t>(cap * 96);
-    uint8_t* dok = cur.take<uint8_t>(cap);
+    WsLayout ws("bzk_jubjub_verify_batch");
+    uint8_t *dpub, *dmsg, *dsig, *dok;
+    ws.take(dpub, cap * 64); ws.take(dmsg, cap * 32); ws.take(dsig, cap * 96); ws.take(dok, cap);
+    BZK_TRY(ws.commit(ctx));
     for (uint64_t off = 0; off < n; off += CHUNK) {  // one stream: a chunk's uploads follow the previous chunk's kernel
         const uint64_t m = n - off < CHUNK ? n - off : CHUNK;
         BZK_HIP(ctx, hipMemcpyAsync(dpub, pub_xy + off * 64, m * 64, hipMemcpyHostToDevice, ctx->stream));
@@ -347,12 +322,10 @@ int32_t bzk_jubjub_decompress_batch(bzk_ctx* ctx, const uint8_t* x, const uint8_
     (void)hipSetDevice(ctx->device);
     constexpr uint64_t CHUNK = (uint64_t)1 << 20;  // 98 bytes per key
     const uint64_t cap = n < CHUNK ? n : CHUNK;
-    BZK_TRY(ws_reserve(ctx, ws_pad(cap * 32) + ws_pad(cap * 64) + 2 * ws_pad(cap) + 1024));
-    WsCursor cur(ctx->ws);
-    uint8_t* dx = cur.take<uint8_t>(cap * 32);
-    uint8_t* dodd = cur.take<uint8_t>(cap);
-    uint8_t* dxy = cur.take<uint8_t>(cap * 64);
-    uint8_t* dok = cur.take<uint8_t>(cap);
+    WsLayout ws("bzk_jubjub_decompress_batch");
+    uint8_t *dx, *dodd, *dxy, *dok;
+    ws.take(dx, cap * 32); ws.take(dodd, cap); ws.take(dxy, cap * 64); ws.take(dok, cap);
+    BZK_TRY(ws.commit(ctx));
     for (uint64_t off = 0; off < n; off += CHUNK) {
         const uint64_t m = n - off < CHUNK ? n - off : CHUNK;
         BZK_HIP(ctx, hipMemcpyAsync(dx, x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
@@ -366,16 +339,16 @@ int32_t bzk_jubjub_decompress_batch(bzk_ctx* ctx, const uint8_t* x, const uint8_
 }
 
 // decompress, then verify: a key that does not decompress leaves (0, 0), which is off the curve, so the verifier's verdict is already 0.  The
-// decompressed keys go through the context's workspace (97 bytes per key); its users are ordered by the context's stream
+// decompressed keys go through the context's workspace (65 bytes per key); its users are ordered by the context's stream
 int32_t bzk_jubjub_verify_batch_compressed_dev(bzk_ctx* ctx, const void* pk_x_dev, const void* pk_odd_dev, const void* msg_dev, const void* sig_dev,
                                                uint64_t n, void* ok_dev) {
     if (!ctx || (n && (!pk_x_dev || !pk_odd_dev || !msg_dev || !sig_dev || !ok_dev))) return BZK_E_ARG;
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    BZK_TRY(ws_reserve(ctx, ws_pad(n * 64) + ws_pad(n) + 512));
-    WsCursor cur(ctx->ws);
-    uint8_t* dxy = cur.take<uint8_t>(n * 64);
-    uint8_t* dkok = cur.take<uint8_t>(n);
+    WsLayout ws("bzk_jubjub_verify_batch_compressed_dev");
+    uint8_t *dxy, *dkok;
+    ws.take(dxy, n * 64); ws.take(dkok, n);
+    BZK_TRY(ws.commit(ctx));
     BZK_TRY(jubjub_decompress_launch(ctx, pk_x_dev, pk_odd_dev, n, dxy, dkok));
     return jubjub_verify_launch(ctx, dxy, msg_dev, sig_dev, n, ok_dev);
 }
@@ -387,15 +360,11 @@ int32_t bzk_jubjub_verify_batch_compressed(bzk_ctx* ctx, const uint8_t* pk_x, co
     (void)hipSetDevice(ctx->device);
     constexpr uint64_t CHUNK = (uint64_t)1 << 20;  // 227 bytes per signature
     const uint64_t cap = n < CHUNK ? n : CHUNK;
-    BZK_TRY(ws_reserve(ctx, 2 * ws_pad(cap * 32) + ws_pad(cap * 64) + ws_pad(cap * 96) + 3 * ws_pad(cap) + 2048));
-    WsCursor cur(ctx->ws);
-    uint8_t* dx = cur.take<uint8_t>(cap * 32);
-    uint8_t* dodd = cur.take<uint8_t>(cap);
-    uint8_t* dxy = cur.take<uint8_t>(cap * 64);
-    uint8_t* dkok = cur.take<uint8_t>(cap);
-    uint8_t* dmsg = cur.take<uint8_t>(cap * 32);
-    uint8_t* dsig = cur.take<uint8_t>(cap * 96);
-    uint8_t* dok = cur.take<uint8_t>(cap);
+    WsLayout ws("bzk_jubjub_verify_batch_compressed");
+    uint8_t *dx, *dodd, *dxy, *dkok, *dmsg, *dsig, *dok;
+    ws.take(dx, cap * 32); ws.take(dodd, cap); ws.take(dxy, cap * 64); ws.take(dkok, cap);
+    ws.take(dmsg, cap * 32); ws.take(dsig, cap * 96); ws.take(dok, cap);
+    BZK_TRY(ws.commit(ctx));
     for (uint64_t off = 0; off < n; off += CHUNK) {
         const uint64_t m = n - off < CHUNK ? n - off : CHUNK;
         BZK_HIP(ctx, hipMemcpyAsync(dx, pk_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
@@ -435,12 +404,10 @@ int32_t bzk_sha3_256_batch(bzk_ctx* ctx, const uint8_t* data, const uint64_t* of
         chunk_at.push_back(b);
         a = b;
     }
-    BZK_TRY(ws_reserve(ctx, ws_pad(cap_bytes + 1) + ws_pad((cap + 1) * 8) + 2 * ws_pad(cap * 32) + 2048));
-    WsCursor cur(ctx->ws);
-    uint8_t* ddata = cur.take<uint8_t>(cap_bytes ? cap_bytes : 1);
-    uint8_t* doff = cur.take<uint8_t>((cap + 1) * 8);
-    uint8_t* ddig = cur.take<uint8_t>(cap * 32);
-    uint8_t* dsc = cur.take<uint8_t>(cap * 32);
+    WsLayout ws("bzk_sha3_256_batch");
+    uint8_t *ddata, *doff, *ddig, *dsc;
+    ws.take(ddata, cap_bytes ? cap_bytes : 1); ws.take(doff, (cap + 1) * 8); ws.take(ddig, cap * 32); ws.take(dsc, cap * 32);
+    BZK_TRY(ws.commit(ctx));
     for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {
         const uint64_t a = chunk_at[c], m = chunk_at[c + 1] - a, bytes = off[a + m] - off[a];
         if (bytes) BZK_HIP(ctx, hipMemcpyAsync(ddata, data + off[a], bytes, hipMemcpyHostToDevice, ctx->stream));

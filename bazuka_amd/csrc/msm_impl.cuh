@@ -1935,59 +1935,48 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
     // capacity of the per-task partial sums: sized for the shortest run length any later adjustment can pick (32; 64 for tables)
     const uint64_t t_cap = std::max<uint64_t>((uint64_t)nb_max + len_max / std::min<uint32_t>(seg, 32u) + 1,
                                               dedup ? (uint64_t)m_max + n / seg_dd + 1 : 0);
-    size_t total = 0;
-    total += 4 * ws_pad(len_max * 4);                 // keys, vals, keys_sorted, vals_sorted
-    total += 7 * ws_pad((size_t)nb_alloc * 4);        // start, count, count_sorted, iota, order, ntask, tbase
-    total += ws_pad((size_t)t_cap * sizeof(Pt));      // per-task partial sums (multi-task buckets only)
     const size_t wide_cap = (size_t)t_cap / 32 + 2 * MSM_FOLD_WIDE_POS + 2;  // slot(i) + chunks(i) <= t / 64 + i + t / 64 + 1 (msm_fold_wide_slot)
-    total += ws_pad(wide_cap * sizeof(Pt));
-    total += ws_pad((size_t)nb_alloc * sizeof(Pt));   // buckets
-    total += ws_pad((size_t)group * per_win_out * sizeof(Pt));
-    if (two_level) total += ws_pad((size_t)group * per_win * sizeof(Pt));
-    total += ws_pad(((size_t)group * (per_win_out / C::WSUM_THREADS + 1)) * sizeof(Pt));
-    total += ws_pad((size_t)w_total * sizeof(StdPt));
     const size_t n_sets_max = (table && !folded) ? 1 : (size_t)group;
     const size_t n_terms = (size_t)c / 2 + 1;  // per bucket set: ceil((c - 1) / 2) digit terms + the plain sum (msm_bitsum_quad_kernel)
-    if (bitsum) total += ws_pad(n_sets_max * rc_per_set * sizeof(Pt)) + ws_pad(n_sets_max * n_terms * sizeof(StdPt));
-    if (C::CONVERT_BASES && !table) total += ws_pad((size_t)((prep ? 0 : n) + (size_t)m_max * E) * sizeof(typename C::DevAff));
-    if (dedup) {
-        total += 11 * ws_pad(n * 4) + ws_pad(n * 32) + ws_pad((size_t)m_max * sizeof(typename C::Fld));
-    }
-    total += ws_pad(tmp) + 8192;
-    BZK_TRY(ws_reserve(ctx, total));
-    BZK_TRY(pinned_reserve(ctx, std::max<size_t>((size_t)w_total, bitsum ? n_sets_max * n_terms : 0) * sizeof(StdPt) + 64));
-    WsCursor cur(ctx->ws);
-    uint32_t* keys = cur.take<uint32_t>(len_max);
-    uint32_t* vals = cur.take<uint32_t>(len_max);
-    uint32_t* keys_s = cur.take<uint32_t>(len_max);
-    uint32_t* vals_s = cur.take<uint32_t>(len_max);
+    // every buffer of the call, declared once; what a configuration does not take stays null
+    WsLayout ws("msm_run");
+    uint32_t *keys, *vals, *keys_s, *vals_s;
     BucketArrays<Pt> BA;
-    BA.start = cur.take<uint32_t>(nb_alloc);
-    BA.count = cur.take<uint32_t>(nb_alloc);
-    BA.count_s = cur.take<uint32_t>(nb_alloc);
-    BA.iota = cur.take<uint32_t>(nb_alloc);
-    BA.order = cur.take<uint32_t>(nb_alloc);
-    BA.ntask = cur.take<uint32_t>(nb_alloc);
-    BA.tbase = cur.take<uint32_t>(nb_alloc);
-    BA.partial = cur.take<Pt>(t_cap);
-    BA.wide = cur.take<Pt>(wide_cap);
-    Pt* buckets = cur.take<Pt>(nb_alloc);
-    Pt* chunk_out = cur.take<Pt>((size_t)group * per_win_out);
-    Pt* chunk_tot = two_level ? cur.take<Pt>((size_t)group * per_win) : nullptr;
-    Pt* wpart = cur.take<Pt>((size_t)group * (per_win_out / C::WSUM_THREADS + 1));
-    StdPt* win_out = cur.take<StdPt>(w_total);
-    Pt* rc_buf = bitsum ? cur.take<Pt>(n_sets_max * rc_per_set) : nullptr;           // row sums of every set, then the column sums
-    StdPt* terms_out = bitsum ? cur.take<StdPt>(n_sets_max * n_terms) : nullptr;
-    const void* bases = table ? table->data : bases_raw;
-    typename C::DevAff* conv = nullptr;
-    typename C::DevAff* sums_aff = nullptr;  // de-duplication group sums in affine form: base indices n .. n + m_max
+    Pt *buckets, *chunk_out, *chunk_tot = nullptr, *wpart, *rc_buf = nullptr;
+    StdPt *win_out, *terms_out = nullptr;
+    typename C::DevAff *conv = nullptr, *sums_aff = nullptr;  // converted raw bases; de-duplication group sums in affine form: base indices n .. n + m_max
+    uint32_t *hkey = nullptr, *hkey_s = nullptr, *didx = nullptr, *didx_s = nullptr, *head = nullptr, *mhead = nullptr, *gid_ex = nullptr,
+             *mid_ex = nullptr, *key2 = nullptr, *rep = nullptr, *gof = nullptr;
+    U128* scal2 = nullptr;
+    typename C::Fld* pref = nullptr;
+    char* tmp_buf;
+    ws.take(keys, len_max); ws.take(vals, len_max); ws.take(keys_s, len_max); ws.take(vals_s, len_max);
+    ws.take(BA.start, nb_alloc); ws.take(BA.count, nb_alloc); ws.take(BA.count_s, nb_alloc); ws.take(BA.iota, nb_alloc);
+    ws.take(BA.order, nb_alloc); ws.take(BA.ntask, nb_alloc); ws.take(BA.tbase, nb_alloc);
+    ws.take(BA.partial, t_cap);  // per-task partial sums (multi-task buckets only)
+    ws.take(BA.wide, wide_cap);
+    ws.take(buckets, nb_alloc);
+    ws.take(chunk_out, (size_t)group * per_win_out);
+    if (two_level) ws.take(chunk_tot, (size_t)group * per_win);
+    ws.take(wpart, (size_t)group * (per_win_out / C::WSUM_THREADS + 1));
+    ws.take(win_out, w_total);
+    if (bitsum) ws.take(rc_buf, n_sets_max * rc_per_set);  // row sums of every set, then the column sums
+    if (bitsum) ws.take(terms_out, n_sets_max * n_terms);
+    const bool convert = !prep && C::CONVERT_BASES && !table;
+    if (prep && m_max) ws.take(sums_aff, (size_t)m_max * E);  // resident internal form, nothing to convert: group sums, then (endomorphism form) their images
+    if (convert) ws.take(conv, n + m_max);                     // raw bases in the internal form, then the group sums
+    if (dedup) {
+        ws.take(hkey, n); ws.take(hkey_s, n); ws.take(didx, n); ws.take(didx_s, n); ws.take(head, n); ws.take(mhead, n);
+        ws.take(gid_ex, n); ws.take(mid_ex, n); ws.take(key2, n); ws.take(rep, n); ws.take(gof, n);
+        ws.take(scal2, 2 * n); ws.take(pref, m_max);
+    }
+    ws.take(tmp_buf, tmp);
+    BZK_TRY(ws.commit(ctx));
+    BZK_TRY(pinned_reserve(ctx, std::max<size_t>((size_t)w_total, bitsum ? n_sets_max * n_terms : 0) * sizeof(StdPt) + 64));
+    if (convert) sums_aff = conv + n;
+    const void* bases = table ? table->data : prep ? prep->data : convert ? (const void*)conv : bases_raw;
     AuxJoin aux(ctx);
-    if (prep) {
-        bases = prep->data;  // resident internal form: nothing to convert
-        if (m_max) sums_aff = cur.take<typename C::DevAff>((size_t)m_max * E);  // group sums, then (endomorphism form) their images
-    } else if (C::CONVERT_BASES && !table) {
-        conv = cur.take<typename C::DevAff>(n + m_max);
-        sums_aff = conv + n;
+    if (convert) {
         // the conversion is not needed before the first accumulation: it runs on the side stream beside digits / sort
         if (msm_aux_ready(ctx) && hipEventRecord(ctx->ev_fork, ctx->stream) == hipSuccess &&
             hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0) == hipSuccess) {
@@ -2003,31 +1992,8 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
             (void)hipGetLastError();
             BZK_TRY(msm_convert_launch<C>(ctx, bases_raw, n, conv));
         }
-        bases = conv;
     }
     const uint32_t n_split = dedup ? (uint32_t)n : 0xffffffffu;
-    uint32_t *hkey = nullptr, *hkey_s = nullptr;
-    uint32_t *didx = nullptr, *didx_s = nullptr, *head = nullptr, *mhead = nullptr, *gid_ex = nullptr, *mid_ex = nullptr, *key2 = nullptr,
-             *rep = nullptr, *gof = nullptr;
-    U128* scal2 = nullptr;
-    typename C::Fld* pref = nullptr;
-    if (dedup) {
-        hkey = cur.take<uint32_t>(n);
-        hkey_s = cur.take<uint32_t>(n);
-        didx = cur.take<uint32_t>(n);
-        didx_s = cur.take<uint32_t>(n);
-        head = cur.take<uint32_t>(n);
-        mhead = cur.take<uint32_t>(n);
-        gid_ex = cur.take<uint32_t>(n);
-        mid_ex = cur.take<uint32_t>(n);
-        key2 = cur.take<uint32_t>(n);
-        rep = cur.take<uint32_t>(n);
-        gof = cur.take<uint32_t>(n);
-        scal2 = cur.take<U128>(2 * n);
-        pref = cur.take<typename C::Fld>(m_max);
-    }
-    void* tmp_buf = cur.take<char>(tmp);
-
     uint64_t n_eff = n;
     const void* scal_eff = scalars;
     if (dedup) {

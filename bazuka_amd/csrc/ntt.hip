@@ -510,11 +510,10 @@ static int32_t ntt_run_ex(bzk_ctx* ctx, void* data_dev, uint32_t log_n, int inve
             }
     }
     static const int ip32 = [] { const char* e = getenv("BZK_NTT_IP32"); return e ? (atoi(e) != 0 ? 1 : 0) : 1; }();  // 0: 48-B inter-pass elements (A/B runs)
-    void* tmp = nullptr;
-    if (T->nb > 1) {
-        BZK_TRY(ws_reserve(ctx, ws_pad(n * (ip32 ? sizeof(Fr) : sizeof(Fr29P))) + 512));
-        tmp = ctx->ws;
-    }
+    WsLayout ws("ntt_run");
+    char* tmp = nullptr;  // inter-pass elements
+    if (T->nb > 1) ws.take(tmp, n * (ip32 ? sizeof(Fr) : sizeof(Fr29P)));
+    BZK_TRY(ws.commit(ctx));
     const int d = inverse ? 1 : 0;
     const uint32_t tile_max = ntt_tile_elems();
     // tiles above 64 KiB of dynamic LDS need the opt-in; the attribute is per DEVICE, so remember it per device id (a process

@@ -557,10 +557,10 @@ int32_t bzk_poseidon_batch(bzk_ctx* ctx, const uint8_t* in, uint32_t arity, uint
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
     const size_t in_b = (size_t)n * arity * 32, out_b = (size_t)n * 32;
-    BZK_TRY(ws_reserve(ctx, ws_pad(in_b) + ws_pad(out_b) + 512));
-    WsCursor cur(ctx->ws);
-    uint8_t* din = cur.take<uint8_t>(in_b);
-    uint8_t* dout = cur.take<uint8_t>(out_b);
+    WsLayout ws("bzk_poseidon_batch");
+    uint8_t *din, *dout;
+    ws.take(din, in_b); ws.take(dout, out_b);
+    BZK_TRY(ws.commit(ctx));
     BZK_HIP(ctx, hipMemcpyAsync(din, in, in_b, hipMemcpyHostToDevice, ctx->stream));
     BZK_TRY(poseidon_launch(ctx, din, arity, n, dout));
     BZK_HIP(ctx, hipMemcpyAsync(out, dout, out_b, hipMemcpyDeviceToHost, ctx->stream));
@@ -579,11 +579,10 @@ int32_t bzk_merkle4_root_dev(bzk_ctx* ctx, const void* leaves_dev, uint32_t log4
         return BZK_OK;
     }
     const uint64_t n_internal = ((((uint64_t)1) << (2 * log4)) - 1) / 3;
+    WsLayout ws("bzk_merkle4_root_dev");
     uint8_t* nodes = (uint8_t*)nodes_opt_dev;
-    if (!nodes) {
-        BZK_TRY(ws_reserve(ctx, ws_pad(n_internal * 32) + 512));
-        nodes = (uint8_t*)ctx->ws;
-    }
+    if (!nodes) ws.take(nodes, n_internal * 32);
+    BZK_TRY(ws.commit(ctx));
     const uint8_t* child = (const uint8_t*)leaves_dev;
     for (int k = (int)log4 - 1; k >= 0; --k) {
         const uint64_t cnt = (uint64_t)1 << (2 * k);
@@ -726,10 +725,11 @@ int32_t bzk_tree4_update(bzk_ctx* ctx, bzk_tree4* t, const uint64_t* idx, const 
             all.insert(all.end(), parents.begin(), parents.end());
         }
     }
-    BZK_TRY(ws_reserve(ctx, ws_pad(all.size() * 8) + ws_pad(m * 32) + 512));
-    WsCursor cur(ctx->ws);
-    uint64_t* d_idx = cur.take<uint64_t>(all.size());
-    Fr* d_val = cur.take<Fr>(m);
+    WsLayout ws("bzk_tree4_update");
+    uint64_t* d_idx;
+    Fr* d_val;
+    ws.take(d_idx, all.size()); ws.take(d_val, m);
+    BZK_TRY(ws.commit(ctx));
     BZK_HIP(ctx, hipMemcpyAsync(d_idx, all.data(), all.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     BZK_HIP(ctx, hipMemcpyAsync(d_val, uval.data(), m * 32, hipMemcpyHostToDevice, ctx->stream));
     BZK_LAUNCH(ctx, "tree4_scatter", tree4_scatter_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, t->nodes + tree4_off(t->log4),
@@ -760,10 +760,11 @@ int32_t bzk_tree4_prove(bzk_ctx* ctx, const bzk_tree4* t, const uint64_t* idx, u
     for (uint64_t i = 0; i < n; ++i)
         if (idx[i] >= n_leaves) return BZK_E_ARG;
     const uint64_t cells = n * t->log4;
-    BZK_TRY(ws_reserve(ctx, ws_pad(n * 8) + ws_pad(cells * 96) + 512));
-    WsCursor cur(ctx->ws);
-    uint64_t* d_idx = cur.take<uint64_t>(n);
-    Fr* d_out = cur.take<Fr>(cells * 3);
+    WsLayout ws("bzk_tree4_prove");
+    uint64_t* d_idx;
+    Fr* d_out;
+    ws.take(d_idx, n); ws.take(d_out, cells * 3);
+    BZK_TRY(ws.commit(ctx));
     BZK_HIP(ctx, hipMemcpyAsync(d_idx, idx, n * 8, hipMemcpyHostToDevice, ctx->stream));
     BZK_LAUNCH(ctx, "tree4_prove", tree4_prove_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (const Fr*)t->nodes, t->log4,
                (const uint64_t*)d_idx, n, d_out);
@@ -1103,13 +1104,11 @@ int32_t bzk_mpn_state_compress_dev(bzk_ctx* ctx, uint32_t log4_tree, uint32_t lo
     if (n_acct * ts > ((uint64_t)1 << 32)) return BZK_E_ARG;
     // workspace: two ping-pong hash buffers of n_acct * ts scalars, the H5 inputs (n_acct x 5) and the account tree's nodes
     const uint64_t n_nodes = tree4_off(log4_tree);
-    BZK_TRY(ws_reserve(ctx, 2 * ws_pad(n_acct * ts * sizeof(Fr)) + ws_pad(n_acct * 5 * sizeof(Fr)) + ws_pad((n_acct + n_nodes) * sizeof(Fr)) + 1024));
-    WsCursor cur(ctx->ws);
-    Fr* h0 = cur.take<Fr>(n_acct * ts);
-    Fr* h1 = cur.take<Fr>(n_acct * ts);
-    Fr* in5 = cur.take<Fr>(n_acct * 5);
-    Fr* leaves = cur.take<Fr>(n_acct);
-    Fr* nodes = cur.take<Fr>(n_nodes ? n_nodes : 1);
+    WsLayout ws("bzk_mpn_state_compress_dev");
+    Fr *h0, *h1, *in5, *leaves, *nodes;
+    ws.take(h0, n_acct * ts); ws.take(h1, n_acct * ts); ws.take(in5, n_acct * 5);
+    ws.take(leaves, n_acct); ws.take(nodes, n_nodes ? n_nodes : 1);
+    BZK_TRY(ws.commit(ctx));
     BZK_TRY(poseidon_launch(ctx, tokens_dev, 2, n_acct * ts, h0));                                  // Struct{token, balance}
     Fr *src = h0, *dst = h1;
     for (int k = (int)log4_token_tree - 1; k >= 0; --k) {                                          // List{T, ..}: per-account sub-trees

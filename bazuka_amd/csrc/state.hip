@@ -300,14 +300,12 @@ int32_t compress_core(bzk_ctx* ctx, const Model& M, const uint64_t* loc_off, con
     // device: values array (constants | pair values | hashed nodes), gather indices, one staging buffer for the widest group
     uint64_t widest = 0;
     for (auto& g : groups) widest = std::max<uint64_t>(widest, g.count * g.arity);
-    const size_t vals_bytes = ((size_t)hash_base + nn) * 32;
-    const size_t total = ws_pad(vals_bytes) + ws_pad(gidx.size() * 4) + ws_pad(widest * 32) + 4096;
     (void)hipSetDevice(ctx->device);
-    BZK_TRY(ws_reserve(ctx, total));
-    WsCursor cur(ctx->ws);
-    Fr* d_vals = cur.take<Fr>((size_t)hash_base + nn);
-    uint32_t* d_idx = cur.take<uint32_t>(gidx.size());
-    Fr* d_in = cur.take<Fr>(widest);
+    WsLayout ws("compress_core");
+    Fr *d_vals, *d_in;
+    uint32_t* d_idx;
+    ws.take(d_vals, (size_t)hash_base + nn); ws.take(d_idx, gidx.size()); ws.take(d_in, widest);
+    BZK_TRY(ws.commit(ctx));
     BZK_HIP(ctx, hipMemcpyAsync(d_vals, P.consts.data(), (size_t)n_const * 32, hipMemcpyHostToDevice, ctx->stream));
     BZK_HIP(ctx, hipMemcpyAsync(d_vals + n_const, values, (size_t)n * 32, hipMemcpyHostToDevice, ctx->stream));
     BZK_HIP(ctx, hipMemcpyAsync(d_idx, gidx.data(), gidx.size() * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -441,10 +439,11 @@ int32_t state_read_slots(bzk_state* S, const std::vector<uint32_t>& idx, uint8_t
     bzk_ctx* ctx = S->ctx;
     if (idx.empty()) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    BZK_TRY(ws_reserve(ctx, ws_pad(idx.size() * 4) + ws_pad(idx.size() * 32) + 1024));
-    WsCursor cur(ctx->ws);
-    uint32_t* d_idx = cur.take<uint32_t>(idx.size());
-    Fr* d_out = cur.take<Fr>(idx.size());
+    WsLayout ws("state_read_slots");
+    uint32_t* d_idx;
+    Fr* d_out;
+    ws.take(d_idx, idx.size()); ws.take(d_out, idx.size());
+    BZK_TRY(ws.commit(ctx));
     BZK_HIP(ctx, hipMemcpyAsync(d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     BZK_LAUNCH(ctx, "state_gather", state_gather_kernel, dim3((unsigned)((idx.size() + 255) / 256)), dim3(256), 0, (const Fr*)S->d_vals,
                (const uint32_t*)d_idx, (uint64_t)idx.size(), d_out);
@@ -661,14 +660,12 @@ int32_t state_update_impl(bzk_state* S, const uint64_t* loc_off, const uint64_t*
         widest = std::max<uint64_t>(widest, (uint64_t)(e - r) * a.arity);
         r = e;
     }
-    BZK_TRY(ws_reserve(ctx, ws_pad(n * 32) + ws_pad(n * 4) + ws_pad(gidx.size() * 4) + ws_pad(gdst.size() * 4) + 2 * ws_pad(widest * 32) + 4096));
-    WsCursor cur(ctx->ws);
-    Fr* d_new = cur.take<Fr>(n);
-    uint32_t* d_sdst = cur.take<uint32_t>(n);
-    uint32_t* d_idx = cur.take<uint32_t>(gidx.size());
-    uint32_t* d_dst = cur.take<uint32_t>(gdst.size());
-    Fr* d_in = cur.take<Fr>(widest);
-    Fr* d_out = cur.take<Fr>(widest);
+    WsLayout ws("state_update_impl");
+    Fr *d_new, *d_in, *d_out;
+    uint32_t *d_sdst, *d_idx, *d_dst;
+    ws.take(d_new, n); ws.take(d_sdst, n); ws.take(d_idx, gidx.size()); ws.take(d_dst, gdst.size());
+    ws.take(d_in, widest); ws.take(d_out, widest);
+    BZK_TRY(ws.commit(ctx));
     // the sources of these copies are pageable vectors of this frame and the caller's `values`: no early return may leave one of
     // them in flight - a failed upload waits for the stream before it reports
     auto upload = [&]() -> int32_t {
@@ -739,11 +736,11 @@ int32_t hash_plan_run(bzk_ctx* ctx, const uint8_t* uploaded, uint64_t n_up, cons
     hashed_out.assign((size_t)n_hash * 32, 0);
     if (!n_hash) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    BZK_TRY(ws_reserve(ctx, ws_pad((n_up + n_hash) * 32) + ws_pad(n_idx * 4) + ws_pad(widest * 32) + 4096));
-    WsCursor cur(ctx->ws);
-    Fr* d_vals = cur.take<Fr>(n_up + n_hash);
-    uint32_t* d_idx = cur.take<uint32_t>(n_idx);
-    Fr* d_in = cur.take<Fr>(widest);
+    WsLayout ws("hash_plan_run");
+    Fr *d_vals, *d_in;
+    uint32_t* d_idx;
+    ws.take(d_vals, n_up + n_hash); ws.take(d_idx, n_idx); ws.take(d_in, widest);
+    BZK_TRY(ws.commit(ctx));
     std::vector<uint32_t> all;
     all.reserve(n_idx);
     for (auto& g : groups) all.insert(all.end(), g.in.begin(), g.in.end());

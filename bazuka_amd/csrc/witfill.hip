@@ -482,7 +482,8 @@ int32_t witfill_run_dev(bzk_ctx* ctx, const DeferData& dd, const wf::Arrays& A, 
         it = S->progs.emplace(&P, dp).first;
     }
     const size_t n_tx = dd.n_tx;
-    const size_t in_bytes = ws_pad(n_tx * (size_t)P.n_inputs * 32), reg_bytes = ws_pad(n_tx * (size_t)P.n_regs * 32);
+    auto pad256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t in_bytes = pad256(n_tx * (size_t)P.n_inputs * 32), reg_bytes = pad256(n_tx * (size_t)P.n_regs * 32);
     if (S->scratch_bytes < 256 + in_bytes + reg_bytes) {
         // the previous buffer may still be read by launches of an earlier call on this stream
         BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -118,7 +118,7 @@ int32_t bzk_jubjub_verify_batch_dev(bzk_ctx* ctx, const void* pub_xy_dev, const 
 int32_t bzk_jubjub_decompress_batch(bzk_ctx* ctx, const uint8_t* x, const uint8_t* odd, uint64_t n, uint8_t* xy_out, uint8_t* ok);
 int32_t bzk_jubjub_decompress_batch_dev(bzk_ctx* ctx, const void* x_dev, const void* odd_dev, uint64_t n, void* xy_out_dev, void* ok_dev);
 /* JubJub::verify as the reference calls it, on a compressed PublicKey: decompress, then bzk_jubjub_verify_batch.  ok = 0 where the key
- * does not decompress.  The _dev form keeps the decompressed keys in the context's workspace (97 bytes per key). */
+ * does not decompress.  The _dev form keeps the decompressed keys in the context's workspace (65 bytes per key). */
 int32_t bzk_jubjub_verify_batch_compressed(bzk_ctx* ctx, const uint8_t* pk_x, const uint8_t* pk_odd, const uint8_t* msg, const uint8_t* sig,
                                            uint64_t n, uint8_t* ok);
 int32_t bzk_jubjub_verify_batch_compressed_dev(bzk_ctx* ctx, const void* pk_x_dev, const void* pk_odd_dev, const void* msg_dev,

@@ -95,6 +95,7 @@ struct bzk_ctx {
     bool heavy_tried = false;
     bool heavy_force = false;  // a later window range of a split call (msm_run_split, priority mode 2): HeavyScope applies whatever BZK_MSM_HEAVY_PRIO says
     void* eddsa_tab = nullptr;  // eddsa.hip: the signature verifier's fixed-base table (multiples of Jubjub's BASE, 29-bit form), built on first use
+    void* ed25519_tab = nullptr;  // eddsa.hip: the Ed25519 verifier's fixed-base table (j 16^i B, bzk_ed25519.cuh base_table_build), built on first use
     void* wf_state = nullptr;  // witfill.hip: device copies of the deferred-witness programs, dense Poseidon constants, scratch (witfill_free)
     // bzk_r1cs_stage: staged assignments handed back by bzk_staged_free (possibly from another thread: the prover's), kept for the next call
     std::mutex staged_mu;
@@ -169,6 +170,23 @@ constexpr uint64_t MPN_WD_CHUNK_BYTES = (uint64_t)64 << 20;   // payment bytes s
 // eddsa.hip: ok n bytes (bit 0 verify_signature, bit 1 verify_calldata); fp_out n x 32 (payment.fingerprint()), xy_out n x 64 (the decompressed
 // keys) or null; synchronises
 int32_t mpn_withdraw_verify_run(bzk_ctx* ctx, const WdSoA& t, uint64_t n, uint8_t* ok, uint8_t* fp_out, uint8_t* xy_out);
+// n parsed MpnDeposits (host memory; mpn.hip cuts them out of the bincode without hashing or field arithmetic)
+struct DpSoA {
+    const uint8_t* txs;        // the records as received
+    const uint64_t* rec_off;   // n + 1: where record i starts in txs
+    const uint64_t* pay_off;   // n: where its ContractDeposit starts in txs
+    const uint32_t* tag_off;   // n: the Option<Signature> tag's offset inside the payment: the signed bytes are payment[0 .. tag_off) | 0x00
+    const uint32_t* src_off;   // n: the 32 bytes of payment.src, offset inside the payment
+    const uint32_t* sig_off;   // n: the 64 signature bytes, offset inside the payment (0 where sig is None)
+    const uint8_t* has_sig;    // n: 1 / 0
+    const uint8_t* key_x;      // n x 32: PointCompressed.0
+    const uint8_t* key_odd;    // n: PointCompressed.1
+};
+// eddsa.hip: ok n bytes (bit 0 payment.verify_signature(), bit 1 mpn_address decompresses); xy_out n x 64 (the decompressed addresses) or null;
+// chunked like mpn_withdraw_verify_run; synchronises
+int32_t mpn_deposit_verify_run(bzk_ctx* ctx, const DpSoA& t, uint64_t n, uint8_t* ok, uint8_t* xy_out);
+// eddsa.hip: the same per-lane Ed25519 code on the host, for record i
+uint8_t mpn_deposit_sig_host(const DpSoA& t, uint64_t i);
 int32_t ntt_run(bzk_ctx* ctx, void* data_dev, uint32_t log_n, int inverse, int coset);  // ntt.hip
 int32_t ntt_h_chain(bzk_ctx* ctx, void* a, void* b, void* c, uint32_t log_m);              // ntt.hip: the h polynomial's 7 transforms, fused
 // msm_g1.hip / msm_g2.hip: windows [w_begin, w_end) (w_end < 0: all) of an MSM over a resident base set (or raw bases when `bases` is

@@ -320,6 +320,7 @@ void bzk_ctx_destroy(bzk_ctx* ctx) {
     for (auto& p : ctx->poseidon_dev)
         if (p) (void)hipFree(p);
     if (ctx->eddsa_tab) (void)hipFree(ctx->eddsa_tab);
+    if (ctx->ed25519_tab) (void)hipFree(ctx->ed25519_tab);
     bzk::ntt_free_tables(ctx);
     bzk::witfill_free(ctx);
     for (bzk_staged* st : ctx->staged_pool) {  // (handles still out at this point are the caller's leak: bzk_staged_free before bzk_ctx_destroy)

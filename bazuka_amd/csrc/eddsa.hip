@@ -7,10 +7,14 @@
 #define BZK_POSEIDON_MDS_RELOAD 1
 #include "bzk_decompress.cuh"
 #include "bzk_keccak.cuh"
+#include "bzk_ed25519.cuh"
+#include <atomic>
+#include <thread>
 #include "bzk_internal.h"
 
 namespace bzk {
 
+int host_default_threads();  // host_zk.hip
 int32_t poseidon_consts_dev_shared(bzk_ctx* ctx, int t, const void** out, int* rf, int* rp);  // poseidon.hip
 int32_t poseidon_launch(bzk_ctx* ctx, const void* in_dev, uint32_t arity, uint64_t n, void* out_dev);       // poseidon.hip
 
@@ -121,6 +125,47 @@ __global__ void __launch_bounds__(256) mpn_withdraw_verdict_kernel(const uint8_t
         diff |= w ^ h.l[k];
     }
     ok[i] = fit[i] ? (uint8_t)((verified[i] ? 1 : 0) | (diff == 0 ? 2 : 0)) : 0;
+}
+
+// SHA-512, one lane per message (bzk_sha512.cuh sha512_one): message i = data[begin[i] - base .. end[i] - base).  State and schedule ring are 48
+// registers and the rounds are integer work, so blocks of four waves as for SHA3; lanes of a wave leave the block loop at their own trip.
+constexpr int SHA512_BLOCK = 256;
+__global__ void __launch_bounds__(SHA512_BLOCK) sha512_kernel(const uint8_t* __restrict__ data, const uint64_t* __restrict__ begin,
+                                                              const uint64_t* __restrict__ end, uint64_t base, uint64_t n,
+                                                              uint32_t* __restrict__ digest) {
+    const uint64_t i = (uint64_t)blockIdx.x * SHA512_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t b = begin[i], e = end[i];
+    const sha512::Digest d = sha512::sha512_one(sha512::msg_one(data + (b - base), e > b ? e - b : 0));
+#pragma unroll
+    for (int k = 0; k < 16; ++k) digest[16 * i + k] = d.w[k];
+}
+
+// Ed25519, one lane per signature (bzk_ed25519.cuh verify_one): hash, reduction and group equation in one kernel.  Key i is the 32 bytes at
+// pk[pk_at[i]] (pk_at null: 32 i), signature i the 64 bytes at sig[sig_at[i]] (null: 64 i), message i = data[begin[i] - base .. end[i] - base)
+// followed by the byte `tail` where tail >= 0.  One wave per block: lane l keeps its table and its two scalars in column l of the block's LDS
+// (word k at lds[64 k + l]), 45 312 bytes per block, three blocks per CU.
+constexpr int ED25519_BLOCK = 64;
+__global__ void __launch_bounds__(ED25519_BLOCK) ed25519_verify_kernel(const uint8_t* __restrict__ pk, const uint64_t* __restrict__ pk_at,
+                                                                       const uint8_t* __restrict__ sig, const uint64_t* __restrict__ sig_at,
+                                                                       const uint8_t* __restrict__ data, const uint64_t* __restrict__ begin,
+                                                                       const uint64_t* __restrict__ end, uint64_t base, int32_t tail, uint64_t n,
+                                                                       const uint32_t* __restrict__ base_tab, uint8_t* __restrict__ ok) {
+    __shared__ uint32_t lds[ed25519::LANE_WORDS * ED25519_BLOCK];
+    const uint64_t i = (uint64_t)blockIdx.x * ED25519_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t b = begin[i], e = end[i];
+    sha512::Msg body = sha512::msg_one(data + (b - base), e > b ? e - b : 0);
+    body.tail = tail;
+    ok[i] = ed25519::verify_one(pk + (pk_at ? pk_at[i] : 32 * i), sig + (sig_at ? sig_at[i] : 64 * i), body, base_tab, lds + threadIdx.x,
+                                ED25519_BLOCK);
+}
+// ok[i]: bit 0 = the payment carries a signature and it verified, bit 1 = mpn_address decompressed
+__global__ void __launch_bounds__(256) mpn_deposit_verdict_kernel(const uint8_t* __restrict__ verified, const uint8_t* __restrict__ has_sig,
+                                                                  const uint8_t* __restrict__ key_ok, uint64_t m, uint8_t* __restrict__ ok) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    ok[i] = (uint8_t)((verified[i] && has_sig[i] ? 1 : 0) | (key_ok[i] ? 2 : 0));
 }
 
 static int32_t eddsa_table_dev(bzk_ctx* ctx, const Fr29** out) {
@@ -274,6 +319,146 @@ int32_t mpn_withdraw_verify_run(bzk_ctx* ctx, const WdSoA& t, uint64_t n, uint8_
     return BZK_OK;
 }
 
+static int32_t ed25519_table_dev(bzk_ctx* ctx, const uint32_t** out) {
+    if (!ctx->ed25519_tab) {
+        void* d = nullptr;
+        BZK_HIP(ctx, hipMalloc(&d, ed25519::BASE_TAB_WORDS * 4));
+        if (hipMemcpyAsync(d, ed25519::base_table_host(), ed25519::BASE_TAB_WORDS * 4, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipStreamSynchronize(ctx->stream) != hipSuccess) {
+            (void)hipFree(d);
+            ctx->last_error = "ed25519: table upload failed";
+            return BZK_E_DEVICE;
+        }
+        ctx->ed25519_tab = d;
+    }
+    *out = (const uint32_t*)ctx->ed25519_tab;
+    return BZK_OK;
+}
+
+static int32_t sha512_launch(bzk_ctx* ctx, const void* data_dev, const void* begin_dev, const void* end_dev, uint64_t base, uint64_t n,
+                             void* digest_dev) {
+    for (uint64_t off = 0; off < n; off += EDDSA_LAUNCH_MAX) {
+        const uint64_t m = n - off < EDDSA_LAUNCH_MAX ? n - off : EDDSA_LAUNCH_MAX;
+        BZK_LAUNCH(ctx, "sha512", sha512_kernel, dim3((unsigned)((m + SHA512_BLOCK - 1) / SHA512_BLOCK)), dim3(SHA512_BLOCK), 0,
+                   (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off, base, m,
+                   (uint32_t*)digest_dev + 16 * off);
+    }
+    return BZK_OK;
+}
+// pk_at_dev / sig_at_dev null: keys and signatures are packed arrays
+static int32_t ed25519_verify_launch(bzk_ctx* ctx, const void* pk_dev, const void* pk_at_dev, const void* sig_dev, const void* sig_at_dev,
+                                     const void* data_dev, const void* begin_dev, const void* end_dev, uint64_t base, int32_t tail, uint64_t n,
+                                     void* ok_dev) {
+    if (n == 0) return BZK_OK;
+    const uint32_t* tab;
+    BZK_TRY(ed25519_table_dev(ctx, &tab));
+    for (uint64_t off = 0; off < n; off += EDDSA_LAUNCH_MAX) {
+        const uint64_t m = n - off < EDDSA_LAUNCH_MAX ? n - off : EDDSA_LAUNCH_MAX;
+        BZK_LAUNCH(ctx, "ed25519_verify", ed25519_verify_kernel, dim3((unsigned)((m + ED25519_BLOCK - 1) / ED25519_BLOCK)), dim3(ED25519_BLOCK), 0,
+                   (const uint8_t*)pk_dev + (pk_at_dev ? 0 : 32 * off), pk_at_dev ? (const uint64_t*)pk_at_dev + off : nullptr,
+                   (const uint8_t*)sig_dev + (sig_at_dev ? 0 : 64 * off), sig_at_dev ? (const uint64_t*)sig_at_dev + off : nullptr,
+                   (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off, base, tail, m, tab,
+                   (uint8_t*)ok_dev + off);
+    }
+    return BZK_OK;
+}
+
+// fn(i) for every i < n on up to `threads` host threads
+template <class F>
+static void host_for_each(uint64_t n, int threads, F fn) {
+    std::atomic<uint64_t> next(0);
+    auto worker = [&] {
+        for (;;) {
+            const uint64_t i = next.fetch_add(1);
+            if (i >= n) break;
+            fn(i);
+        }
+    };
+    std::vector<std::thread> th;
+    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(threads, 1), n);
+    for (int k = 1; k < nt; ++k) th.emplace_back(worker);
+    worker();
+    for (auto& x : th) x.join();
+}
+
+uint8_t mpn_deposit_sig_host(const DpSoA& t, uint64_t i) {
+    if (!t.has_sig[i]) return 0;
+    const uint8_t* pay = t.txs + t.pay_off[i];
+    sha512::Msg body = sha512::msg_one(pay, t.tag_off[i]);
+    body.tail = 0;  // the None tag of the unsigned form
+    return ed25519::verify_host(pay + t.src_off[i], pay + t.sig_off[i], body);
+}
+
+// ContractDeposit::verify_signature and the address decompression for n parsed MpnDeposits (mpn.hip parses; DpSoA is what it hands over).  Chunks
+// as mpn_withdraw_verify_run cuts them; a chunk's records go up as they stand and the verifier reads key, signature and signed bytes inside them.
+// Per chunk: one Ed25519 launch, one decompress launch, the verdicts.  No hashing and no field arithmetic on the host.
+int32_t mpn_deposit_verify_run(bzk_ctx* ctx, const DpSoA& t, uint64_t n, uint8_t* ok, uint8_t* xy_out) {
+    if (n == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    std::vector<uint64_t> chunk_at(1, 0), begin(n), end(n), pk_at(n), sig_at(n);  // relative to their chunk's first byte
+    uint64_t cap = 0, cap_bytes = 0;
+    for (uint64_t a = 0; a < n;) {
+        uint64_t b = a, pay = 0;
+        while (b < n && b - a < MPN_TX_CHUNK && (b == a || pay + (t.rec_off[b + 1] - t.pay_off[b]) <= MPN_WD_CHUNK_BYTES))
+            pay += t.rec_off[b + 1] - t.pay_off[b], ++b;
+        for (uint64_t i = a; i < b; ++i) {
+            begin[i] = t.pay_off[i] - t.rec_off[a];
+            end[i] = begin[i] + t.tag_off[i];
+            pk_at[i] = begin[i] + t.src_off[i];
+            sig_at[i] = begin[i] + t.sig_off[i];
+        }
+        cap = std::max(cap, b - a);
+        cap_bytes = std::max(cap_bytes, t.rec_off[b] - t.rec_off[a]);
+        chunk_at.push_back(b);
+        a = b;
+    }
+    WsLayout ws("mpn_deposit_verify_run");
+    uint8_t *dbytes, *dbeg, *dend, *dpk, *dsg, *dkx, *dxy, *dodd, *dhas, *dkok, *dver, *dok;
+    ws.take(dbytes, cap_bytes); ws.take(dbeg, cap * 8); ws.take(dend, cap * 8); ws.take(dpk, cap * 8); ws.take(dsg, cap * 8);
+    ws.take(dkx, cap * 32); ws.take(dxy, cap * 64); ws.take(dodd, cap); ws.take(dhas, cap); ws.take(dkok, cap); ws.take(dver, cap);
+    ws.take(dok, cap);
+    BZK_TRY(ws.commit(ctx));
+    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {  // one stream: a chunk's uploads follow the previous chunk's kernels
+        const uint64_t off = chunk_at[c], m = chunk_at[c + 1] - off;
+        BZK_HIP(ctx, hipMemcpyAsync(dbytes, t.txs + t.rec_off[off], t.rec_off[off + m] - t.rec_off[off], hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dbeg, begin.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dend, end.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dpk, pk_at.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dsg, sig_at.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dkx, t.key_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dodd, t.key_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dhas, t.has_sig + off, m, hipMemcpyHostToDevice, ctx->stream));
+        BZK_TRY(ed25519_verify_launch(ctx, dbytes, dpk, dbytes, dsg, dbytes, dbeg, dend, 0, 0, m, dver));
+        BZK_TRY(jubjub_decompress_launch(ctx, dkx, dodd, m, dxy, dkok));
+        BZK_LAUNCH(ctx, "mpn_deposit_verdict", mpn_deposit_verdict_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, dver, dhas, dkok, m, dok);
+        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
+        if (xy_out) BZK_HIP(ctx, hipMemcpyAsync(xy_out + off * 64, dxy, m * 64, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
+// the chunks of a host batch of messages: at most `chunk` messages or `chunk_bytes` bytes each, and at least one message
+static void message_chunks(const uint64_t* off, uint64_t n, uint64_t chunk, uint64_t chunk_bytes, std::vector<uint64_t>& chunk_at, uint64_t& cap,
+                           uint64_t& cap_bytes) {
+    chunk_at.assign(1, 0);
+    cap = cap_bytes = 0;
+    for (uint64_t a = 0; a < n;) {
+        uint64_t b = a + 1;
+        while (b < n && b - a < chunk && off[b + 1] - off[a] <= chunk_bytes) ++b;
+        cap = std::max(cap, b - a);
+        cap_bytes = std::max(cap_bytes, off[b] - off[a]);
+        chunk_at.push_back(b);
+        a = b;
+    }
+}
+static bool offsets_ok(const uint64_t* off, uint64_t n) {
+    if (off[0] != 0) return false;
+    for (uint64_t i = 0; i < n; ++i)
+        if (off[i + 1] < off[i]) return false;
+    return true;
+}
+
 }  // namespace bzk
 
 using namespace bzk;
@@ -418,6 +603,97 @@ int32_t bzk_sha3_256_batch(bzk_ctx* ctx, const uint8_t* data, const uint64_t* of
     }
     BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return BZK_OK;
+}
+
+int32_t bzk_sha512_batch_dev(bzk_ctx* ctx, const void* data_dev, const void* off_dev, uint64_t n, void* digest_out_dev) {
+    if (!ctx || (n && (!data_dev || !off_dev || !digest_out_dev))) return BZK_E_ARG;
+    if (n == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    return sha512_launch(ctx, data_dev, off_dev, (const uint64_t*)off_dev + 1, 0, n, digest_out_dev);
+}
+
+int32_t bzk_sha512_batch(bzk_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n, uint8_t* digest_out) {
+    if (n && (!data || !off || !digest_out)) return BZK_E_ARG;
+    if (n == 0) return BZK_OK;
+    if (!offsets_ok(off, n)) return BZK_E_ARG;
+    if (!ctx) {  // the same per-lane code on host threads
+        host_for_each(n, host_default_threads(), [&](uint64_t i) {
+            const sha512::Digest d = sha512::sha512_one(sha512::msg_one(data + off[i], off[i + 1] - off[i]));
+            memcpy(digest_out + 64 * i, d.w, 64);
+        });
+        return BZK_OK;
+    }
+    (void)hipSetDevice(ctx->device);
+    std::vector<uint64_t> chunk_at;
+    uint64_t cap, cap_bytes;
+    message_chunks(off, n, (uint64_t)1 << 20, (uint64_t)64 << 20, chunk_at, cap, cap_bytes);
+    WsLayout ws("bzk_sha512_batch");
+    uint8_t *ddata, *doff, *ddig;
+    ws.take(ddata, cap_bytes ? cap_bytes : 1); ws.take(doff, (cap + 1) * 8); ws.take(ddig, cap * 64);
+    BZK_TRY(ws.commit(ctx));
+    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {
+        const uint64_t a = chunk_at[c], m = chunk_at[c + 1] - a, bytes = off[a + m] - off[a];
+        if (bytes) BZK_HIP(ctx, hipMemcpyAsync(ddata, data + off[a], bytes, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(doff, off + a, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        BZK_TRY(sha512_launch(ctx, ddata, doff, doff + 8, off[a], m, ddig));
+        BZK_HIP(ctx, hipMemcpyAsync(digest_out + a * 64, ddig, m * 64, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
+int32_t bzk_ed25519_verify_batch_dev(bzk_ctx* ctx, const void* pk_dev, const void* msg_dev, const void* off_dev, const void* sig_dev, uint64_t n,
+                                     void* ok_dev) {
+    if (!ctx || (n && (!pk_dev || !msg_dev || !off_dev || !sig_dev || !ok_dev))) return BZK_E_ARG;
+    if (n == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    return ed25519_verify_launch(ctx, pk_dev, nullptr, sig_dev, nullptr, msg_dev, off_dev, (const uint64_t*)off_dev + 1, 0, -1, n, ok_dev);
+}
+
+int32_t bzk_ed25519_verify_batch(bzk_ctx* ctx, const uint8_t* pk, const uint8_t* msg, const uint64_t* off, const uint8_t* sig, uint64_t n,
+                                 uint8_t* ok) {
+    if (n && (!pk || !msg || !off || !sig || !ok)) return BZK_E_ARG;
+    if (n == 0) return BZK_OK;
+    if (!offsets_ok(off, n)) return BZK_E_ARG;
+    if (!ctx) {
+        host_for_each(n, host_default_threads(), [&](uint64_t i) {
+            ok[i] = ed25519::verify_host(pk + 32 * i, sig + 64 * i, sha512::msg_one(msg + off[i], off[i + 1] - off[i]));
+        });
+        return BZK_OK;
+    }
+    (void)hipSetDevice(ctx->device);
+    std::vector<uint64_t> chunk_at;
+    uint64_t cap, cap_bytes;
+    message_chunks(off, n, (uint64_t)1 << 20, (uint64_t)64 << 20, chunk_at, cap, cap_bytes);
+    WsLayout ws("bzk_ed25519_verify_batch");
+    uint8_t *ddata, *doff, *dpk, *dsig, *dok;
+    ws.take(ddata, cap_bytes ? cap_bytes : 1); ws.take(doff, (cap + 1) * 8); ws.take(dpk, cap * 32); ws.take(dsig, cap * 64); ws.take(dok, cap);
+    BZK_TRY(ws.commit(ctx));
+    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {
+        const uint64_t a = chunk_at[c], m = chunk_at[c + 1] - a, bytes = off[a + m] - off[a];
+        if (bytes) BZK_HIP(ctx, hipMemcpyAsync(ddata, msg + off[a], bytes, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(doff, off + a, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dpk, pk + a * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dsig, sig + a * 64, m * 64, hipMemcpyHostToDevice, ctx->stream));
+        BZK_TRY(ed25519_verify_launch(ctx, dpk, nullptr, dsig, nullptr, ddata, doff, doff + 8, off[a], -1, m, dok));
+        BZK_HIP(ctx, hipMemcpyAsync(ok + a, dok, m, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
+int32_t bzk_host_sha512(const uint8_t* in, uint64_t len, uint8_t out[64]) {
+    if ((len && !in) || !out) return BZK_E_ARG;
+    const uint8_t none = 0;
+    const sha512::Digest d = sha512::sha512_one(sha512::msg_one(in ? in : &none, len));
+    memcpy(out, d.w, 64);
+    return BZK_OK;
+}
+
+int32_t bzk_host_ed25519_verify(const uint8_t pk[32], const uint8_t* msg, uint64_t len, const uint8_t sig[64]) {
+    if (!pk || !sig || (len && !msg)) return BZK_E_ARG;
+    const uint8_t none = 0;
+    return ed25519::verify_host(pk, sig, sha512::msg_one(msg ? msg : &none, len));
 }
 
 }  // extern "C"

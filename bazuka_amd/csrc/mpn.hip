@@ -2746,3 +2746,155 @@ int32_t bzk_mpn_push_withdraws(bzk_mpn* w, const uint8_t* txs, uint64_t len, uin
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Wire-form deposits: bincode(MpnDeposit) records in, verdicts and decompressed addresses out (bzk_mpn_deposit_verify_batch), accepted ones queued
+// with their payment bytes (bzk_mpn_push_deposits).  The parser only cuts byte ranges and reads integers and tags; the Ed25519 check of
+// ContractDeposit::verify_signature (src/core/transaction.rs:192-202) is eddsa.hip's, on the device or - the same per-lane code - on host threads.
+// ------------------------------------------------------------------------------------------------
+namespace bzk {
+namespace {
+std::atomic<uint32_t> g_wire_flags(0);  // bzk_mpn_set_wire_flags
+struct DpParsed {
+    const uint8_t* txs = nullptr;
+    std::vector<uint64_t> rec_off, pay_off, amount;
+    std::vector<uint32_t> pay_len, tag_off, src_off, sig_off, circuit;
+    std::vector<uint8_t> has_sig, key_x, key_odd, cid, tok;  // cid n x 32: payment.contract_id as a scalar; tok n x 32: amount.token_id
+    DpSoA soa() const {
+        return {txs, rec_off.data(), pay_off.data(), tag_off.data(), src_off.data(), sig_off.data(), has_sig.data(), key_x.data(), key_odd.data()};
+    }
+};
+bool parse_deposits(const uint8_t* txs, uint64_t len, uint64_t n, uint32_t flags, DpParsed& P, std::string& err) {
+    if (n > len / 150) {  // the shortest record: 33 + (8 + 4 + 4 + 32 + 40 + 2 x 12 + 4 + 1)
+        err = "fewer bytes than " + std::to_string(n) + " MpnDeposit records need";
+        return false;
+    }
+    P.txs = txs;
+    P.rec_off.resize(n + 1); P.pay_off.resize(n); P.amount.resize(n);
+    P.pay_len.resize(n); P.tag_off.resize(n); P.src_off.resize(n); P.sig_off.resize(n); P.circuit.resize(n);
+    P.has_sig.resize(n); P.key_x.resize(n * 32); P.key_odd.resize(n); P.cid.resize(n * 32); P.tok.resize(n * 32);
+    BinReader r(txs, (size_t)len);
+    uint8_t fee_tok[32];
+    const char* too_long = "ContractDeposit longer than 65536 bytes";
+    for (uint64_t i = 0; i < n && r.ok; ++i) {
+        P.rec_off[i] = r.pos;
+        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.key_x[32 * i], b, 32);
+        P.key_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
+        P.pay_off[i] = r.pos;
+        skip_string(r);
+        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail(too_long);
+        parse_contract_id(r, &P.cid[32 * i]);
+        P.circuit[i] = r.u32("deposit_circuit_id");
+        r.bytes(32, "calldata");
+        if (r.u64("ed25519 public key length") != 32) r.fail("ed25519 public key length");
+        P.src_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
+        r.bytes(32, "ed25519 public key");
+        parse_contract_id(r, &P.tok[32 * i]);
+        P.amount[i] = r.u64("Amount");
+        parse_contract_id(r, fee_tok);
+        r.u64("Amount");
+        r.u32("nonce");
+        P.tag_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
+        const uint8_t some = r.u8("Option<Signature> tag");
+        if (r.ok && some > 1) r.fail("Option tag");
+        P.has_sig[i] = some == 1;
+        P.sig_off[i] = 0;
+        if (r.ok && some) {
+            if (flags & BZK_WORK_SIG_LEN_PREFIXED)
+                if (r.u64("ed25519 signature length") != 64) r.fail("ed25519 signature length");
+            P.sig_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
+            r.bytes(64, "ed25519 signature");
+        }
+        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail(too_long);
+        P.pay_len[i] = (uint32_t)(r.pos - P.pay_off[i]);
+        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
+    }
+    if (r.ok) P.rec_off[n] = r.pos;
+    if (r.ok && r.pos != len) r.fail("bytes after the last record");
+    err = r.err;
+    return r.ok;
+}
+// all records: on the device when ctx is set, else on `threads` host threads; xy n x 64: the decompressed addresses (zeros where there is none)
+int32_t deposit_verify_all(bzk_ctx* ctx, int threads, const DpParsed& P, uint64_t n, uint8_t* ok, uint8_t* xy) {
+    if (ctx) return mpn_deposit_verify_run(ctx, P.soa(), n, ok, xy);
+    const DpSoA t = P.soa();
+    std::atomic<uint64_t> next(0);
+    auto worker = [&] {
+        for (;;) {
+            const uint64_t i = next.fetch_add(1);
+            if (i >= n) break;
+            PointAffine a;
+            const bool key_ok = decompress_checked(&P.key_x[32 * i], P.key_odd[i] != 0, a);
+            ok[i] = (uint8_t)(mpn_deposit_sig_host(t, i) | (key_ok ? 2 : 0));
+            if (xy) {
+                a.x.to_bytes(xy + 64 * i);
+                a.y.to_bytes(xy + 64 * i + 32);
+            }
+        }
+    };
+    std::vector<std::thread> th;
+    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(threads, 1), n);
+    for (int k = 1; k < nt; ++k) th.emplace_back(worker);
+    worker();
+    for (auto& x : th) x.join();
+    return BZK_OK;
+}
+}  // namespace
+}  // namespace bzk
+
+extern "C" {
+
+int32_t bzk_mpn_set_wire_flags(uint32_t flags) {
+    if (flags & ~BZK_WORK_SIG_LEN_PREFIXED) return BZK_E_ARG;
+    g_wire_flags.store(flags);
+    return BZK_OK;
+}
+
+int32_t bzk_mpn_deposit_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* addr_xy_out) {
+    if (n && (!txs || !ok)) return BZK_E_ARG;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        DpParsed P;
+        if (!parse_deposits(txs, len, n, g_wire_flags.load(), P, g_work_error)) return BZK_E_ARG;
+        return deposit_verify_all(ctx, host_default_threads(), P, n, ok, addr_xy_out);
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+int32_t bzk_mpn_push_deposits(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out) {
+    if (!w || (n && !txs)) return BZK_E_ARG;
+    if (accepted_out) *accepted_out = 0;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        DpParsed P;
+        if (!parse_deposits(txs, len, n, g_wire_flags.load(), P, g_work_error)) return BZK_E_ARG;
+        std::vector<uint8_t> ok(n), xy(n * 64);
+        if (const int32_t st = deposit_verify_all(w->dev, w->threads, P, n, ok.data(), xy.data()); st != BZK_OK) {
+            if (w->dev) w->dev_error = bzk_last_error(w->dev);
+            return st;
+        }
+        uint8_t world_id[32];
+        w->contract_id.to_bytes(world_id);
+        uint64_t accepted = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            // mempool.rs:241-258 for a deposit: the payment is for this contract's deposit circuit 0 and signed; the address as apply_deposit.rs:8 needs it
+            const bool admit = ok[i] == 3 && memcmp(&P.cid[32 * i], world_id, 32) == 0 && P.circuit[i] == 0 && limbs_of_a_residue(&P.tok[32 * i]);
+            ok[i] = admit ? 1 : 0;
+            if (!admit) continue;
+            DepositTx tx;
+            tx.mpn_address = {ZkScalar::from_bytes(&xy[64 * i]), ZkScalar::from_bytes(&xy[64 * i + 32])};
+            tx.amount = Money{ZkScalar::from_bytes(&P.tok[32 * i]), P.amount[i]};
+            tx.payment.assign(P.txs + P.pay_off[i], P.txs + P.pay_off[i] + P.pay_len[i]);
+            w->deposit_queue.push_back(std::move(tx));
+            ++accepted;
+        }
+        if (ok_out) memcpy(ok_out, ok.data(), n);
+        if (accepted_out) *accepted_out = accepted;
+        return BZK_OK;
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+}  // extern "C"

@@ -53,6 +53,12 @@ SIGNATURES = {
     "bzk_sha3_256_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "bzk_sha3_256_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "bzk_mpn_withdraw_verify_batch": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp]),
+    "bzk_sha512_batch": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "bzk_sha512_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "bzk_ed25519_verify_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_ed25519_verify_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_mpn_deposit_verify_batch": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp]),
+    "bzk_mpn_set_wire_flags": (_i32, [C.c_uint32]),
     "bzk_merkle4_root": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_merkle4_root_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_state_compress": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
@@ -123,6 +129,7 @@ SIGNATURES = {
     "bzk_mpn_tree_prove_token": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_mpn_push_txs": (_i32, [_vp, _vp, _u64, _u64, _vp, C.POINTER(_u64)]),
     "bzk_mpn_push_withdraws": (_i32, [_vp, _vp, _u64, _u64, _vp, C.POINTER(_u64)]),
+    "bzk_mpn_push_deposits": (_i32, [_vp, _vp, _u64, _u64, _vp, C.POINTER(_u64)]),
     "bzk_mpn_push_deposit": (_i32, [_vp, _u64, _vp, _u64]),
     "bzk_mpn_push_withdraw": (_i32, [_vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "bzk_mpn_push_withdraw_signed": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _vp]),
@@ -141,6 +148,8 @@ SIGNATURES = {
     "bzk_r1cs_free": (None, [_vp]),
     "bzk_host_poseidon": (_i32, [_vp, _u32, _vp]),
     "bzk_host_sha3_256": (_i32, [_vp, _u64, _vp]),
+    "bzk_host_sha512": (_i32, [_vp, _u64, _vp]),
+    "bzk_host_ed25519_verify": (_i32, [_vp, _vp, _u64, _vp]),
     "bzk_host_jubjub_keys": (_i32, [_vp, _u32, _vp]),
     "bzk_host_jubjub_sign": (_i32, [_vp, _vp, _vp]),
     "bzk_host_jubjub_verify": (_i32, [_vp, _vp, _vp]),
@@ -403,6 +412,19 @@ class Bzk:
         record raises"""
         return _mpn_withdraw_verify_batch(self.h, txs, n, want_fingerprint)
 
+    def sha512_batch(self, msgs) -> bytes:
+        """SHA-512 of each of the byte strings in msgs on the device: digests n x 64"""
+        return _sha512_batch(self.h, msgs)
+
+    def ed25519_verify_batch(self, pks: bytes, msgs, sigs: bytes) -> bytes:
+        """Ed25519 (the node's non-strict ed25519-dalek 1 verifier) for len(msgs) signatures: pks n x 32, sigs n x 64; verdict bytes"""
+        return _ed25519_verify_batch(self.h, pks, msgs, sigs)
+
+    def mpn_deposit_verify_batch(self, txs: bytes, n: int, want_address: bool = True):
+        """n consecutive bincode(MpnDeposit): (verdict bytes: bit 0 the payment's Ed25519 signature, bit 1 the address decompresses; addresses
+        n x 64 or None); a malformed record raises"""
+        return _mpn_deposit_verify_batch(self.h, txs, n, want_address)
+
     def merkle4_root(self, leaves: bytes, log4: int, want_nodes: bool = False):
         root = C.create_string_buffer(32)
         nn = (4 ** log4 - 1) // 3
@@ -446,6 +468,14 @@ class Bzk:
     def sha3_256_batch_dev(self, data, off, n: int, digest=None, scalar=None):
         """device buffers: data bytes, off n + 1 u64; digest n x 32 and / or scalar n x 32 are written in stream order"""
         self._ck(self.lib.bzk_sha3_256_batch_dev(self.h, _ptr(data), _ptr(off), n, _ptr(digest), _ptr(scalar)), "sha3_256_batch_dev")
+
+    def sha512_batch_dev(self, data, off, n: int, digest):
+        """device buffers: data bytes, off n + 1 u64; digest n x 64 is written in stream order"""
+        self._ck(self.lib.bzk_sha512_batch_dev(self.h, _ptr(data), _ptr(off), n, _ptr(digest)), "sha512_batch_dev")
+
+    def ed25519_verify_batch_dev(self, pk, msg, off, sig, n: int, ok):
+        """device buffers: pk n x 32, message bytes, off n + 1 u64, sig n x 64; ok n verdict bytes, written in stream order"""
+        self._ck(self.lib.bzk_ed25519_verify_batch_dev(self.h, _ptr(pk), _ptr(msg), _ptr(off), _ptr(sig), n, _ptr(ok)), "ed25519_verify_batch_dev")
 
     def merkle4_root_dev(self, leaves, log4: int, nodes=None) -> bytes:
         root = C.create_string_buffer(32)
@@ -1048,6 +1078,15 @@ class MpnWorld:
             raise BzkError(f"push_withdraws: {self.lib.bzk_strerror(st).decode()} [{self.lib.bzk_mpn_work_last_error().decode()}]")
         return ok.raw[:n], acc.value
 
+    def push_deposits(self, txs: bytes, n: int):
+        """mempool admission of n wire-form deposits (consecutive bincode(MpnDeposit)): (1 / 0 per record, number queued).  Checked on the
+        device when set_device was given a context, else on host threads; the accepted ones are queued in input order with their payments"""
+        ok, acc = C.create_string_buffer(max(n, 1)), _u64()
+        st = self.lib.bzk_mpn_push_deposits(self.h, _ptr(txs), len(txs), n, ok, C.byref(acc))
+        if st != 0:
+            raise BzkError(f"push_deposits: {self.lib.bzk_strerror(st).decode()} [{self.lib.bzk_mpn_work_last_error().decode()}]")
+        return ok.raw[:n], acc.value
+
     def push_deposit(self, key_index: int, token_id: bytes, amount: int):
         _st(self.lib.bzk_mpn_push_deposit(self.h, key_index, _ptr(token_id), amount), "push_deposit")
 
@@ -1395,3 +1434,72 @@ def _mpn_withdraw_verify_batch(ctx_handle, txs: bytes, n: int, want_fingerprint:
 def host_mpn_withdraw_verify_batch(txs: bytes, n: int, want_fingerprint: bool = True):
     """Bzk.mpn_withdraw_verify_batch without a device: the same verdicts and fingerprints on host threads"""
     return _mpn_withdraw_verify_batch(None, txs, n, want_fingerprint)
+
+
+def _offsets(msgs):
+    off = (_u64 * (len(msgs) + 1))()
+    for i, m in enumerate(msgs):
+        off[i + 1] = off[i] + len(m)
+    return off, (b"".join(msgs) or b"\0")
+
+
+def _sha512_batch(ctx_handle, msgs) -> bytes:
+    n = len(msgs)
+    off, data = _offsets(msgs)
+    dig = C.create_string_buffer(max(64 * n, 1))
+    _st(load_library().bzk_sha512_batch(ctx_handle, _ptr(data), off, n, dig), "sha512_batch")
+    return dig.raw[: 64 * n]
+
+
+def host_sha512_batch(msgs) -> bytes:
+    """Bzk.sha512_batch without a device: the same per-lane code on host threads"""
+    return _sha512_batch(None, msgs)
+
+
+def _ed25519_verify_batch(ctx_handle, pks: bytes, msgs, sigs: bytes) -> bytes:
+    n = len(msgs)
+    if len(pks) != 32 * n or len(sigs) != 64 * n:
+        raise BzkError("ed25519_verify_batch: pks must hold 32 and sigs 64 bytes per message")
+    off, data = _offsets(msgs)
+    ok = C.create_string_buffer(max(n, 1))
+    _st(load_library().bzk_ed25519_verify_batch(ctx_handle, _ptr(pks) if n else None, _ptr(data), off, _ptr(sigs) if n else None, n, ok),
+        "ed25519_verify_batch")
+    return ok.raw[:n]
+
+
+def host_ed25519_verify_batch(pks: bytes, msgs, sigs: bytes) -> bytes:
+    """Bzk.ed25519_verify_batch without a device: the same per-lane code on host threads"""
+    return _ed25519_verify_batch(None, pks, msgs, sigs)
+
+
+def host_sha512(b: bytes) -> bytes:
+    out = C.create_string_buffer(64)
+    _st(load_library().bzk_host_sha512(_ptr(b) if b else None, len(b), out), "host_sha512")
+    return out.raw
+
+
+def host_ed25519_verify(pk: bytes, msg: bytes, sig: bytes) -> bool:
+    r = load_library().bzk_host_ed25519_verify(_ptr(pk), _ptr(msg) if msg else None, len(msg), _ptr(sig))
+    if r < 0:
+        raise BzkError("ed25519_verify: bad argument")
+    return bool(r)
+
+
+def _mpn_deposit_verify_batch(ctx_handle, txs: bytes, n: int, want_address: bool):
+    lib = load_library()
+    ok = C.create_string_buffer(max(n, 1))
+    xy = C.create_string_buffer(max(64 * n, 1)) if want_address else None
+    st = lib.bzk_mpn_deposit_verify_batch(ctx_handle, _ptr(txs), len(txs), n, ok, xy)
+    if st != 0:
+        raise BzkError(f"mpn_deposit_verify_batch: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+    return ok.raw[:n], (xy.raw[: 64 * n] if want_address else None)
+
+
+def host_mpn_deposit_verify_batch(txs: bytes, n: int, want_address: bool = True):
+    """Bzk.mpn_deposit_verify_batch without a device: the same verdicts and addresses on host threads"""
+    return _mpn_deposit_verify_batch(None, txs, n, want_address)
+
+
+def mpn_set_wire_flags(flags: int):
+    """process-wide: WORK_SIG_LEN_PREFIXED where wire-form deposits carry length-prefixed Ed25519 signatures (ed25519 < 1.3), else 0"""
+    _st(load_library().bzk_mpn_set_wire_flags(flags), "mpn_set_wire_flags")

@@ -151,6 +151,35 @@ int32_t bzk_sha3_256_batch_dev(bzk_ctx* ctx, const void* data_dev, const void* o
  * 64 MiB of payment bytes, whichever comes first; synchronises.  ctx = NULL: the same on host threads (bzk_host_default_threads). */
 int32_t bzk_mpn_withdraw_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* fingerprint_out);
 
+/* ---- batched SHA-512 and Ed25519; wire-form deposits ----------------------------------------------------------
+ * SHA-512 (FIPS 180-4) of n messages laid out as for bzk_sha3_256_batch (off: n + 1 non-decreasing entries from 0); digest_out n x 64.  One
+ * lane per message.  n = 0 is a no-op; the host form checks off, stages through the workspace (rounds of 2^20 messages or 64 MiB) and
+ * synchronises; the _dev form enqueues on the context's stream and trusts off (digest_out_dev 4-byte aligned).  ctx = NULL (host form): the
+ * same per-lane code on host threads (bzk_host_default_threads). */
+int32_t bzk_sha512_batch(bzk_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n, uint8_t* digest_out);
+int32_t bzk_sha512_batch_dev(bzk_ctx* ctx, const void* data_dev, const void* off_dev, uint64_t n, void* digest_out_dev);
+/* Ed25519 as the node checks it (`ed25519-dalek = "1"` PublicKey::verify, src/crypto/ed25519.rs:81-83), one lane per signature: pk n x 32,
+ * sig n x 64 (R | s), messages as above; ok[i] = 1 / 0.  Cofactorless: encode([s]B - [k]A) == R as bytes, k = SHA-512(R | A | M) mod l; no
+ * small-order rejection; s >= l gives 0; A's y is taken mod p without a canonicity check and x = 0 with the sign bit set is accepted; a key
+ * that does not decode gives 0, not an error.  The L1 signature of every transaction of a block (src/blockchain/ops/apply_block.rs:88) is this
+ * check too.  Conventions as bzk_sha512_batch. */
+int32_t bzk_ed25519_verify_batch(bzk_ctx* ctx, const uint8_t* pk, const uint8_t* msg, const uint64_t* off, const uint8_t* sig, uint64_t n,
+                                 uint8_t* ok);
+int32_t bzk_ed25519_verify_batch_dev(bzk_ctx* ctx, const void* pk_dev, const void* msg_dev, const void* off_dev, const void* sig_dev, uint64_t n,
+                                     void* ok_dev);
+/* MpnDeposit's checks for n deposits given as n consecutive bincode(MpnDeposit) (PointCompressed, ContractDeposit: 150 bytes and up, len bytes
+ * in all).  ok[i]: bit 0 = payment.verify_signature() (src/core/transaction.rs:192-202: Ed25519 by payment.src over the payment's bytes up to
+ * the Option<Signature> tag followed by a None tag; sig: None gives 0), bit 1 = mpn_address decompresses (the reference's builder panics
+ * where it does not).  addr_xy_out (n x 64, may be NULL) = the decompressed address, zeros where there is none.  BZK_E_ARG with
+ * bzk_mpn_work_last_error() naming the record when the bytes are not n well-formed records or a payment is longer than 65 536 bytes; nothing
+ * is written then.  The host only parses; rounds end at 2^16 records or 64 MiB of payment bytes; synchronises.  ctx = NULL: the same per-lane
+ * code on host threads.  The signature inside the payment is read as the 64-tuple of ed25519 >= 1.3 unless bzk_mpn_set_wire_flags says
+ * otherwise. */
+int32_t bzk_mpn_deposit_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* addr_xy_out);
+/* process-wide: how wire-form records spell what the work codec takes a flag for (BZK_WORK_SIG_LEN_PREFIXED below, or 0).  Read by
+ * bzk_mpn_deposit_verify_batch and bzk_mpn_push_deposits; pass the same flags to bzk_mpn_work_decode for works made from such deposits. */
+int32_t bzk_mpn_set_wire_flags(uint32_t flags);
+
 /* ---- K2: dense 4-ary ZkState tree re-hash ----------------------------------------------------
  * Root of `ZkStateModel::List{log4_size, Scalar}` with every leaf present, as
  * `ZkStateBuilder::compress` / `KvStoreStateManager::root` would give (src/zk/state/mod.rs:66-90,
@@ -426,6 +455,13 @@ int32_t bzk_mpn_push_txs(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t 
  * be NULL).  Nothing is queued on BZK_E_ARG (bytes that are not n well-formed records, or a payment over 65 536 bytes:
  * bzk_mpn_work_last_error). */
 int32_t bzk_mpn_push_withdraws(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out);
+/* Mempool admission of deposits (src/blockchain/mempool.rs:241-258): checks the n wire-form deposits (bzk_mpn_deposit_verify_batch's input)
+ * and queues, in input order, those whose payment.contract_id is the world's, whose deposit_circuit_id is 0, whose amount.token_id is a
+ * residue's limbs and whose two verdict bits are set, each with its decompressed address, its amount and its payment bytes as received - so
+ * bzk_mpn_make_work carries the payment unchanged and the builders (src/blockchain/ops/apply_deposit.rs:8) treat it like a deposit queued by
+ * bzk_mpn_push_deposit.  With a context set the checks run on the device; without, on host threads.  ok_out (n bytes of 1 / 0, may be NULL),
+ * *accepted_out (may be NULL).  Nothing is queued on BZK_E_ARG.  Fee token, minimum fee, nonce and balance rules stay with the node. */
+int32_t bzk_mpn_push_deposits(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out);
 /* applies up to 4^log4_batch queued txs (update::update), pads with UpdateTransition::null, synthesizes the
  * circuit.  Public inputs = [commitment, height, state, aux_data, next_state]. */
 int32_t bzk_mpn_update_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_t commitment[32], const uint8_t fee_token[32],
@@ -565,6 +601,9 @@ int32_t bzk_host_jubjub_verify(const uint8_t pub_xy[64], const uint8_t msg[32], 
 /* PointCompressed::decompress (src/crypto/jubjub/curve.rs:78-88) on the host.  x: 32 B Montgomery, odd: 0 / 1.  Returns 1 / 0; 0 (and
  * xy_out = zeros) where the reference panics (no square root) or x is not a residue's limbs.  Negative on bad arguments. */
 int32_t bzk_host_jubjub_decompress(const uint8_t x[32], int32_t odd, uint8_t xy_out[64]);
+int32_t bzk_host_sha512(const uint8_t* in, uint64_t len, uint8_t out[64]);
+/* the verdict of bzk_ed25519_verify_batch for one signature, on the host */
+int32_t bzk_host_ed25519_verify(const uint8_t pk[32], const uint8_t* msg, uint64_t len, const uint8_t sig[64]);  /* 1 / 0 */
 
 /* ---- static-base tables (the Groth16 CRS queries are fixed point sets) -------------------------------------------
  * build: tab[w][i] = 2^(c w) * base_i for every window, kept in HBM (W x the base memory, internal limb form).  With a

@@ -12,6 +12,10 @@
 //!   * `Gpu::mpn_withdraw_verify_batch` - `MpnWithdraw::verify_signature` and `verify_calldata` (src/core/transaction.rs:177-189) for many
 //!                                wire-form withdrawals at once, with `payment.fingerprint()` (:204-211, a SHA3-256) taken on the device
 //!   * `Gpu::sha3_256_batch`    - `hash_to_scalar` (src/zk/mod.rs:218-220) for many messages at once
+//!   * `Gpu::mpn_deposit_verify_batch` - `ContractDeposit::verify_signature` (src/core/transaction.rs:192-202) for many wire-form deposits at
+//!                                once, and whether each `mpn_address` decompresses
+//!   * `Gpu::ed25519_verify_batch` - `Ed25519::verify` (src/crypto/ed25519.rs:81-83) for many (key, message, signature) at once
+//!   * `Gpu::sha512_batch`      - SHA-512 of many messages at once
 //!   * `groth16_prove`          - beside `groth16_verify` (src/zk/groth16/mod.rs:67-75), same argument order
 //!   * `compress`               - `ZkStateModel::compress::<H>(&data)` (src/zk/mod.rs:392-399)
 //!   * `DeviceStateManager`     - `KvStoreStateManager::{update_contract, root, get_data, prove}` (src/zk/state/mod.rs:218-438) for one
@@ -27,7 +31,7 @@
 //!
 //! Layout assumptions (already relied upon by the reference's own `transmute`s, src/zk/groth16/mod.rs:7-17): `ZkScalar` is
 //! `[u64; 4]` little-endian Montgomery limbs; bincode 1.3 with default options; `Groth16Proof` = 97 + 193 + 97 bytes under bincode.
-use bazuka::core::{Address, MpnWithdraw};
+use bazuka::core::{Address, MpnDeposit, MpnWithdraw};
 use bazuka::crypto::jubjub::{PublicKey, Signature};
 use bazuka::mpn::MpnWork;
 use bazuka::zk::groth16::Groth16Proof;
@@ -153,6 +157,60 @@ impl Gpu {
         check(self.0, unsafe {
             sys::bzk_sha3_256_batch(self.0, data.as_ptr(), off.as_ptr(), msgs.len() as u64, ptr::null_mut(), out.as_mut_ptr() as *mut u8)
         })?;
+        Ok(out)
+    }
+
+    /// Bulk `ContractDeposit::verify_signature` (src/core/transaction.rs:192-202), what mempool admission (src/blockchain/mempool.rs:241-258) asks
+    /// per deposit, and whether `mpn_address` decompresses (src/blockchain/ops/apply_deposit.rs:8 needs the point): `(signature ok, address ok)`.
+    /// The deposits travel as bincode; SHA-512, the reduction mod l, the group equation and the key decompression run on the device.  A payment
+    /// without a signature gives `false`; a payment longer than 65 536 bytes is refused (`GpuError::Status`).  A host built against an `ed25519`
+    /// release older than 1.3 calls `sys::bzk_mpn_set_wire_flags(sys::BZK_WORK_SIG_LEN_PREFIXED)` once before.
+    pub fn mpn_deposit_verify_batch(&self, txs: &[MpnDeposit]) -> Result<Vec<(bool, bool)>, GpuError> {
+        let mut bytes = Vec::with_capacity(246 * txs.len());
+        for tx in txs {
+            bytes.extend_from_slice(&bincode::serialize(tx)?);
+        }
+        let mut ok = vec![0u8; txs.len()];
+        let st =
+            unsafe { sys::bzk_mpn_deposit_verify_batch(self.0, bytes.as_ptr(), bytes.len() as u64, txs.len() as u64, ok.as_mut_ptr(), ptr::null_mut()) };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(self.0, st)?;
+        Ok(ok.into_iter().map(|b| (b & 1 != 0, b & 2 != 0)).collect())
+    }
+
+    /// Bulk `Ed25519::verify(pk, msg, sig)` (src/crypto/ed25519.rs:81-83: ed25519-dalek 1 `PublicKey::verify`, the non-strict verifier) over raw
+    /// bytes: 32-byte keys, 64-byte signatures.  What src/blockchain/ops/apply_block.rs:88 asks per transaction of a block.
+    pub fn ed25519_verify_batch(&self, items: &[(&[u8; 32], &[u8], &[u8; 64])]) -> Result<Vec<bool>, GpuError> {
+        let n = items.len();
+        let (mut pk, mut sig, mut data, mut off) = (Vec::with_capacity(32 * n), Vec::with_capacity(64 * n), Vec::new(), Vec::with_capacity(n + 1));
+        off.push(0u64);
+        for (k, m, s) in items {
+            pk.extend_from_slice(&k[..]);
+            sig.extend_from_slice(&s[..]);
+            data.extend_from_slice(m);
+            off.push(data.len() as u64);
+        }
+        let mut ok = vec![0u8; n];
+        check(self.0, unsafe {
+            sys::bzk_ed25519_verify_batch(self.0, pk.as_ptr(), data.as_ptr(), off.as_ptr(), sig.as_ptr(), n as u64, ok.as_mut_ptr())
+        })?;
+        Ok(ok.into_iter().map(|b| b != 0).collect())
+    }
+
+    /// SHA-512 per message, one device lane each
+    pub fn sha512_batch(&self, msgs: &[&[u8]]) -> Result<Vec<[u8; 64]>, GpuError> {
+        let mut off = Vec::with_capacity(msgs.len() + 1);
+        let mut data = Vec::new();
+        off.push(0u64);
+        for m in msgs {
+            data.extend_from_slice(m);
+            off.push(data.len() as u64);
+        }
+        let mut out = vec![[0u8; 64]; msgs.len()];
+        check(self.0, unsafe { sys::bzk_sha512_batch(self.0, data.as_ptr(), off.as_ptr(), msgs.len() as u64, out.as_mut_ptr() as *mut u8) })?;
         Ok(out)
     }
 

@@ -387,10 +387,23 @@ BZK_HD Fe fe_load(const uint32_t* at, int stride) {
     return r;
 }
 
-// The verdict for key pk (32 bytes), signature sig (64 bytes: R | s) and the message body (up to two ranges and a literal byte: body.p[2] /
-// body.len[2] are not used).  base_tab: base_table_build's words.  lane: LANE_WORDS words of the lane's own, word k at lane[k * stride] (the
-// kernel passes its LDS column, the host a local array).
-BZK_HD uint8_t verify_one(const uint8_t* pk, const uint8_t* sig, const sha512::Msg& body, const uint32_t* __restrict__ base_tab, uint32_t* lane,
+// SHA-512(R | A | M) for the two ways a message body is given.  A sha512::Msg body (up to two ranges and a literal byte: body.p[2] / body.len[2]
+// are not used) gets R and A as the ranges in front of it; a gathered body (bzk_gather.cuh) carries R | A as its first two pieces already
+// (gather::signed_form with_ra), since they lie in the same record as the signed bytes.
+BZK_HD sha512::Digest hash_ram(const uint8_t* pk, const uint8_t* sig, const sha512::Msg& body) {
+    sha512::Msg m;
+    m.p[0] = sig; m.len[0] = 32;
+    m.p[1] = pk; m.len[1] = 32;
+    m.p[2] = body.p[0]; m.len[2] = body.len[0];
+    m.tail = body.tail;
+    return sha512::sha512_one(m);
+}
+BZK_HD sha512::Digest hash_ram(const uint8_t*, const uint8_t*, const gather::Msg& body) { return sha512::sha512_one(body); }
+
+// The verdict for key pk (32 bytes), signature sig (64 bytes: R | s) and the message body (see hash_ram).  base_tab: base_table_build's words.
+// lane: LANE_WORDS words of the lane's own, word k at lane[k * stride] (the kernel passes its LDS column, the host a local array).
+template <class Body>
+BZK_HD uint8_t verify_one(const uint8_t* pk, const uint8_t* sig, const Body& body, const uint32_t* __restrict__ base_tab, uint32_t* lane,
                           int stride) {
     uint32_t key[8], r[8], s[8];
     load_words8(pk, key);
@@ -400,12 +413,7 @@ BZK_HD uint8_t verify_one(const uint8_t* pk, const uint8_t* sig, const sha512::M
     uint32_t* const kw = lane + VAR_TAB * CACHED_WORDS * stride;
     uint32_t* const sw = kw + 9 * stride;
     {
-        sha512::Msg m;
-        m.p[0] = sig; m.len[0] = 32;
-        m.p[1] = pk; m.len[1] = 32;
-        m.p[2] = body.p[0]; m.len[2] = body.len[0];
-        m.tail = body.tail;
-        const sha512::Digest h = sha512::sha512_one(m);
+        const sha512::Digest h = hash_ram(pk, sig, body);
         uint32_t k[8];
         sc_reduce512(h.w, k);
         uint64_t carry = 0;
@@ -495,7 +503,8 @@ inline const uint32_t* base_table_host() {
     return tab.data();
 }
 // verify_one with the lane's words on the stack
-inline uint8_t verify_host(const uint8_t* pk, const uint8_t* sig, const sha512::Msg& body) {
+template <class Body>
+inline uint8_t verify_host(const uint8_t* pk, const uint8_t* sig, const Body& body) {
     uint32_t lane[LANE_WORDS];
     return verify_one(pk, sig, body, base_table_host(), lane, 1);
 }

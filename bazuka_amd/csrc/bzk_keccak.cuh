@@ -9,10 +9,15 @@
 // Bytes are fetched eight at a time where the word lies wholly inside the message and outside the blanked range, byte by byte otherwise (the
 // message's tail and the words the blanked range touches).  The blanked range is how ContractWithdraw::fingerprint (src/core/transaction.rs:204-211)
 // hashes the payment "with calldata := 0" without a copy of the payment.
+//
+// The absorb loop is a template on where its words come from: the flat message with its blanked range, or a gathered message (bzk_gather.cuh),
+// which is how Transaction::hash (src/core/transaction.rs:383-385) hashes a record's signed form in place.  sha3_256_pair is the 64-byte case
+// of the block's Merkle tree (src/crypto/merkle.rs:9-19): one permutation.
 #pragma once
 #include <utility>
 
 #include "bzk_field.cuh"
+#include "bzk_gather.cuh"
 
 namespace bzk {
 namespace keccak {
@@ -103,8 +108,29 @@ BZK_HD uint64_t load_word(const uint8_t* __restrict__ data, uint64_t len, uint64
     return w;
 }
 
-// SHA3-256 of data[0 .. len) with the 32 bytes at blank_off (NO_BLANK: none) absorbed as zeros
-BZK_HD Digest sha3_256_one(const uint8_t* __restrict__ data, uint64_t len, uint64_t blank_off) {
+// where the absorb loop's words come from: load(pos) = the eight message bytes at pos as a little-endian word, zeros at or past the end
+struct FlatWords {
+    const uint8_t* __restrict__ data;
+    uint64_t len, blank_off;
+    BZK_HD uint64_t operator()(uint64_t pos) const { return load_word(data, len, pos, blank_off); }
+};
+struct GatheredWords {
+    const gather::Msg& m;
+    BZK_HD uint64_t operator()(uint64_t pos) const { return gather::fetch8_le(m, pos); }
+};
+
+BZK_HD Digest squeeze(const State& a) {
+    Digest d;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        d.w[2 * i] = (uint32_t)a.s[i];
+        d.w[2 * i + 1] = (uint32_t)(a.s[i] >> 32);
+    }
+    return d;
+}
+
+template <class Words>
+BZK_HD Digest sha3_256_absorb(uint64_t len, const Words& load) {
     State a;
 #pragma unroll
     for (int i = 0; i < 25; ++i) a.s[i] = 0;
@@ -116,7 +142,7 @@ BZK_HD Digest sha3_256_one(const uint8_t* __restrict__ data, uint64_t len, uint6
         const uint64_t rem = len - base;  // only meaningful in the last block: 0 .. 135 message bytes in it
 #pragma unroll
         for (int w = 0; w < 17; ++w) {
-            uint64_t v = load_word(data, len, base + 8 * w, blank_off);
+            uint64_t v = load(base + 8 * w);
             if (last) {
                 if ((rem >> 3) == (uint64_t)w) v ^= (uint64_t)0x06 << (8 * (rem & 7));
                 if (w == 16) v ^= (uint64_t)0x80 << 56;
@@ -125,13 +151,30 @@ BZK_HD Digest sha3_256_one(const uint8_t* __restrict__ data, uint64_t len, uint6
         }
         permute(a);
     }
-    Digest d;
+    return squeeze(a);
+}
+
+// SHA3-256 of data[0 .. len) with the 32 bytes at blank_off (NO_BLANK: none) absorbed as zeros
+BZK_HD Digest sha3_256_one(const uint8_t* __restrict__ data, uint64_t len, uint64_t blank_off) {
+    return sha3_256_absorb(len, FlatWords{data, len, blank_off});
+}
+// SHA3-256 of a gathered message
+BZK_HD Digest sha3_256_one(const gather::Msg& m) { return sha3_256_absorb(gather::total(m), GatheredWords{m}); }
+
+// SHA3-256 of the 64 bytes a | b (each eight little-endian words): less than one block, so one permutation
+BZK_HD Digest sha3_256_pair(const uint32_t* a, const uint32_t* b) {
+    State st;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        d.w[2 * i] = (uint32_t)a.s[i];
-        d.w[2 * i + 1] = (uint32_t)(a.s[i] >> 32);
+        st.s[i] = (uint64_t)a[2 * i] | ((uint64_t)a[2 * i + 1] << 32);
+        st.s[4 + i] = (uint64_t)b[2 * i] | ((uint64_t)b[2 * i + 1] << 32);
     }
-    return d;
+    st.s[8] = 0x06;
+#pragma unroll
+    for (int i = 9; i < 25; ++i) st.s[i] = 0;
+    st.s[16] = (uint64_t)0x80 << 56;
+    permute(st);
+    return squeeze(st);
 }
 
 // ZkScalar::new (src/zk/mod.rs:263-270) of a 32-byte little-endian integer: its residue in Montgomery form.  2^256 < 3 r, so two conditional

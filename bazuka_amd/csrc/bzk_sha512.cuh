@@ -9,8 +9,12 @@
 // A message is up to three byte ranges and an optional literal last byte, hashed in that order without a copy: Ed25519 hashes R | A | M, and
 // the signed form of a ContractDeposit is its bytes up to the Option<Signature> tag followed by a None tag (src/core/transaction.rs:192-202).
 // Bytes are fetched eight at a time where the word lies inside one range, byte by byte at range edges, the tail and the padding.
+//
+// sha512_one is a template on the message type: the same rounds absorb a gathered message (bzk_gather.cuh: up to six pieces, each a range or a
+// zero run), which is how the signed form of an L1 Transaction is hashed in place.
 #pragma once
 #include "bzk_field.cuh"
+#include "bzk_gather.cuh"
 
 namespace bzk {
 namespace sha512 {
@@ -91,6 +95,17 @@ BZK_HD uint64_t load_word(const Msg& m, uint64_t total, uint64_t pos) {
     return w;
 }
 
+BZK_HD uint64_t msg_total(const Msg& m) { return m.len[0] + m.len[1] + m.len[2] + (m.tail >= 0 ? 1 : 0); }
+
+// the same for a gathered message: its bytes read as zero past the end, so the 0x80 byte is set here
+BZK_HD uint64_t msg_total(const gather::Msg& m) { return gather::total(m); }
+BZK_HD uint64_t load_word(const gather::Msg& m, uint64_t total, uint64_t pos) {
+    uint64_t w = gather::fetch8_be(m, pos);
+    const uint64_t k = total - pos;  // wraps where pos > total
+    if (k < 8) w |= (uint64_t)0x80 << (8 * (7 - k));
+    return w;
+}
+
 #define BZK_SHA512_ROUND(a, b, c, d, e, f, g, h, i)                                                        \
     {                                                                                                      \
         if (t) w[i] += small_sigma1(w[(i + 14) & 15]) + w[(i + 9) & 15] + small_sigma0(w[(i + 1) & 15]);   \
@@ -100,10 +115,11 @@ BZK_HD uint64_t load_word(const Msg& m, uint64_t total, uint64_t pos) {
         h = t1 + t2;                                                                                       \
     }
 
-BZK_HD Digest sha512_one(const Msg& m) {
+template <class M>
+BZK_HD Digest sha512_one(const M& m) {
     uint64_t s[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
                      0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
-    const uint64_t total = m.len[0] + m.len[1] + m.len[2] + (m.tail >= 0 ? 1 : 0);
+    const uint64_t total = msg_total(m);
     const uint64_t blocks = (total + 144) / 128;  // the 0x80 byte and the 16 length bytes always fit the last block
 #pragma unroll 1
     for (uint64_t blk = 0; blk < blocks; ++blk) {

@@ -8,6 +8,7 @@
 #include "bzk_decompress.cuh"
 #include "bzk_keccak.cuh"
 #include "bzk_ed25519.cuh"
+#include "bzk_l1.cuh"
 #include <atomic>
 #include <thread>
 #include "bzk_internal.h"
@@ -166,6 +167,63 @@ __global__ void __launch_bounds__(256) mpn_deposit_verdict_kernel(const uint8_t*
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
     ok[i] = (uint8_t)((verified[i] && has_sig[i] ? 1 : 0) | (key_ok[i] ? 2 : 0));
+}
+
+// Transaction::verify_signature, one lane per record (bzk_l1.cuh verify_one): k = SHA-512(R | A | signed form) with the signed form gathered in
+// place from the uploaded record, then ed25519_verify_kernel's group equation with the same LDS columns.  Lanes whose record has no src or is
+// Unsigned take their verdict from the parse flags and leave.
+__global__ void __launch_bounds__(ED25519_BLOCK) l1_tx_verify_kernel(const uint8_t* __restrict__ data, const l1::L1Rec* __restrict__ rec, uint64_t n,
+                                                                     const uint32_t* __restrict__ base_tab, uint8_t* __restrict__ ok) {
+    __shared__ uint32_t lds[ed25519::LANE_WORDS * ED25519_BLOCK];
+    const uint64_t i = (uint64_t)blockIdx.x * ED25519_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    ok[i] = l1::verify_one(data, rec[i], base_tab, lds + threadIdx.x, ED25519_BLOCK);
+}
+// Transaction::hash, one lane per record (bzk_l1.cuh hash_one): SHA3-256 of the signed form.  A kernel of its own: Keccak's fifty state
+// registers and four waves per block are not the verifier's profile.
+__global__ void __launch_bounds__(SHA3_BLOCK) l1_tx_hash_kernel(const uint8_t* __restrict__ data, const l1::L1Rec* __restrict__ rec, uint64_t n,
+                                                                uint32_t* __restrict__ digest) {
+    const uint64_t i = (uint64_t)blockIdx.x * SHA3_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const keccak::Digest d = l1::hash_one(data, rec[i]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) digest[8 * i + k] = d.w[k];
+}
+// MerkleTree::new for the m trees of a call, whose node arrays lie one after another in `nodes` (tree[t].node_base, in nodes).
+// Leaves first: one lane per leaf, leaf_start (m + 1 entries) says which tree a lane's leaf belongs to, merkle_leaf_map where it goes.
+__global__ void __launch_bounds__(256) sha3_merkle_place_kernel(const uint32_t* __restrict__ leaves, const l1::TreeAt* __restrict__ tree,
+                                                                const uint32_t* __restrict__ leaf_start, uint32_t m, uint32_t n_leaves,
+                                                                uint32_t* __restrict__ nodes) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_leaves) return;
+    const uint32_t t = l1::tree_of(leaf_start, m, i);
+    const size_t at = (size_t)tree[t].node_base + l1::merkle_leaf_map(tree[t].len, i - leaf_start[t]);
+#pragma unroll
+    for (int w = 0; w < 8; ++w) nodes[8 * at + w] = leaves[8 * (size_t)i + w];
+}
+// Then one launch per level d, deepest first: one lane per parent over all trees (lane_start: m + 1 entries for this level; a tree shallower
+// than d contributes no lanes).  64 bytes in, one Keccak permutation (bzk_l1.cuh merkle_parent_one).
+__global__ void __launch_bounds__(SHA3_BLOCK) sha3_merkle_level_kernel(uint32_t* __restrict__ nodes, const l1::TreeAt* __restrict__ tree,
+                                                                       const uint32_t* __restrict__ lane_start, uint32_t m, uint32_t d,
+                                                                       uint32_t lanes) {
+    const uint32_t i = blockIdx.x * SHA3_BLOCK + threadIdx.x;
+    if (i >= lanes) return;
+    const uint32_t t = l1::tree_of(lane_start, m, i);
+    l1::merkle_parent_one(nodes + 8 * (size_t)tree[t].node_base, d, i - lane_start[t]);
+}
+// roots[t] = tree t's node 0; all_ok[t] (where tx_ok is given) = every record of body t verified
+__global__ void __launch_bounds__(256) sha3_merkle_roots_kernel(const uint32_t* __restrict__ nodes, const l1::TreeAt* __restrict__ tree,
+                                                                const uint32_t* __restrict__ leaf_start, const uint8_t* __restrict__ tx_ok, uint32_t m,
+                                                                uint32_t* __restrict__ roots, uint8_t* __restrict__ all_ok) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= m) return;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) roots[8 * (size_t)t + w] = nodes[8 * (size_t)tree[t].node_base + w];
+    if (tx_ok) {
+        uint8_t all = 1;
+        for (uint32_t i = leaf_start[t]; i < leaf_start[t + 1]; ++i) all &= tx_ok[i] ? 1 : 0;
+        all_ok[t] = all;
+    }
 }
 
 static int32_t eddsa_table_dev(bzk_ctx* ctx, const Fr29** out) {
@@ -459,6 +517,167 @@ static bool offsets_ok(const uint64_t* off, uint64_t n) {
     return true;
 }
 
+// ---- wire-form L1 transactions and the block root (bzk_l1.cuh) -------------------------------------------------------------------------------
+// The layout of a call's m trees: where each tree's nodes and leaves lie and, per level, which lanes are whose.  Host arithmetic only.
+struct MerklePlan {
+    std::vector<l1::TreeAt> tree;      // m
+    std::vector<uint32_t> start;       // (depth + 1) rows of m + 1: row 0 the leaves' prefix sums, row d level d's lanes'
+    uint32_t m = 0, depth = 0, n_leaves = 0, n_nodes = 0;
+    const uint32_t* row(uint32_t d) const { return start.data() + (size_t)d * (m + 1); }
+    bool build(const uint64_t* count, uint64_t trees) {
+        uint64_t leaves = 0, nodes = 0;
+        for (uint64_t t = 0; t < trees; ++t) {
+            if (count[t] >= ((uint64_t)1 << 30)) return false;
+            leaves += count[t];
+            nodes += count[t] ? 2 * count[t] - 1 : 1;
+        }
+        if (trees >= ((uint64_t)1 << 31) || nodes >= ((uint64_t)1 << 31)) return false;  // node indices are 32-bit
+        m = (uint32_t)trees; n_leaves = (uint32_t)leaves; n_nodes = (uint32_t)nodes;
+        tree.resize(m);
+        depth = 0;
+        uint32_t at = 0;
+        for (uint32_t t = 0; t < m; ++t) {
+            tree[t] = {at, count[t] ? (uint32_t)(2 * count[t] - 1) : 1u};
+            at += tree[t].len;
+            depth = std::max(depth, l1::merkle_depth(tree[t].len));
+        }
+        start.assign((size_t)(depth + 1) * (m + 1), 0);
+        for (uint32_t t = 0; t < m; ++t) {
+            start[t + 1] = start[t] + (uint32_t)count[t];
+            for (uint32_t d = 1; d <= depth; ++d) {
+                uint32_t* r = start.data() + (size_t)d * (m + 1);
+                r[t + 1] = r[t] + (d <= l1::merkle_depth(tree[t].len) ? l1::merkle_level_pairs(tree[t].len, d) : 0);
+            }
+        }
+        return true;
+    }
+};
+// leaves_dev (n_leaves x 32) -> nodes_dev (n_nodes x 32), roots_dev (m x 32) and, where tx_ok_dev is given, all_ok_dev (m); dtree / dstart: the
+// plan's two arrays on the device.  Enqueues on the context's stream.
+static int32_t merkle_enqueue(bzk_ctx* ctx, const MerklePlan& P, const void* leaves_dev, const void* tx_ok_dev, l1::TreeAt* dtree, uint32_t* dstart,
+                              void* nodes_dev, void* roots_dev, void* all_ok_dev) {
+    if (P.m == 0) return BZK_OK;
+    BZK_HIP(ctx, hipMemcpyAsync(dtree, P.tree.data(), P.tree.size() * sizeof(l1::TreeAt), hipMemcpyHostToDevice, ctx->stream));
+    BZK_HIP(ctx, hipMemcpyAsync(dstart, P.start.data(), P.start.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    BZK_HIP(ctx, hipMemsetAsync(nodes_dev, 0, (size_t)P.n_nodes * 32, ctx->stream));  // the node of a tree without leaves stays zero
+    if (P.n_leaves)
+        BZK_LAUNCH(ctx, "sha3_merkle_place", sha3_merkle_place_kernel, dim3((P.n_leaves + 255) / 256), dim3(256), 0, (const uint32_t*)leaves_dev,
+                   (const l1::TreeAt*)dtree, (const uint32_t*)dstart, P.m, P.n_leaves, (uint32_t*)nodes_dev);
+    for (uint32_t d = P.depth; d >= 1; --d) {
+        const uint32_t lanes = P.row(d)[P.m];
+        if (!lanes) continue;
+        BZK_LAUNCH(ctx, "sha3_merkle_level", sha3_merkle_level_kernel, dim3((lanes + SHA3_BLOCK - 1) / SHA3_BLOCK), dim3(SHA3_BLOCK), 0,
+                   (uint32_t*)nodes_dev, (const l1::TreeAt*)dtree, (const uint32_t*)(dstart + (size_t)d * (P.m + 1)), P.m, d, lanes);
+    }
+    BZK_LAUNCH(ctx, "sha3_merkle_roots", sha3_merkle_roots_kernel, dim3((P.m + 255) / 256), dim3(256), 0, (const uint32_t*)nodes_dev,
+               (const l1::TreeAt*)dtree, (const uint32_t*)dstart, (const uint8_t*)tx_ok_dev, P.m, (uint32_t*)roots_dev, (uint8_t*)all_ok_dev);
+    return BZK_OK;
+}
+// the same on host threads: nodes (n_nodes x 32) is the caller's
+static void merkle_host(int threads, const MerklePlan& P, const uint8_t* leaves, const uint8_t* tx_ok, uint32_t* nodes, uint8_t* roots, uint8_t* all_ok) {
+    memset(nodes, 0, (size_t)P.n_nodes * 32);
+    host_for_each(P.n_leaves, threads, [&](uint64_t i) {
+        const uint32_t t = l1::tree_of(P.row(0), P.m, (uint32_t)i);
+        memcpy(nodes + 8 * ((size_t)P.tree[t].node_base + l1::merkle_leaf_map(P.tree[t].len, (uint32_t)i - P.row(0)[t])), leaves + 32 * i, 32);
+    });
+    for (uint32_t d = P.depth; d >= 1; --d) {
+        const uint32_t* row = P.row(d);
+        host_for_each(row[P.m], threads, [&](uint64_t i) {
+            const uint32_t t = l1::tree_of(row, P.m, (uint32_t)i);
+            l1::merkle_parent_one(nodes + 8 * (size_t)P.tree[t].node_base, d, (uint32_t)i - row[t]);
+        });
+    }
+    for (uint32_t t = 0; t < P.m; ++t) {
+        memcpy(roots + 32 * (size_t)t, nodes + 8 * (size_t)P.tree[t].node_base, 32);
+        if (tx_ok) {
+            uint8_t all = 1;
+            for (uint32_t i = P.row(0)[t]; i < P.row(0)[t + 1]; ++i) all &= tx_ok[i] ? 1 : 0;
+            all_ok[t] = all;
+        }
+    }
+}
+
+int32_t l1_check_host(int threads, const L1SoA& t, uint64_t n, const uint64_t* count, uint64_t m, uint8_t* ok, uint8_t* hash_out,
+                      uint8_t* sig_ok_out, uint8_t* root_out) {
+    MerklePlan P;
+    if (count && !P.build(count, m)) return BZK_E_ARG;
+    std::vector<uint8_t> hashes, verdicts;
+    if (count && !hash_out) {
+        hashes.resize(n * 32);
+        hash_out = hashes.data();
+    }
+    if (!ok) {
+        verdicts.resize(n);
+        ok = verdicts.data();
+    }
+    const uint32_t* tab = ed25519::base_table_host();
+    host_for_each(n, threads, [&](uint64_t i) {
+        uint32_t lane[ed25519::LANE_WORDS];
+        ok[i] = l1::verify_one(t.txs + t.rec_off[i], t.rec[i], tab, lane, 1);  // rec.at is 0: the record's own first byte is the base
+        if (hash_out) {
+            const keccak::Digest d = l1::hash_one(t.txs + t.rec_off[i], t.rec[i]);
+            memcpy(hash_out + 32 * i, d.w, 32);
+        }
+    });
+    if (count && m) {
+        std::vector<uint32_t> nodes((size_t)P.n_nodes * 8);
+        merkle_host(threads, P, hash_out, ok, nodes.data(), root_out, sig_ok_out);
+    }
+    return BZK_OK;
+}
+
+// Rounds end at l1::CHUNK records or l1::CHUNK_BYTES of record bytes (a record is at most l1::RECORD_MAX bytes, so a round always holds one); a
+// round's records go up as they stand with their L1Rec, one verify launch and one hash launch per round.  Verdicts and hashes of all rounds stay
+// on the device; with count given the trees are built from them there.
+int32_t l1_check_run(bzk_ctx* ctx, const L1SoA& t, uint64_t n, const uint64_t* count, uint64_t m, uint8_t* ok, uint8_t* hash_out,
+                     uint8_t* sig_ok_out, uint8_t* root_out) {
+    if (n == 0 && (!count || m == 0)) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    MerklePlan P;
+    if (count && !P.build(count, m)) return BZK_E_ARG;
+    std::vector<uint64_t> chunk_at;
+    uint64_t cap = 0, cap_bytes = 0;
+    if (n) message_chunks(t.rec_off, n, l1::CHUNK, l1::CHUNK_BYTES, chunk_at, cap, cap_bytes);
+    else chunk_at.assign(1, 0);
+    const bool want_hash = hash_out || count;
+    WsLayout ws("l1_check_run");
+    uint8_t *dbytes, *dok, *dhash, *dnodes, *droots, *dall;
+    l1::L1Rec* drec;
+    l1::TreeAt* dtree;
+    uint32_t* dstart;
+    ws.take(dbytes, cap_bytes + 8); ws.take(drec, cap ? cap : 1); ws.take(dok, n ? n : 1); ws.take(dhash, want_hash ? n * 32 + 32 : 32);
+    ws.take(dnodes, (size_t)P.n_nodes * 32 + 32); ws.take(droots, (size_t)P.m * 32 + 32); ws.take(dall, (size_t)P.m + 1);
+    ws.take(dtree, (size_t)P.m + 1); ws.take(dstart, P.start.size() + 1);
+    BZK_TRY(ws.commit(ctx));
+    const uint32_t* tab = nullptr;
+    if (n) BZK_TRY(ed25519_table_dev(ctx, &tab));
+    std::vector<l1::L1Rec> recs(cap);
+    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {  // one stream: a round's uploads follow the previous round's kernels
+        const uint64_t off = chunk_at[c], k = chunk_at[c + 1] - off;
+        if (c) BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // recs is reused: the previous round's upload has to have left it
+        for (uint64_t i = 0; i < k; ++i) {
+            recs[i] = t.rec[off + i];
+            recs[i].at = (uint32_t)(t.rec_off[off + i] - t.rec_off[off]);
+        }
+        BZK_HIP(ctx, hipMemcpyAsync(dbytes, t.txs + t.rec_off[off], t.rec_off[off + k] - t.rec_off[off], hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(drec, recs.data(), k * sizeof(l1::L1Rec), hipMemcpyHostToDevice, ctx->stream));
+        BZK_LAUNCH(ctx, "l1_tx_verify", l1_tx_verify_kernel, dim3((unsigned)((k + ED25519_BLOCK - 1) / ED25519_BLOCK)), dim3(ED25519_BLOCK), 0,
+                   (const uint8_t*)dbytes, (const l1::L1Rec*)drec, k, tab, dok + off);
+        if (want_hash)
+            BZK_LAUNCH(ctx, "l1_tx_hash", l1_tx_hash_kernel, dim3((unsigned)((k + SHA3_BLOCK - 1) / SHA3_BLOCK)), dim3(SHA3_BLOCK), 0,
+                       (const uint8_t*)dbytes, (const l1::L1Rec*)drec, k, (uint32_t*)dhash + 8 * off);
+    }
+    if (count && m) {
+        BZK_TRY(merkle_enqueue(ctx, P, dhash, dok, dtree, dstart, dnodes, droots, dall));
+        BZK_HIP(ctx, hipMemcpyAsync(root_out, droots, (size_t)P.m * 32, hipMemcpyDeviceToHost, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(sig_ok_out, dall, P.m, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (n && ok) BZK_HIP(ctx, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (n && hash_out) BZK_HIP(ctx, hipMemcpyAsync(hash_out, dhash, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
 }  // namespace bzk
 
 using namespace bzk;
@@ -678,6 +897,57 @@ int32_t bzk_ed25519_verify_batch(bzk_ctx* ctx, const uint8_t* pk, const uint8_t*
         BZK_TRY(ed25519_verify_launch(ctx, dpk, nullptr, dsig, nullptr, ddata, doff, doff + 8, off[a], -1, m, dok));
         BZK_HIP(ctx, hipMemcpyAsync(ok + a, dok, m, hipMemcpyDeviceToHost, ctx->stream));
     }
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
+int32_t bzk_sha3_merkle_roots(bzk_ctx* ctx, const uint8_t* leaves, const uint64_t* count, uint64_t m, uint8_t* roots_out, uint8_t* nodes_out) {
+    if (m && (!count || !roots_out)) return BZK_E_ARG;
+    if (m == 0) return BZK_OK;
+    MerklePlan P;
+    if (!P.build(count, m) || (P.n_leaves && !leaves)) return BZK_E_ARG;
+    if (!ctx) {  // the same per-lane code on host threads
+        std::vector<uint32_t> own;
+        if (!nodes_out || ((uintptr_t)nodes_out & 3)) own.resize((size_t)P.n_nodes * 8);
+        uint32_t* nodes = own.empty() ? (uint32_t*)nodes_out : own.data();
+        merkle_host(host_default_threads(), P, leaves, nullptr, nodes, roots_out, nullptr);
+        if (nodes_out && !own.empty()) memcpy(nodes_out, nodes, (size_t)P.n_nodes * 32);
+        return BZK_OK;
+    }
+    (void)hipSetDevice(ctx->device);
+    WsLayout ws("bzk_sha3_merkle_roots");
+    uint8_t *dleaves, *dnodes, *droots;
+    l1::TreeAt* dtree;
+    uint32_t* dstart;
+    ws.take(dleaves, (size_t)P.n_leaves * 32 + 32); ws.take(dnodes, (size_t)P.n_nodes * 32); ws.take(droots, (size_t)P.m * 32);
+    ws.take(dtree, P.m); ws.take(dstart, P.start.size());
+    BZK_TRY(ws.commit(ctx));
+    if (P.n_leaves) BZK_HIP(ctx, hipMemcpyAsync(dleaves, leaves, (size_t)P.n_leaves * 32, hipMemcpyHostToDevice, ctx->stream));
+    BZK_TRY(merkle_enqueue(ctx, P, dleaves, nullptr, dtree, dstart, dnodes, droots, nullptr));
+    BZK_HIP(ctx, hipMemcpyAsync(roots_out, droots, (size_t)P.m * 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (nodes_out) BZK_HIP(ctx, hipMemcpyAsync(nodes_out, dnodes, (size_t)P.n_nodes * 32, hipMemcpyDeviceToHost, ctx->stream));
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+
+int32_t bzk_sha3_merkle_roots_dev(bzk_ctx* ctx, const void* leaves_dev, const void* count_dev, uint64_t m, uint64_t n_leaves, void* roots_out_dev,
+                                  void* nodes_out_dev) {
+    if (!ctx || (m && (!count_dev || !roots_out_dev)) || (n_leaves && !leaves_dev)) return BZK_E_ARG;
+    if (m == 0) return BZK_OK;
+    (void)hipSetDevice(ctx->device);
+    std::vector<uint64_t> count(m);  // the levels are laid out on the host: the counts come back first
+    BZK_HIP(ctx, hipMemcpyAsync(count.data(), count_dev, m * 8, hipMemcpyDeviceToHost, ctx->stream));
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    MerklePlan P;
+    if (!P.build(count.data(), m) || P.n_leaves != n_leaves) return BZK_E_ARG;
+    WsLayout ws("bzk_sha3_merkle_roots_dev");
+    uint8_t* dnodes;
+    l1::TreeAt* dtree;
+    uint32_t* dstart;
+    ws.take(dnodes, nodes_out_dev ? 0 : (size_t)P.n_nodes * 32); ws.take(dtree, P.m); ws.take(dstart, P.start.size());
+    BZK_TRY(ws.commit(ctx));
+    BZK_TRY(merkle_enqueue(ctx, P, leaves_dev, nullptr, dtree, dstart, nodes_out_dev ? nodes_out_dev : dnodes, roots_out_dev, nullptr));
+    // the plan's host arrays are read by the uploads just enqueued
     BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return BZK_OK;
 }

@@ -36,6 +36,7 @@
 #include <string>
 #include <vector>
 
+#include "bzk_l1.h"
 #include "host_mpn_types.h"
 
 namespace bzk {
@@ -537,6 +538,239 @@ inline ZkScalar mpn_work_commitment(const uint8_t prover_pub[32], uint64_t rewar
     w.raw(prover_pub, 32);
     w.u64(reward);
     return hash_to_scalar(w.b.data(), w.b.size());
+}
+
+// ---- L1 transactions (src/core/transaction.rs:313-363): structure only ------------------------------------------------------------------
+// parse_l1_txs cuts n consecutive bincode(Transaction) / bincode(TransactionAndDelta) records into what the device needs to hash the signed
+// form in place (bzk_l1.h L1Rec): where the key, the signature and the Signature tag lie and, for CreateContract { state: Some } /
+// UpdateContract { delta: Some }, the byte range of that option.  No hashing and no field arithmetic.  What a record's structure does not
+// show stays with the node's deserializer: canonical scalars, valid curve points inside verifying keys, the token-name regex
+// (Token::validate), ZkStateModel::is_valid.  That is why the model and the pairs are walked here and not by state.hip's readers, which
+// apply the limits of is_valid and of a locator's length on top of bincode's rules.
+//
+//   Transaction        { src: Option<S::Pub>, nonce u32, data: TransactionData, fee: Money, memo: String, sig: Signature<S> }    :349-357
+//   TransactionAndDelta{ tx, state_delta: Option<ZkDeltaPairs> }                                                                 :359-363
+//   TransactionData    enum { UpdateStaker 0, Delegate 1, Undelegate 2, AutoDelegate 3, RegularSend 4, CreateContract 5, UpdateContract 6 }
+//   Signature<S>       enum { Unsigned = 0, Signed(S::Sig) = 1 }                                                  src/core/address.rs:34-37
+//   ContractUpdate     { circuit_id u32, data: ContractUpdateData, next_state: ZkCompressedState, prover, reward: Amount, proof: ZkProof }
+//   ContractUpdateData enum { Deposit { Vec<ContractDeposit> } 0, Withdraw { Vec<ContractWithdraw> } 1, FunctionCall { fee } 2, Mint { amount } 3 }
+//   ZkContract         { initial_state, state_model, deposit_functions, withdraw_functions: Vec<ZkMultiInputVerifierKey { vk, u8 }>,
+//                        functions: Vec<ZkSingleInputVerifierKey { vk }>, token: Option<ZkTokenContract { Token, Vec<Single..> }> }  src/zk/mod.rs:573-644
+//   Token              { name, symbol: String, supply: Amount, decimals u8, minter: Option<S::Pub> }                             :254-261
+//   ZkDataPairs / ZkDeltaPairs  HashMap<ZkDataLocator(Vec<u64>), ZkScalar / Option<ZkScalar>>                       src/zk/mod.rs:427, 471-474
+//
+// `V::Pub` of UpdateStaker is schnorrkel's PublicKey; the crate is not vendored [recalled]: under bincode it is a length-prefixed byte string
+// of 32, as ed25519_dalek::PublicKey is.
+inline bool rd_option_tag(BinReader& r, const char* what) {
+    const uint8_t tag = r.u8(what);
+    if (r.ok && tag > 1) r.fail(what);
+    return r.ok && tag == 1;
+}
+inline void skip_vrf_pub(BinReader& r) {  // schnorrkel::PublicKey [recalled]
+    if (r.u64("vrf public key length") != 32) r.fail("vrf public key length");
+    r.bytes(32, "vrf public key");
+}
+inline void skip_compressed_state(BinReader& r) {
+    r.bytes(32, "ZkCompressedState.state_hash");
+    r.u64("ZkCompressedState.state_size");
+}
+inline void skip_state_model(BinReader& r, int depth = 0) {  // enum { Scalar 0, Struct { Vec } 1, List { u8, Box } 2 }
+    if (depth > 256) { r.fail("ZkStateModel nested deeper than 256"); return; }  // bounds the recursion, not the reference's rule
+    const uint32_t tag = r.u32("ZkStateModel tag");
+    if (!r.ok || tag == 0) return;
+    if (tag == 1) {
+        const uint64_t k = r.len(4, "ZkStateModel::Struct fields");
+        for (uint64_t i = 0; i < k && r.ok; ++i) skip_state_model(r, depth + 1);
+    } else if (tag == 2) {
+        r.u8("ZkStateModel::List log4_size");
+        skip_state_model(r, depth + 1);
+    } else {
+        r.fail("ZkStateModel variant");
+    }
+}
+inline void skip_locator(BinReader& r) {
+    const uint64_t k = r.len(8, "ZkDataLocator length");
+    r.bytes((size_t)k * 8, "ZkDataLocator");
+}
+inline void skip_data_pairs(BinReader& r) {
+    const uint64_t k = r.len(40, "ZkDataPairs length");
+    for (uint64_t i = 0; i < k && r.ok; ++i) {
+        skip_locator(r);
+        r.bytes(32, "ZkDataPairs value");
+    }
+}
+inline void skip_delta_pairs(BinReader& r) {
+    const uint64_t k = r.len(9, "ZkDeltaPairs length");
+    for (uint64_t i = 0; i < k && r.ok; ++i) {
+        skip_locator(r);
+        if (rd_option_tag(r, "ZkDeltaPairs Option tag")) r.bytes(32, "ZkDeltaPairs value");
+    }
+}
+inline void skip_contract_withdraw(BinReader& r) {  // rd_contract_withdraw without its fingerprint: nothing is hashed here
+    skip_string(r);
+    rd_contract_id(r);
+    r.u32("withdraw_circuit_id");
+    r.bytes(32, "calldata");
+    skip_l1_pub(r);
+    rd_money(r);
+    rd_money(r);
+}
+inline void skip_zk_proof(BinReader& r) {  // ZkProof::Groth16(Box<Groth16Proof { a: G1, b: G2, c: G1 }>): u32 0 + 97 + 193 + 97 bytes
+    if (r.u32("ZkProof tag") != 0) r.fail("ZkProof variant (only Groth16 = 0 exists outside cfg(test))");
+    r.bytes(387, "Groth16Proof");
+}
+inline void skip_single_vks(BinReader& r, const char* what) {
+    const uint64_t k = r.len(882, what);
+    for (uint64_t i = 0; i < k && r.ok; ++i) rd_verifier_key(r);
+}
+inline void skip_multi_vks(BinReader& r, const char* what) {
+    const uint64_t k = r.len(883, what);
+    for (uint64_t i = 0; i < k && r.ok; ++i) {
+        rd_verifier_key(r);
+        r.u8("log4_payment_capacity");
+    }
+}
+inline void skip_zk_contract(BinReader& r) {
+    skip_compressed_state(r);
+    skip_state_model(r);
+    skip_multi_vks(r, "ZkContract.deposit_functions");
+    skip_multi_vks(r, "ZkContract.withdraw_functions");
+    skip_single_vks(r, "ZkContract.functions");
+    if (rd_option_tag(r, "Option<ZkTokenContract> tag")) {
+        skip_string(r);  // Token.name
+        skip_string(r);  // Token.symbol
+        r.u64("Token.supply");
+        r.u8("Token.decimals");
+        if (rd_option_tag(r, "Option<minter> tag")) skip_l1_pub(r);
+        skip_single_vks(r, "ZkTokenContract.mint_functions");
+    }
+}
+inline void skip_contract_update(BinReader& r, uint32_t flags) {
+    r.u32("ContractUpdate.circuit_id");
+    const uint32_t tag = r.u32("ContractUpdateData tag");
+    if (!r.ok) return;
+    if (tag == 0) {
+        const uint64_t k = r.len(117, "ContractUpdateData::Deposit length");
+        DepositTx scratch;
+        for (uint64_t i = 0; i < k && r.ok; ++i) rd_contract_deposit(r, flags, scratch);
+    } else if (tag == 1) {
+        const uint64_t k = r.len(112, "ContractUpdateData::Withdraw length");
+        for (uint64_t i = 0; i < k && r.ok; ++i) skip_contract_withdraw(r);
+    } else if (tag == 2) {
+        rd_money(r);
+    } else if (tag == 3) {
+        r.u64("Mint.amount");
+    } else {
+        r.fail("ContractUpdateData variant");
+    }
+    skip_compressed_state(r);
+    skip_l1_pub(r);
+    r.u64("ContractUpdate.reward");
+    skip_zk_proof(r);
+}
+// an Option in the middle of the record that the signature leaves out: [cut_a, cut_b) where it is Some, empty otherwise
+template <class Skip>
+inline void rd_cut_option(BinReader& r, size_t p0, l1::L1Rec& o, const char* what, Skip skip) {
+    const size_t at = r.pos;
+    if (!rd_option_tag(r, what)) return;
+    skip(r);
+    if (r.ok) {
+        o.cut_a = (uint32_t)(at - p0);
+        o.cut_b = (uint32_t)(r.pos - p0);
+    }
+}
+inline void rd_l1_tx(BinReader& r, uint32_t flags, bool and_delta, l1::L1Rec& o) {
+    const size_t p0 = r.pos;
+    o = l1::L1Rec();
+    if (rd_option_tag(r, "Option<src> tag")) {
+        if (r.u64("ed25519 public key length") != 32) r.fail("ed25519 public key length");
+        o.key_off = (uint32_t)(r.pos - p0);
+        r.bytes(32, "ed25519 public key");
+        o.flags |= l1::HAS_SRC;
+    }
+    r.u32("nonce");
+    const uint32_t tag = r.u32("TransactionData tag");
+    if (!r.ok) return;
+    switch (tag) {
+    case 0:  // UpdateStaker { vrf_pub_key, commission: Ratio }
+        skip_vrf_pub(r);
+        r.u8("commission");
+        break;
+    case 1:  // Delegate { amount, to }
+    case 2:  // Undelegate { amount, from }
+        r.u64("Amount");
+        skip_l1_pub(r);
+        break;
+    case 3:  // AutoDelegate { to, ratio }
+        skip_l1_pub(r);
+        r.u8("ratio");
+        break;
+    case 4: {  // RegularSend { entries: Vec<{ dst, amount: Money }> }
+        const uint64_t k = r.len(52, "RegularSend entries");
+        for (uint64_t i = 0; i < k && r.ok; ++i) {
+            skip_l1_pub(r);
+            rd_money(r);
+        }
+        break;
+    }
+    case 5:  // CreateContract { contract, money, state: Option<ZkDataPairs> }
+        skip_zk_contract(r);
+        rd_money(r);
+        rd_cut_option(r, p0, o, "Option<ZkDataPairs> tag", skip_data_pairs);
+        break;
+    case 6: {  // UpdateContract { contract_id, updates, delta: Option<ZkDeltaPairs> }
+        rd_contract_id(r);
+        const uint64_t k = r.len(495, "UpdateContract updates");
+        for (uint64_t i = 0; i < k && r.ok; ++i) skip_contract_update(r, flags);
+        rd_cut_option(r, p0, o, "Option<ZkDeltaPairs> tag", skip_delta_pairs);
+        break;
+    }
+    default:
+        r.fail("TransactionData variant");
+    }
+    rd_money(r);     // fee
+    skip_string(r);  // memo
+    o.sig_tag = (uint32_t)(r.pos - p0);
+    o.sig_tagv = r.u32("Signature tag");
+    if (r.ok && o.sig_tagv > 1) r.fail("Signature variant");
+    if (r.ok && o.sig_tagv == 1) {
+        if (flags & BZK_WORK_SIG_LEN_PREFIXED)
+            if (r.u64("ed25519 signature length") != 64) r.fail("ed25519 signature length");
+        o.sig_off = (uint32_t)(r.pos - p0);
+        r.bytes(64, "ed25519 signature");
+        o.flags |= l1::SIGNED;
+    }
+    if (and_delta && rd_option_tag(r, "Option<state_delta> tag")) skip_delta_pairs(r);
+    if (r.ok && r.pos - p0 > l1::RECORD_MAX) r.fail("record longer than 1048576 bytes");
+}
+struct L1Parsed {
+    const uint8_t* txs = nullptr;
+    std::vector<uint64_t> rec_off;  // n + 1
+    std::vector<l1::L1Rec> rec;     // n
+    L1SoA soa() const { return {txs, rec_off.data(), rec.data()}; }
+};
+// and_delta: the records are TransactionAndDelta.  false with err naming the record when the bytes are not n well-formed records
+inline bool parse_l1_txs(const uint8_t* txs, uint64_t len, uint64_t n, bool and_delta, uint32_t flags, L1Parsed& P, std::string& err) {
+    if (n > len / 29) {  // the shortest record: 1 + 4 + (4 + 8) + 4 + 8 + 4, and a TransactionAndDelta's tag
+        err = "record " + std::to_string(len / 29) + ": the input ends before it (" + std::to_string(n) + " Transaction records need 29 bytes each)";
+        return false;
+    }
+    P.txs = txs;
+    P.rec_off.resize(n + 1);
+    P.rec.resize(n);
+    BinReader r(txs, (size_t)len);
+    for (uint64_t i = 0; i < n && r.ok; ++i) {
+        P.rec_off[i] = r.pos;
+        rd_l1_tx(r, flags, and_delta, P.rec[i]);
+        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
+    }
+    if (r.ok) P.rec_off[n] = r.pos;
+    if (r.ok && r.pos != len) {
+        r.fail("bytes after the last record");
+        if (n) r.err = "record " + std::to_string(n - 1) + ": " + r.err;
+    }
+    err = r.err;
+    return r.ok;
 }
 
 }  // namespace bzk

@@ -2898,3 +2898,45 @@ int32_t bzk_mpn_push_deposits(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Wire-form L1 transactions: bincode(Transaction) / bincode(TransactionAndDelta) records in, verify_signature verdicts and Transaction::hash out
+// (bzk_l1_tx_verify_batch); whole block bodies in, per-block verdict and Merkle root out (bzk_block_bodies_check).  The parser is
+// host_bincode.h's parse_l1_txs (structure only); hashing, Ed25519 and the trees are eddsa.hip's, on the device or on host threads.
+// ------------------------------------------------------------------------------------------------
+extern "C" {
+
+int32_t bzk_l1_tx_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, uint8_t* ok, uint8_t* hash_out) {
+    if (form > BZK_L1_FORM_TX_AND_DELTA || (n && (!txs || !ok))) return BZK_E_ARG;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        L1Parsed P;
+        if (!parse_l1_txs(txs, len, n, form == BZK_L1_FORM_TX_AND_DELTA, g_wire_flags.load(), P, g_work_error)) return BZK_E_ARG;
+        if (ctx) return l1_check_run(ctx, P.soa(), n, nullptr, 0, ok, hash_out, nullptr, nullptr);
+        return l1_check_host(host_default_threads(), P.soa(), n, nullptr, 0, ok, hash_out, nullptr, nullptr);
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+int32_t bzk_block_bodies_check(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, const uint64_t* count, uint64_t m, uint8_t* sig_ok_out,
+                               uint8_t* root_out, uint8_t* tx_ok_out, uint8_t* hash_out) {
+    if (m && (!count || !sig_ok_out || !root_out)) return BZK_E_ARG;
+    if (m == 0 && len == 0) return BZK_OK;
+    uint64_t n = 0;
+    for (uint64_t j = 0; j < m; ++j) {
+        if (count[j] > len) return BZK_E_ARG;  // a record is tens of bytes: also keeps the sum from wrapping
+        n += count[j];
+    }
+    if (n && !txs) return BZK_E_ARG;
+    try {
+        L1Parsed P;
+        if (!parse_l1_txs(txs, len, n, false, g_wire_flags.load(), P, g_work_error)) return BZK_E_ARG;
+        if (ctx) return l1_check_run(ctx, P.soa(), n, count, m, tx_ok_out, hash_out, sig_ok_out, root_out);
+        return l1_check_host(host_default_threads(), P.soa(), n, count, m, tx_ok_out, hash_out, sig_ok_out, root_out);
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+}  // extern "C"

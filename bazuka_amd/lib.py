@@ -13,6 +13,8 @@ BZK_F_DEDUP = 2
 BZK_F_THROUGHPUT = 4
 BZK_SYNTH_DEFER = 2        # bzk_mpn_work_synthesize's record_matrices: the hash-dependent values left to the device
 BZK_SYNTH_DEFER_SIG = 4    # ... and the EdDSA gadget's ladders
+L1_FORM_TX = 0             # bzk_l1_tx_verify_batch: the records are bincode(Transaction)
+L1_FORM_TX_AND_DELTA = 1   # ... bincode(TransactionAndDelta)
 
 
 def _flags(canonical=False, dedup=False, throughput=False) -> int:
@@ -59,6 +61,10 @@ SIGNATURES = {
     "bzk_ed25519_verify_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_mpn_deposit_verify_batch": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "bzk_mpn_set_wire_flags": (_i32, [C.c_uint32]),
+    "bzk_l1_tx_verify_batch": (_i32, [_vp, _vp, _u64, _u64, C.c_uint32, _vp, _vp]),
+    "bzk_sha3_merkle_roots": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_sha3_merkle_roots_dev": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "bzk_block_bodies_check": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "bzk_merkle4_root": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_merkle4_root_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_state_compress": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
@@ -424,6 +430,26 @@ class Bzk:
         """n consecutive bincode(MpnDeposit): (verdict bytes: bit 0 the payment's Ed25519 signature, bit 1 the address decompresses; addresses
         n x 64 or None); a malformed record raises"""
         return _mpn_deposit_verify_batch(self.h, txs, n, want_address)
+
+    def l1_tx_verify_batch(self, txs: bytes, n: int, form: int = L1_FORM_TX, want_hash: bool = True):
+        """n consecutive bincode(Transaction) (form L1_FORM_TX) or bincode(TransactionAndDelta) (L1_FORM_TX_AND_DELTA): (verdict bytes of
+        Transaction::verify_signature, Transaction::hash n x 32 or None); a malformed record raises"""
+        return _l1_tx_verify_batch(self.h, txs, n, form, want_hash)
+
+    def sha3_merkle_roots(self, leaves: bytes, counts, want_nodes: bool = False):
+        """MerkleTree::<Sha3Hasher>::new for len(counts) trees whose 32-byte leaves lie one tree after another in leaves: roots m x 32, or
+        (roots, all node arrays in heap order) with want_nodes"""
+        return _sha3_merkle_roots(self.h, leaves, counts, want_nodes)
+
+    def sha3_merkle_roots_dev(self, leaves, count, m: int, n_leaves: int, roots, nodes=None):
+        """device buffers: leaves n_leaves x 32, count m u64; roots m x 32 and (optionally) nodes are written on the context's stream"""
+        self._ck(self.lib.bzk_sha3_merkle_roots_dev(self.h, _ptr(leaves), _ptr(count), m, n_leaves, _ptr(roots), _ptr(nodes)),
+                 "sha3_merkle_roots_dev")
+
+    def block_bodies_check(self, txs: bytes, counts, want_tx: bool = True):
+        """the bodies of len(counts) blocks as bincode(Transaction) back to back, counts[j] per block: (sig_ok m bytes, roots m x 32, tx_ok n
+        bytes or None, hashes n x 32 or None); a malformed record raises"""
+        return _block_bodies_check(self.h, txs, counts, want_tx)
 
     def merkle4_root(self, leaves: bytes, log4: int, want_nodes: bool = False):
         root = C.create_string_buffer(32)
@@ -1503,3 +1529,54 @@ def host_mpn_deposit_verify_batch(txs: bytes, n: int, want_address: bool = True)
 def mpn_set_wire_flags(flags: int):
     """process-wide: WORK_SIG_LEN_PREFIXED where wire-form deposits carry length-prefixed Ed25519 signatures (ed25519 < 1.3), else 0"""
     _st(load_library().bzk_mpn_set_wire_flags(flags), "mpn_set_wire_flags")
+
+
+def _l1_tx_verify_batch(ctx_handle, txs: bytes, n: int, form: int, want_hash: bool):
+    lib = load_library()
+    ok = C.create_string_buffer(max(n, 1))
+    h = C.create_string_buffer(max(32 * n, 1)) if want_hash else None
+    st = lib.bzk_l1_tx_verify_batch(ctx_handle, _ptr(txs) if txs else None, len(txs), n, form, ok, h)
+    if st != 0:
+        raise BzkError(f"l1_tx_verify_batch: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+    return ok.raw[:n], (h.raw[: 32 * n] if want_hash else None)
+
+
+def host_l1_tx_verify_batch(txs: bytes, n: int, form: int = L1_FORM_TX, want_hash: bool = True):
+    """Bzk.l1_tx_verify_batch without a device: the same per-lane code on host threads"""
+    return _l1_tx_verify_batch(None, txs, n, form, want_hash)
+
+
+def _sha3_merkle_roots(ctx_handle, leaves: bytes, counts, want_nodes: bool):
+    m = len(counts)
+    if len(leaves) != 32 * sum(counts):
+        raise BzkError("sha3_merkle_roots: leaves must hold 32 bytes per counted leaf")
+    cnt = (C.c_uint64 * max(m, 1))(*counts)
+    n_nodes = sum(max(1, 2 * c - 1) for c in counts)
+    roots = C.create_string_buffer(max(32 * m, 1))
+    nodes = C.create_string_buffer(max(32 * n_nodes, 1)) if want_nodes else None
+    _st(load_library().bzk_sha3_merkle_roots(ctx_handle, _ptr(leaves) if leaves else None, cnt, m, roots, nodes), "sha3_merkle_roots")
+    return (roots.raw[: 32 * m], nodes.raw[: 32 * n_nodes]) if want_nodes else roots.raw[: 32 * m]
+
+
+def host_sha3_merkle_roots(leaves: bytes, counts, want_nodes: bool = False):
+    """Bzk.sha3_merkle_roots without a device"""
+    return _sha3_merkle_roots(None, leaves, counts, want_nodes)
+
+
+def _block_bodies_check(ctx_handle, txs: bytes, counts, want_tx: bool):
+    lib = load_library()
+    m, n = len(counts), sum(counts)
+    cnt = (C.c_uint64 * max(m, 1))(*counts)
+    sig_ok = C.create_string_buffer(max(m, 1))
+    roots = C.create_string_buffer(max(32 * m, 1))
+    tx_ok = C.create_string_buffer(max(n, 1)) if want_tx else None
+    h = C.create_string_buffer(max(32 * n, 1)) if want_tx else None
+    st = lib.bzk_block_bodies_check(ctx_handle, _ptr(txs) if txs else None, len(txs), cnt, m, sig_ok, roots, tx_ok, h)
+    if st != 0:
+        raise BzkError(f"block_bodies_check: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+    return sig_ok.raw[:m], roots.raw[: 32 * m], (tx_ok.raw[:n] if want_tx else None), (h.raw[: 32 * n] if want_tx else None)
+
+
+def host_block_bodies_check(txs: bytes, counts, want_tx: bool = True):
+    """Bzk.block_bodies_check without a device"""
+    return _block_bodies_check(None, txs, counts, want_tx)

@@ -180,6 +180,37 @@ int32_t bzk_mpn_deposit_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t 
  * bzk_mpn_deposit_verify_batch and bzk_mpn_push_deposits; pass the same flags to bzk_mpn_work_decode for works made from such deposits. */
 int32_t bzk_mpn_set_wire_flags(uint32_t flags);
 
+/* ---- wire-form L1 transactions: signature, hash and block root -------------------------------------------------
+ * The fourth arm of GeneralTransaction::verify_signature (src/core/mod.rs:163-170) and the cryptographic part of apply_block's body checks.
+ * The signed bytes of a Transaction are bincode(tx.sig_state_excluded()) (src/core/transaction.rs:369-397): the record with Signature::Unsigned
+ * for its signature and, for CreateContract { state } / UpdateContract { delta }, None for that option.  The host parses the records' structure
+ * only (all seven TransactionData variants) and the device hashes that form in place from the uploaded record, as a list of ranges and zero runs.
+ * Canonical scalars, valid curve points inside verifying keys and the token-name rules stay with the node's deserializer; nonce, balance and fee
+ * rules with its state machine. */
+#define BZK_L1_FORM_TX            0   /* n consecutive bincode(Transaction): a block body's elements        */
+#define BZK_L1_FORM_TX_AND_DELTA  1   /* n consecutive bincode(TransactionAndDelta): what the mempool gets  */
+/* Transaction::verify_signature (transaction.rs:386-397) and Transaction::hash (:383-385).  ok[i] = 1 / 0 (src None: 1; Unsigned: 0);
+ * hash_out n x 32, may be NULL.  ctx = NULL: the same per-lane code on host threads.  Ed25519 semantics are bzk_ed25519_verify_batch's.
+ * BZK_E_ARG with bzk_mpn_work_last_error() naming the record when the bytes are not n well-formed records (truncation, trailing bytes, an enum
+ * or Option tag out of range, a length past the record, a key / signature length other than 32 / 64) or a record is longer than 2^20 bytes
+ * (max_block_size, src/config/blockchain.rs:337); nothing is written then.  Signatures are read as bzk_mpn_set_wire_flags says.  n = 0 is a
+ * no-op.  One lane per record; rounds end at 2^16 records or 64 MiB of record bytes; synchronises. */
+int32_t bzk_l1_tx_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, uint8_t* ok, uint8_t* hash_out);
+/* MerkleTree::<Sha3Hasher>::new (src/crypto/merkle.rs) for m trees: tree j has count[j] leaves of 32 bytes, consecutive in leaves.  roots_out
+ * m x 32 (no leaves: 32 zero bytes; one leaf: the leaf); nodes_out (may be NULL) receives each tree's whole node array in the reference's heap
+ * order (MerkleTree.data), tree after tree (max(1, 2 count[j] - 1) nodes each).  One launch per level covers all trees.  m = 0 is a no-op;
+ * ctx = NULL (host form): the same per-lane code on host threads.  The _dev form takes device pointers (n_leaves = the sum of count) and
+ * works on the context's stream; the levels are laid out on the host, so it reads count_dev back (m x 8 bytes) first and synchronises. */
+int32_t bzk_sha3_merkle_roots(bzk_ctx* ctx, const uint8_t* leaves, const uint64_t* count, uint64_t m, uint8_t* roots_out, uint8_t* nodes_out);
+int32_t bzk_sha3_merkle_roots_dev(bzk_ctx* ctx, const void* leaves_dev, const void* count_dev, uint64_t m, uint64_t n_leaves, void* roots_out_dev,
+                                  void* nodes_out_dev);
+/* The body checks of apply_block (src/blockchain/ops/apply_block.rs:47 and :88) for m blocks at once: txs = all bodies' bincode(Transaction)
+ * back to back, count[j] per block.  sig_ok_out[j] = every transaction of block j verifies (an empty body: 1); root_out[j] = block j's
+ * merkle_tree().root() (src/core/blocks.rs:17-19), to be compared with header.block_root by the caller; tx_ok_out (n bytes) and hash_out
+ * (n x 32) may be NULL.  Hashes and trees stay on the device between the two steps.  Refusals as bzk_l1_tx_verify_batch; ctx = NULL as there. */
+int32_t bzk_block_bodies_check(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, const uint64_t* count, uint64_t m, uint8_t* sig_ok_out,
+                               uint8_t* root_out, uint8_t* tx_ok_out, uint8_t* hash_out);
+
 /* ---- K2: dense 4-ary ZkState tree re-hash ----------------------------------------------------
  * Root of `ZkStateModel::List{log4_size, Scalar}` with every leaf present, as
  * `ZkStateBuilder::compress` / `KvStoreStateManager::root` would give (src/zk/state/mod.rs:66-90,

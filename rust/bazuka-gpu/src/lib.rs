@@ -16,6 +16,10 @@
 //!                                once, and whether each `mpn_address` decompresses
 //!   * `Gpu::ed25519_verify_batch` - `Ed25519::verify` (src/crypto/ed25519.rs:81-83) for many (key, message, signature) at once
 //!   * `Gpu::sha512_batch`      - SHA-512 of many messages at once
+//!   * `Gpu::l1_tx_verify_batch` - `Transaction::verify_signature` and `Transaction::hash` (src/core/transaction.rs:383-397) for many L1
+//!                                transactions at once, the signed form hashed in place on the device
+//!   * `Gpu::sha3_merkle_root`  - `MerkleTree::<Sha3Hasher>::new(leaves).root()` (src/crypto/merkle.rs)
+//!   * `Gpu::block_bodies_check` - the body checks of src/blockchain/ops/apply_block.rs:47 and :88 for many blocks in one call
 //!   * `groth16_prove`          - beside `groth16_verify` (src/zk/groth16/mod.rs:67-75), same argument order
 //!   * `compress`               - `ZkStateModel::compress::<H>(&data)` (src/zk/mod.rs:392-399)
 //!   * `DeviceStateManager`     - `KvStoreStateManager::{update_contract, root, get_data, prove}` (src/zk/state/mod.rs:218-438) for one
@@ -31,7 +35,7 @@
 //!
 //! Layout assumptions (already relied upon by the reference's own `transmute`s, src/zk/groth16/mod.rs:7-17): `ZkScalar` is
 //! `[u64; 4]` little-endian Montgomery limbs; bincode 1.3 with default options; `Groth16Proof` = 97 + 193 + 97 bytes under bincode.
-use bazuka::core::{Address, MpnDeposit, MpnWithdraw};
+use bazuka::core::{Address, Block, MpnDeposit, MpnWithdraw, Transaction};
 use bazuka::crypto::jubjub::{PublicKey, Signature};
 use bazuka::mpn::MpnWork;
 use bazuka::zk::groth16::Groth16Proof;
@@ -179,6 +183,61 @@ impl Gpu {
         }
         check(self.0, st)?;
         Ok(ok.into_iter().map(|b| (b & 1 != 0, b & 2 != 0)).collect())
+    }
+
+    /// Bulk `tx.verify_signature()` and `tx.hash()` (src/core/transaction.rs:383-397): the fourth arm of
+    /// `GeneralTransaction::verify_signature` (src/core/mod.rs:163-170).  The transactions travel as bincode; the device hashes
+    /// `bincode(tx.sig_state_excluded())` in place from each record.  `(verified, hash)` per transaction.
+    pub fn l1_tx_verify_batch(&self, txs: &[Transaction]) -> Result<Vec<(bool, [u8; 32])>, GpuError> {
+        let mut bytes = Vec::new();
+        for tx in txs {
+            bytes.extend_from_slice(&bincode::serialize(tx)?);
+        }
+        let (mut ok, mut hash) = (vec![0u8; txs.len()], vec![0u8; 32 * txs.len()]);
+        let form = 0u32; // BZK_L1_FORM_TX: the records are bincode(Transaction)
+        let st =
+            unsafe { sys::bzk_l1_tx_verify_batch(self.0, bytes.as_ptr(), bytes.len() as u64, txs.len() as u64, form, ok.as_mut_ptr(), hash.as_mut_ptr()) };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(self.0, st)?;
+        Ok(ok.iter().zip(hash.chunks_exact(32)).map(|(b, h)| (*b != 0, h.try_into().unwrap())).collect())
+    }
+
+    /// `MerkleTree::<Sha3Hasher>::new(leaves.to_vec()).root()` (src/crypto/merkle.rs:79-108).  One small tree is a chain of dependent launches:
+    /// the value is in `block_bodies_check`, which builds many blocks' trees level by level together.
+    pub fn sha3_merkle_root(&self, leaves: &[[u8; 32]]) -> Result<[u8; 32], GpuError> {
+        let count = [leaves.len() as u64];
+        let mut root = [0u8; 32];
+        check(self.0, unsafe {
+            sys::bzk_sha3_merkle_roots(self.0, leaves.as_ptr() as *const u8, count.as_ptr(), 1, root.as_mut_ptr(), ptr::null_mut())
+        })?;
+        Ok(root)
+    }
+
+    /// The cryptographic part of validating block bodies (src/blockchain/ops/apply_block.rs:47 and :88) for many fetched blocks in one call:
+    /// per block, whether every transaction's signature verifies and `block.merkle_tree().root()`, which the caller compares with
+    /// `block.header.block_root`.
+    pub fn block_bodies_check(&self, blocks: &[Block]) -> Result<Vec<(bool, [u8; 32])>, GpuError> {
+        let (mut bytes, mut count) = (Vec::new(), Vec::with_capacity(blocks.len()));
+        for b in blocks {
+            for tx in &b.body {
+                bytes.extend_from_slice(&bincode::serialize(tx)?);
+            }
+            count.push(b.body.len() as u64);
+        }
+        let (mut ok, mut roots) = (vec![0u8; blocks.len()], vec![0u8; 32 * blocks.len()]);
+        let st = unsafe {
+            sys::bzk_block_bodies_check(self.0, bytes.as_ptr(), bytes.len() as u64, count.as_ptr(), blocks.len() as u64, ok.as_mut_ptr(),
+                                        roots.as_mut_ptr(), ptr::null_mut(), ptr::null_mut())
+        };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(self.0, st)?;
+        Ok(ok.iter().zip(roots.chunks_exact(32)).map(|(b, r)| (*b != 0, r.try_into().unwrap())).collect())
     }
 
     /// Bulk `Ed25519::verify(pk, msg, sig)` (src/crypto/ed25519.rs:81-83: ed25519-dalek 1 `PublicKey::verify`, the non-strict verifier) over raw

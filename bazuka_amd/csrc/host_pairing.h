@@ -14,78 +14,85 @@
 //            yardstick of the tests, which check fast == plain^3 on Miller outputs.
 // Cost on one core of the build container (Xeon @ 2.1 GHz, -O3): the four-pair check of a Groth16 verification ~2.2 ms (Miller loop ~1.5, final
 // exponentiation ~0.6) of the verifier's 2.8 ms; the first version spent 6.8 ms on line inversions and 11 ms on the plain exponentiation.
+// Those figures were taken when the tower was plain value code in this file; multi_miller and final_exp now run the shared slot functions of
+// bzk_pairing28.cuh on a local slab and have not been re-timed piece by piece (the flagship benchmark, which ends in this verifier, is unchanged).
 #pragma once
+#include <vector>
+
 #include "host_fp64.h"
+#include "bzk_pairing28.cuh"
 
 namespace bzk {
+namespace pairing {
+template <> struct FieldIn<HFpOps> {
+    static HFp load(const uint8_t* b) { HFp r; memcpy(r.l, b, 48); return r; }   // same Montgomery value, same little-endian bytes
+};
+}  // namespace pairing
 namespace hp {
 
+// The tower itself is bzk_pairing28.cuh, generic over the field: Fp2 / Fp6 on values (TW), Fp12 on the slots of a slab.  The functions below are
+// its instantiation over the host field with the value signatures the verifier and the CPU harness use: an Fp12 function copies its operands
+// into a local slab, runs the slot function and copies the result out.  Those copies are for the harness's piecewise checks only: the loops that
+// matter, multi_miller and final_exp, keep their accumulator in one slab from start to end.
 typedef HFpOps F1;
 typedef HFp2Ops F2;
 typedef HFp2 E2;
-struct E6 { E2 c0, c1, c2; };
-struct E12 { E6 a0, a1; };
+typedef pairing::Tower<HFpOps, HFp2Ops> TW;
+typedef TW::E6 E6;
+typedef TW::E12 E12;
+struct LaneH {   // the host lane: slot i is s[i]
+    typedef HFpOps F1;
+    typedef HFp2Ops F2;
+    HFp* s;
+    HFp ld1(int i) const { return s[i]; }
+    void st1(int i, const HFp& v) const { s[i] = v; }
+};
+static_assert(sizeof(E12) == 12 * sizeof(HFp), "an Fp12 value is twelve slots in tower order");
+inline void put12(HFp* s, int at, const E12& a) { memcpy(s + at, &a, sizeof a); }
+inline E12 get12(const HFp* s, int at) { E12 r; memcpy(&r, s + at, sizeof r); return r; }
 
 inline HFp to_h(const Fp& a) { HFp r; memcpy(r.l, a.l, 48); return r; }          // same Montgomery value, same little-endian bytes
 inline E2 to_h(const Fp2& a) { return {to_h(a.c0), to_h(a.c1)}; }
 
-inline E2 e2_mul_xi(const E2& a) { return {F1::sub(a.c0, a.c1), F1::add(a.c0, a.c1)}; }  // * (1 + u)
-inline E2 e2_scale(const E2& a, const HFp& k) { return {F1::mul(a.c0, k), F1::mul(a.c1, k)}; }
-inline E2 e2_conj(const E2& a) { return {a.c0, F1::neg(a.c1)}; }
-inline E6 e6_zero() { return {F2::zero(), F2::zero(), F2::zero()}; }
-inline E6 e6_one() { return {F2::one(), F2::zero(), F2::zero()}; }
-inline E6 e6_add(const E6& a, const E6& b) { return {F2::add(a.c0, b.c0), F2::add(a.c1, b.c1), F2::add(a.c2, b.c2)}; }
-inline E6 e6_sub(const E6& a, const E6& b) { return {F2::sub(a.c0, b.c0), F2::sub(a.c1, b.c1), F2::sub(a.c2, b.c2)}; }
-inline E6 e6_neg(const E6& a) { return {F2::neg(a.c0), F2::neg(a.c1), F2::neg(a.c2)}; }
-inline E6 e6_mul(const E6& a, const E6& b) {  // Karatsuba: 6 Fp2 products
-    const E2 t0 = F2::mul(a.c0, b.c0), t1 = F2::mul(a.c1, b.c1), t2 = F2::mul(a.c2, b.c2);
-    E6 r;
-    r.c0 = F2::add(t0, e2_mul_xi(F2::sub(F2::sub(F2::mul(F2::add(a.c1, a.c2), F2::add(b.c1, b.c2)), t1), t2)));
-    r.c1 = F2::add(F2::sub(F2::sub(F2::mul(F2::add(a.c0, a.c1), F2::add(b.c0, b.c1)), t0), t1), e2_mul_xi(t2));
-    r.c2 = F2::add(F2::sub(F2::sub(F2::mul(F2::add(a.c0, a.c2), F2::add(b.c0, b.c2)), t0), t2), t1);
-    return r;
-}
-inline E6 e6_mul_v(const E6& a) { return {e2_mul_xi(a.c2), a.c0, a.c1}; }
-// a * (b0 + b1 v)
-inline E6 e6_mul_by_01(const E6& a, const E2& b0, const E2& b1) {
-    return {F2::add(F2::mul(a.c0, b0), e2_mul_xi(F2::mul(a.c2, b1))), F2::add(F2::mul(a.c0, b1), F2::mul(a.c1, b0)),
-            F2::add(F2::mul(a.c1, b1), F2::mul(a.c2, b0))};
-}
-// a * (k v) with k in Fp
-inline E6 e6_mul_by_1_fp(const E6& a, const HFp& k) { return {e2_mul_xi(e2_scale(a.c2, k)), e2_scale(a.c0, k), e2_scale(a.c1, k)}; }
-inline E6 e6_inv(const E6& a) {
-    const E2 c0 = F2::sub(F2::sqr(a.c0), e2_mul_xi(F2::mul(a.c1, a.c2)));
-    const E2 c1 = F2::sub(e2_mul_xi(F2::sqr(a.c2)), F2::mul(a.c0, a.c1));
-    const E2 c2 = F2::sub(F2::sqr(a.c1), F2::mul(a.c0, a.c2));
-    const E2 t = F2::add(F2::mul(a.c0, c0), e2_mul_xi(F2::add(F2::mul(a.c2, c1), F2::mul(a.c1, c2))));
-    const E2 ti = F2::inv(t);
-    return {F2::mul(c0, ti), F2::mul(c1, ti), F2::mul(c2, ti)};
-}
+inline E2 e2_mul_xi(const E2& a) { return TW::e2_mul_xi(a); }
+inline E2 e2_scale(const E2& a, const HFp& k) { return TW::e2_scale(a, k); }
+inline E2 e2_conj(const E2& a) { return TW::e2_conj(a); }
+inline E6 e6_zero() { return TW::e6_zero(); }
+inline E6 e6_one() { return TW::e6_one(); }
+inline E6 e6_add(const E6& a, const E6& b) { return TW::e6_add(a, b); }
+inline E6 e6_sub(const E6& a, const E6& b) { return TW::e6_sub(a, b); }
+inline E6 e6_neg(const E6& a) { return TW::e6_neg(a); }
+inline E6 e6_mul(const E6& a, const E6& b) { return TW::e6_mul(a, b); }
+inline E6 e6_mul_v(const E6& a) { return TW::e6_mul_v(a); }
+inline E6 e6_mul_by_01(const E6& a, const E2& b0, const E2& b1) { return TW::e6_mul_by_01(a, b0, b1); }
+inline E6 e6_mul_by_1_fp(const E6& a, const HFp& k) { return TW::e6_mul_by_1_fp(a, k); }
+inline E6 e6_mul_by_1(const E6& a, const E2& b1) { return TW::e6_mul_by_1(a, b1); }
+inline E6 e6_inv(const E6& a) { return TW::e6_inv(a); }
 inline E12 e12_one() { return {e6_one(), e6_zero()}; }
 inline E12 e12_mul(const E12& a, const E12& b) {
-    const E6 t0 = e6_mul(a.a0, b.a0), t1 = e6_mul(a.a1, b.a1);
-    E12 r;
-    r.a0 = e6_add(t0, e6_mul_v(t1));
-    r.a1 = e6_sub(e6_sub(e6_mul(e6_add(a.a0, a.a1), e6_add(b.a0, b.a1)), t0), t1);
-    return r;
+    HFp s[48];
+    put12(s, 0, a); put12(s, 12, b);
+    pairing::e12_mul(LaneH{s}, 24, 0, 12, 36);
+    return get12(s, 24);
 }
-inline E12 e12_sqr(const E12& a) {  // (a0 + a1 w)^2 = (a0 + a1)(a0 + v a1) - ab - v ab + 2 ab w,  ab = a0 a1
-    const E6 ab = e6_mul(a.a0, a.a1);
-    E12 r;
-    r.a0 = e6_sub(e6_sub(e6_mul(e6_add(a.a0, a.a1), e6_add(a.a0, e6_mul_v(a.a1))), ab), e6_mul_v(ab));
-    r.a1 = e6_add(ab, ab);
-    return r;
+inline E12 e12_sqr(const E12& a) {
+    HFp s[36];
+    put12(s, 0, a);
+    pairing::e12_sqr(LaneH{s}, 12, 0, 24);
+    return get12(s, 12);
 }
 inline E12 e12_conj(const E12& a) { return {a.a0, e6_neg(a.a1)}; }
 inline E12 e12_inv(const E12& a) {
-    const E6 t = e6_inv(e6_sub(e6_mul(a.a0, a.a0), e6_mul_v(e6_mul(a.a1, a.a1))));
-    return {e6_mul(a.a0, t), e6_neg(e6_mul(a.a1, t))};
+    HFp s[36];
+    put12(s, 0, a);
+    pairing::e12_inv(LaneH{s}, 12, 0, 24);
+    return get12(s, 12);
 }
-inline bool e6_eq(const E6& a, const E6& b) { return F2::eq(a.c0, b.c0) && F2::eq(a.c1, b.c1) && F2::eq(a.c2, b.c2); }
+inline bool e6_eq(const E6& a, const E6& b) { return TW::e6_eq(a, b); }
 inline bool e12_eq(const E12& a, const E12& b) { return e6_eq(a.a0, b.a0) && e6_eq(a.a1, b.a1); }
 inline bool e12_is_one(const E12& a) { return e12_eq(a, e12_one()); }
 
-// f * l for a line l = l00 + l01 v + (l11 v) w with l11 in Fp (what `line` below produces): 6 + 6 + 3 Fp2-size products instead of 18
+// f * l for a line l = l00 + l01 v + (l11 v) w with l11 in Fp (the affine loop's lines): 6 + 6 + 3 Fp2-size products instead of 18
 inline E12 e12_mul_by_line(const E12& f, const E2& l00, const E2& l01, const HFp& l11) {
     const E6 t0 = e6_mul_by_01(f.a0, l00, l01);
     const E6 t1 = e6_mul_by_1_fp(f.a1, l11);
@@ -95,16 +102,36 @@ inline E12 e12_mul_by_line(const E12& f, const E2& l00, const E2& l01, const HFp
     r.a1 = e6_sub(e6_sub(e6_mul_by_01(e6_add(f.a0, f.a1), l00, s01), t0), t1);
     return r;
 }
-
 // the same with l11 in Fp2 (the projective lines): positions 0, 1 and 4 of the tower - 6 + 3 + 6 Fp2 products
-inline E6 e6_mul_by_1(const E6& a, const E2& b1) { return {e2_mul_xi(F2::mul(a.c2, b1)), F2::mul(a.c0, b1), F2::mul(a.c1, b1)}; }
 inline E12 e12_mul_by_014(const E12& f, const E2& c0, const E2& c1, const E2& c4) {
-    const E6 t0 = e6_mul_by_01(f.a0, c0, c1);
-    const E6 t1 = e6_mul_by_1(f.a1, c4);
-    E12 r;
-    r.a0 = e6_add(t0, e6_mul_v(t1));
-    r.a1 = e6_sub(e6_sub(e6_mul_by_01(e6_add(f.a0, f.a1), c0, F2::add(c1, c4)), t0), t1);
-    return r;
+    HFp s[30];
+    put12(s, 0, f);
+    memcpy(s + 12, &c0, sizeof c0); memcpy(s + 14, &c1, sizeof c1); memcpy(s + 16, &c4, sizeof c4);
+    pairing::e12_mul_by_014(LaneH{s}, 0, 12, 18);
+    return get12(s, 0);
+}
+
+// ---- the library's packed points.  Montgomery limbs of an Fp element are below p: anything else is not a value `Fp([u64; 6])` can legitimately
+// hold, and arithmetic on it would leave the verdict to the reduction details of whichever library runs it
+struct G1A { HFp x, y; bool inf; };
+struct G2A { E2 x, y; bool inf; };
+inline bool fp_in_range(const HFp& a) { return !hfp::geq_p(a.l, hfp::consts().p); }
+inline HFp fp_four() { return F1::dbl(F1::dbl(F1::one())); }   // Montgomery form of 4
+inline bool g1_unpack(const uint8_t* in, G1A& o) {  // packed 97 bytes; range + on-curve check
+    o.inf = in[96] != 0;
+    memcpy(o.x.l, in, 48);
+    memcpy(o.y.l, in + 48, 48);
+    if (o.inf) return true;
+    if (!fp_in_range(o.x) || !fp_in_range(o.y)) return false;
+    return F1::eq(F1::sqr(o.y), F1::add(F1::mul(F1::sqr(o.x), o.x), fp_four()));
+}
+inline bool g2_unpack(const uint8_t* in, G2A& o) {
+    o.inf = in[192] != 0;
+    memcpy(o.x.c0.l, in, 48); memcpy(o.x.c1.l, in + 48, 48); memcpy(o.y.c0.l, in + 96, 48); memcpy(o.y.c1.l, in + 144, 48);
+    if (o.inf) return true;
+    if (!fp_in_range(o.x.c0) || !fp_in_range(o.x.c1) || !fp_in_range(o.y.c0) || !fp_in_range(o.y.c1)) return false;
+    const E2 b = {fp_four(), fp_four()};
+    return F2::eq(F2::sqr(o.y), F2::add(F2::mul(F2::sqr(o.x), o.x), b));
 }
 
 // ---- Frobenius: (sum_i c_i w^i)^p = sum_i conj(c_i) gamma_i w^i,  gamma_i = xi^(i (p - 1) / 6)
@@ -138,67 +165,39 @@ inline const FrobConsts& frob_consts() {
     return c;
 }
 inline E12 e12_frob(const E12& f) {
-    const FrobConsts& k = frob_consts();
-    E12 r;
-    r.a0.c0 = e2_conj(f.a0.c0);                       // w^0
-    r.a1.c0 = F2::mul(e2_conj(f.a1.c0), k.g[1]);      // w^1
-    r.a0.c1 = F2::mul(e2_conj(f.a0.c1), k.g[2]);      // w^2 = v
-    r.a1.c1 = F2::mul(e2_conj(f.a1.c1), k.g[3]);      // w^3
-    r.a0.c2 = F2::mul(e2_conj(f.a0.c2), k.g[4]);      // w^4 = v^2
-    r.a1.c2 = F2::mul(e2_conj(f.a1.c2), k.g[5]);      // w^5
-    return r;
+    HFp s[24];
+    put12(s, 0, f);
+    pairing::e12_frob(LaneH{s}, 12, 0, frob_consts().g);
+    return get12(s, 12);
 }
-
-// ---- squaring in the cyclotomic subgroup (Granger - Scott): three squarings in Fp4 = Fp2[t] / (t^2 - xi) over the pairs
-// (c0, c3), (c1, c4), (c2, c5) of  f = sum c_i w^i  regrouped as  (c0 + c3 w^3) + (c1 + c4 w^3) w + (c2 + c5 w^3) w^2,  (w^3)^2 = xi
-inline void fp4_sqr(const E2& a, const E2& b, E2& o0, E2& o1) {  // (a + b t)^2 = a^2 + xi b^2 + ((a + b)^2 - a^2 - b^2) t
-    const E2 t0 = F2::sqr(a), t1 = F2::sqr(b);
-    o0 = F2::add(e2_mul_xi(t1), t0);
-    o1 = F2::sub(F2::sub(F2::sqr(F2::add(a, b)), t0), t1);
-}
+// squaring in the cyclotomic subgroup (Granger - Scott, see bzk_pairing28.cuh)
+inline void fp4_sqr(const E2& a, const E2& b, E2& o0, E2& o1) { TW::fp4_sqr(a, b, o0, o1); }
 inline E12 e12_cyc_sqr(const E12& f) {
-    // coefficients by power of w: w^0 = a0.c0, w^1 = a1.c0, w^2 = a0.c1, w^3 = a1.c1, w^4 = a0.c2, w^5 = a1.c2
-    const E2 &c0 = f.a0.c0, &c1 = f.a1.c0, &c2 = f.a0.c1, &c3 = f.a1.c1, &c4 = f.a0.c2, &c5 = f.a1.c2;
-    E2 A0, A1, B0, B1, C0, C1;
-    fp4_sqr(c0, c3, A0, A1);  // (c0 + c3 t)^2
-    fp4_sqr(c1, c4, B0, B1);  // (c1 + c4 t)^2
-    fp4_sqr(c2, c5, C0, C1);  // (c2 + c5 t)^2
-    // g = x + y s + z s^2 over Fp4 (s = w, s^3 = t), unitary:  g^2 = (3 x^2 - 2 conj x) + (3 t z^2 + 2 conj y) s + (3 y^2 - 2 conj z) s^2,
-    // conj (a + b t) = a - b t
-    auto three_minus_two = [](const E2& sq, const E2& v) { const E2 d = F2::sub(sq, v); return F2::add(F2::add(d, d), sq); };   // 3 sq - 2 v
-    auto three_plus_two = [](const E2& sq, const E2& v) { const E2 d = F2::add(sq, v); return F2::add(F2::add(d, d), sq); };     // 3 sq + 2 v
-    E12 r;
-    r.a0.c0 = three_minus_two(A0, c0);            // w^0: 3 A0 - 2 c0
-    r.a1.c1 = three_plus_two(A1, c3);             // w^3: 3 A1 + 2 c3
-    const E2 tz0 = e2_mul_xi(C1);                 // t (C0 + C1 t) = xi C1 + C0 t
-    r.a1.c0 = three_plus_two(tz0, c1);            // w^1: 3 xi C1 + 2 c1
-    r.a0.c2 = three_minus_two(C0, c4);            // w^4: 3 C0 - 2 c4
-    r.a0.c1 = three_minus_two(B0, c2);            // w^2: 3 B0 - 2 c2
-    r.a1.c2 = three_plus_two(B1, c5);             // w^5: 3 B1 + 2 c5
-    return r;
+    HFp s[12];
+    put12(s, 0, f);
+    pairing::e12_cyc_sqr(LaneH{s}, 0, 0);
+    return get12(s, 0);
 }
-static constexpr uint64_t X_ABS = 0xd201000000010000ull;
+static constexpr uint64_t X_ABS = pairing::X_ABS;
 // g^x for g in the cyclotomic subgroup (x = -|x|: the inverse there is the conjugate)
 inline E12 e12_cyc_exp_x(const E12& g) {
-    E12 r = g;  // bit 63 of |x| is the leading one
-    for (int i = 62; i >= 0; --i) {
-        r = e12_cyc_sqr(r);
-        if ((X_ABS >> i) & 1) r = e12_mul(r, g);
-    }
-    return e12_conj(r);
+    HFp s[36];
+    put12(s, 0, g);
+    pairing::e12_cyc_exp_x(LaneH{s}, 12, 0, 24);
+    return get12(s, 12);
 }
-inline E12 final_exp_easy(const E12& f) {
-    const E12 g = e12_mul(e12_conj(f), e12_inv(f));   // f^(p^6 - 1)
-    return e12_mul(e12_frob(e12_frob(g)), g);        // ^(p^2 + 1)
+inline E12 final_exp_easy(const E12& f) {   // f^(p^6 - 1)(p^2 + 1)
+    HFp s[pairing::slot::COUNT];
+    put12(s, pairing::slot::F, f);
+    pairing::final_exp_easy(LaneH{s}, frob_consts().g);
+    return get12(s, pairing::slot::R1);
 }
 // (easy part)^( (x - 1)^2 (x + p)(x^2 + p^2 - 1) + 3 ) = f^(3 (p^12 - 1) / r)
 inline E12 final_exp(const E12& f) {
-    const E12 m = final_exp_easy(f);
-    const E12 t = e12_mul(e12_cyc_exp_x(m), e12_conj(m));                               // m^(x - 1)
-    const E12 a = e12_mul(e12_cyc_exp_x(t), e12_conj(t));                               // m^((x - 1)^2)
-    const E12 b = e12_mul(e12_cyc_exp_x(a), e12_frob(a));                               // a^(x + p)
-    const E12 c = e12_mul(e12_mul(e12_cyc_exp_x(e12_cyc_exp_x(b)), e12_frob(e12_frob(b))), e12_conj(b));   // b^(x^2 + p^2 - 1)
-    return e12_mul(c, e12_mul(e12_cyc_sqr(m), m));                                      // * m^3
+    HFp s[pairing::slot::COUNT];
+    put12(s, pairing::slot::F, f);
+    pairing::final_exp(LaneH{s}, frob_consts().g);
+    return get12(s, pairing::slot::R4);
 }
 
 // the first version's final exponentiation: easy half by conjugate / inverse, everything else as one exponentiation by (p^6 + 1) / r
@@ -221,8 +220,6 @@ inline E12 final_exp_plain(const E12& f) {
 }
 
 // ---- Miller loop
-struct G1A { HFp x, y; bool inf; };
-struct G2A { E2 x, y; bool inf; };
 
 // f *= the line through T (twist coordinates, slope lam) evaluated at P, up to a factor the final exponentiation kills:
 // (lam xT - yT) + (-lam xP) w^2 + yP w^3
@@ -255,56 +252,41 @@ inline bool batch_inv(const E2* d, int n, E2* out) {
 // is used multiplied by its slope's denominator (an Fp2 factor the final exponentiation removes):
 //   doubling  lam = 3 X^2 / (2 Y Z),          x 2 Y Z^3:   (3 X^3 - 2 Y^2)  -  3 X^2 Z^2 xP w^2  +  2 Y Z^3 yP w^3
 //   addition  lam = (yQ Z^3 - Y) / (Z H),     x Z H:       (R xQ - yQ Z H)  -  R xP w^2          +  Z H yP w^3       H = xQ Z^2 - X, R = yQ Z^3 - Y
-struct G2J { E2 X, Y, Z; };
+typedef TW::G2J G2J;
 inline E12 multi_miller(const G1A* p, const G2A* q, int n, bool* degenerate) {
     G2J t[4];
     int live[4], nl = 0;
     for (int k = 0; k < n && k < 4; ++k)
         if (!p[k].inf && !q[k].inf) { t[nl] = {q[k].x, q[k].y, F2::one()}; live[nl++] = k; }
-    E12 f = e12_one();
+    // the accumulator stays in a local slab through the loop: f in slots 0 .. 11, the line in 12 .. 17, temporaries in 18 .. 29
+    HFp s[30];
+    const LaneH l = {s};
+    const auto mul_line014 = [&](const E2& l00, const E2& c1, const E2& c4) {
+        pairing::st2(l, 12, l00); pairing::st2(l, 14, c1); pairing::st2(l, 16, c4);
+        pairing::e12_mul_by_014(l, 0, 12, 18);
+    };
+    pairing::e12_set_one(l, 0);
     for (int i = 62; i >= 0; --i) {  // bit 63 is the leading one
-        f = e12_sqr(f);
+        pairing::e12_sqr(l, 0, 0, 18);
         for (int j = 0; j < nl; ++j) {
             G2J& T = t[j];
             const G1A& P = p[live[j]];
-            if (F2::is_zero(T.Y)) { *degenerate = true; return e12_one(); }   // vertical tangent (Z is never zero before this happens)
-            const E2 A = F2::sqr(T.X), B = F2::sqr(T.Y), C = F2::sqr(B), ZZ = F2::sqr(T.Z);
-            const E2 E = F2::add(F2::add(A, A), A);                                          // 3 X^2
-            E2 D = F2::sub(F2::sub(F2::sqr(F2::add(T.X, B)), A), C);
-            D = F2::add(D, D);                                                               // 4 X Y^2
-            const E2 Z3 = F2::sub(F2::sub(F2::sqr(F2::add(T.Y, T.Z)), B), ZZ);               // 2 Y Z
-            // line (before the point moves)
-            const E2 l00 = F2::sub(F2::mul(E, T.X), F2::add(B, B));                          // 3 X^3 - 2 Y^2
-            const E2 l01 = e2_scale(F2::neg(F2::mul(E, ZZ)), P.x);                           // - 3 X^2 Z^2 xP
-            const E2 l11 = e2_scale(F2::mul(Z3, ZZ), P.y);                                   // 2 Y Z^3 yP  (an Fp2 value here, not Fp)
-            f = e12_mul_by_014(f, l00, l01, l11);
-            const E2 X3 = F2::sub(F2::sqr(E), F2::add(D, D));
-            E2 C8 = F2::add(C, C);
-            C8 = F2::add(C8, C8);
-            C8 = F2::add(C8, C8);
-            T = {X3, F2::sub(F2::mul(E, F2::sub(D, X3)), C8), Z3};
+            E2 l00, cx, cy;
+            if (!TW::dbl_coeffs(T, l00, cx, cy)) { *degenerate = true; return e12_one(); }   // vertical tangent
+            mul_line014(l00, e2_scale(cx, P.x), e2_scale(cy, P.y));
         }
         if ((X_ABS >> i) & 1) {
             for (int j = 0; j < nl; ++j) {
                 G2J& T = t[j];
                 const G1A& P = p[live[j]];
                 const G2A& Q = q[live[j]];
-                const E2 ZZ = F2::sqr(T.Z);
-                const E2 H = F2::sub(F2::mul(Q.x, ZZ), T.X);
-                const E2 Rr = F2::sub(F2::mul(Q.y, F2::mul(ZZ, T.Z)), T.Y);
-                if (F2::is_zero(H)) { *degenerate = true; return e12_one(); }                // T = +-Q
-                const E2 Z3 = F2::mul(T.Z, H);
-                const E2 l00 = F2::sub(F2::mul(Rr, Q.x), F2::mul(Q.y, Z3));
-                const E2 l01 = e2_scale(F2::neg(Rr), P.x);
-                const E2 l11 = e2_scale(Z3, P.y);
-                f = e12_mul_by_014(f, l00, l01, l11);
-                const E2 HH = F2::sqr(H), HHH = F2::mul(HH, H), V = F2::mul(T.X, HH);
-                const E2 X3 = F2::sub(F2::sub(F2::sqr(Rr), HHH), F2::add(V, V));
-                T = {X3, F2::sub(F2::mul(Rr, F2::sub(V, X3)), F2::mul(T.Y, HHH)), Z3};
+                E2 l00, cx, cy;
+                if (!TW::add_coeffs(T, Q.x, Q.y, l00, cx, cy)) { *degenerate = true; return e12_one(); }   // T = +-Q
+                mul_line014(l00, e2_scale(cx, P.x), e2_scale(cy, P.y));
             }
         }
     }
-    return e12_conj(f);  // the curve parameter is -|x|
+    return e12_conj(get12(s, 0));  // the curve parameter is -|x|
 }
 
 // the same product with AFFINE running points (slopes inverted together, one Fp2 inversion per step): the second version, kept as the
@@ -341,6 +323,120 @@ inline E12 multi_miller_affine(const G1A* p, const G2A* q, int n, bool* degenera
     }
     return e12_conj(f);  // the curve parameter is -|x|
 }
+
+// ==== a verifying key as the batched verifier prepares it, once per call (verify.hip; tests/host/pairing28_check.hip)
+// ---- what a call prepares from its key, in the host field
+struct KeyHost {
+    bool valid = false;   // false: InvalidVerifyingKey, or a key point off its curve / out of range - every verdict is 0
+    uint32_t n_inputs = 0;
+    std::vector<HFp> tab_xy;
+    std::vector<uint8_t> tab_inf;
+    std::vector<HFp2> gamma, delta;
+    uint32_t gamma_live = 0, delta_live = 0, gamma_steps = 0, delta_steps = 0;
+    HFp m[12];
+    pairing::KeyView<HFpOps, HFp2Ops> view() const {
+        return {n_inputs, tab_xy.data(), tab_inf.data(), gamma.data(), delta.data(), m, frob_consts().g, gamma_live, delta_live, gamma_steps,
+                delta_steps};
+    }
+};
+// the line coefficients of the running point of q over the whole loop (they do not depend on the first argument); returns how many lines there
+// are before a zero slope denominator (MILLER_STEPS: all of them)
+inline uint32_t line_table(const G2A& q, std::vector<HFp2>& out) {
+    out.assign((size_t)3 * pairing::MILLER_STEPS, HFp2Ops::zero());
+    TW::G2J T = {q.x, q.y, HFp2Ops::one()};
+    uint32_t step = 0;
+    for (int i = 62; i >= 0; --i) {
+        if (!TW::dbl_coeffs(T, out[3 * step], out[3 * step + 1], out[3 * step + 2])) return step;
+        ++step;
+        if ((pairing::X_ABS >> i) & 1) {
+            if (!TW::add_coeffs(T, q.x, q.y, out[3 * step], out[3 * step + 1], out[3 * step + 2])) return step;
+            ++step;
+        }
+    }
+    return step;
+}
+inline void key_prepare(const uint8_t* vk, uint64_t vk_len, uint32_t n_inputs, KeyHost& K) {
+    K.n_inputs = n_inputs;
+    uint64_t n_ic;
+    memcpy(&n_ic, vk + 870, 8);
+    if (n_ic != (uint64_t)n_inputs + 1 || vk_len != 878 + 97 * n_ic) return;  // verify_proof: VerificationError::InvalidVerifyingKey
+    G1A alpha, ic;
+    G2A beta, gamma, delta;
+    if (!g1_unpack(vk, alpha) || !g2_unpack(vk + 194, beta) || !g2_unpack(vk + 387, gamma) || !g2_unpack(vk + 677, delta)) return;
+    // j IC_i for j = 1 .. 15 (the 4-bit windows of input i), affine, and IC_0 last; an entry may be the identity (IC_i at infinity, or of small order)
+    typedef XyzzT<HFpOps> Pt;
+    const size_t entries = (size_t)15 * n_inputs + 1;
+    K.tab_xy.assign(2 * entries, HFpOps::zero());
+    K.tab_inf.assign(entries, 1);
+    auto put = [&](size_t e, const Pt& p) {
+        AffineT<HFpOps> a;
+        if (!xyzz_to_affine<HFpOps>(p, a)) return;
+        K.tab_inf[e] = 0;
+        K.tab_xy[2 * e] = a.x;
+        K.tab_xy[2 * e + 1] = a.y;
+    };
+    for (uint64_t i = 0; i < n_ic; ++i) {
+        if (!g1_unpack(vk + 878 + 97 * i, ic)) return;
+        const Pt one = ic.inf ? xyzz_identity<HFpOps>() : xyzz_from_affine<HFpOps>({ic.x, ic.y});
+        if (i == 0) {
+            put(entries - 1, one);
+            continue;
+        }
+        Pt t = one;
+        for (int j = 0; j < 15; ++j) {
+            put(15 * (i - 1) + j, t);
+            xyzz_add<HFpOps>(t, one);
+        }
+    }
+    // e(A, B) e(X, -gamma) e(C, -delta) e(-alpha, beta) == 1
+    gamma.y = F2::neg(gamma.y);
+    delta.y = F2::neg(delta.y);
+    alpha.y = F1::neg(alpha.y);
+    K.gamma_live = !gamma.inf;
+    K.delta_live = !delta.inf;
+    K.gamma_steps = gamma.inf ? (uint32_t)pairing::MILLER_STEPS : line_table(gamma, K.gamma);
+    K.delta_steps = delta.inf ? (uint32_t)pairing::MILLER_STEPS : line_table(delta, K.delta);
+    if (gamma.inf) K.gamma.assign((size_t)3 * pairing::MILLER_STEPS, HFp2Ops::zero());
+    if (delta.inf) K.delta.assign((size_t)3 * pairing::MILLER_STEPS, HFp2Ops::zero());
+    bool degenerate = false;
+    const E12 m = multi_miller(&alpha, &beta, 1, &degenerate);   // a constant of the key: Miller functions of a shared accumulator multiply
+    if (degenerate) return;                                      // the single call meets the same exit in its loop: 0 whatever the proof
+    memcpy(K.m, &m, sizeof m);
+    K.valid = true;
+}
+
+inline Fp28 h_to28(const HFp& a) {
+    Fp t;
+    memcpy(t.l, a.l, 48);
+    return fp28::to28(t);
+}
+// the key's tables in the device field, packed into one upload: tab_xy | gamma | delta | m | frob | tab_inf
+struct KeyUpload {
+    std::vector<uint8_t> bytes;
+    size_t at_tab = 0, at_gamma = 0, at_delta = 0, at_m = 0, at_frob = 0, at_inf = 0;
+    explicit KeyUpload(const KeyHost& K) {
+        std::vector<Fp28> f;
+        auto put2 = [&](const HFp2& a) { f.push_back(h_to28(a.c0)); f.push_back(h_to28(a.c1)); };
+        at_tab = 0;
+        for (const HFp& a : K.tab_xy) f.push_back(h_to28(a));
+        at_gamma = f.size() * sizeof(Fp28);
+        for (const HFp2& a : K.gamma) put2(a);
+        at_delta = f.size() * sizeof(Fp28);
+        for (const HFp2& a : K.delta) put2(a);
+        at_m = f.size() * sizeof(Fp28);
+        for (int i = 0; i < 12; ++i) f.push_back(h_to28(K.m[i]));
+        at_frob = f.size() * sizeof(Fp28);
+        for (int i = 0; i < 6; ++i) put2(frob_consts().g[i]);
+        at_inf = f.size() * sizeof(Fp28);
+        bytes.resize(at_inf + K.tab_inf.size());
+        memcpy(bytes.data(), f.data(), at_inf);
+        memcpy(bytes.data() + at_inf, K.tab_inf.data(), K.tab_inf.size());
+    }
+    pairing::KeyView<Fp28Ops, Fp2x28Ops> view(const KeyHost& K, const uint8_t* d) const {
+        return {K.n_inputs, (const Fp28*)(d + at_tab), d + at_inf, (const Fp2x28*)(d + at_gamma), (const Fp2x28*)(d + at_delta),
+                (const Fp28*)(d + at_m), (const Fp2x28*)(d + at_frob), K.gamma_live, K.delta_live, K.gamma_steps, K.delta_steps};
+    }
+};
 
 }  // namespace hp
 }  // namespace bzk

@@ -27,29 +27,8 @@ using hp::F2;
 using hp::G1A;
 using hp::G2A;
 
-// Montgomery limbs of an Fp element are below p: anything else is not a value `Fp([u64; 6])` can legitimately hold, and arithmetic on
-// it would leave the verdict to the reduction details of whichever library runs it
-bool fp_in_range(const HFp& a) { return !hfp::geq_p(a.l, hfp::consts().p); }
-HFp fp_four() {  // Montgomery form of 4
-    const HFp two = F1::dbl(F1::one());
-    return F1::dbl(two);
-}
-bool g1_unpack(const uint8_t* in, G1A& o) {  // packed 97 bytes; range + on-curve check
-    o.inf = in[96] != 0;
-    memcpy(o.x.l, in, 48);
-    memcpy(o.y.l, in + 48, 48);
-    if (o.inf) return true;
-    if (!fp_in_range(o.x) || !fp_in_range(o.y)) return false;
-    return F1::eq(F1::sqr(o.y), F1::add(F1::mul(F1::sqr(o.x), o.x), fp_four()));
-}
-bool g2_unpack(const uint8_t* in, G2A& o) {
-    o.inf = in[192] != 0;
-    memcpy(o.x.c0.l, in, 48); memcpy(o.x.c1.l, in + 48, 48); memcpy(o.y.c0.l, in + 96, 48); memcpy(o.y.c1.l, in + 144, 48);
-    if (o.inf) return true;
-    if (!fp_in_range(o.x.c0) || !fp_in_range(o.x.c1) || !fp_in_range(o.y.c0) || !fp_in_range(o.y.c1)) return false;
-    const E2 b = {fp_four(), fp_four()};
-    return F2::eq(F2::sqr(o.y), F2::add(F2::mul(F2::sqr(o.x), o.x), b));
-}
+using hp::g1_unpack;
+using hp::g2_unpack;
 
 }  // namespace
 

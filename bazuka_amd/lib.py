@@ -105,6 +105,8 @@ SIGNATURES = {
     "bzk_bellman_params_encode": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     "bzk_params_load_bellman": (_i32, [_vp, _vp, _u64, _u32, _u32, _vp, _vp, C.POINTER(_vp), _vp, _u64]),
     "bzk_groth16_verify": (_i32, [_vp, _u64, _vp, _u32, _vp]),
+    "bzk_groth16_verify_batch": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp]),
+    "bzk_groth16_verify_batch_dev": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp]),
     "bzk_params_read": (_i32, [_vp, _vp, _i32, _vp, _u64, C.POINTER(_u64)]),
     "bzk_groth16_setup": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, C.POINTER(_vp), _vp, _u64]),
     "bzk_groth16_h_dev": (_i32, [_vp, _vp, _vp, _vp, _u32]),
@@ -426,6 +428,10 @@ class Bzk:
         """Ed25519 (the node's non-strict ed25519-dalek 1 verifier) for len(msgs) signatures: pks n x 32, sigs n x 64; verdict bytes"""
         return _ed25519_verify_batch(self.h, pks, msgs, sigs)
 
+    def groth16_verify_batch(self, vk_bincode: bytes, inputs: bytes, n_inputs: int, proofs: bytes) -> bytes:
+        """`groth16_verify` for len(proofs) / 387 proofs of one key, one device lane per proof: inputs n x n_inputs x 32 B Montgomery; verdict bytes"""
+        return _groth16_verify_batch(self.h, vk_bincode, inputs, n_inputs, proofs)
+
     def mpn_deposit_verify_batch(self, txs: bytes, n: int, want_address: bool = True):
         """n consecutive bincode(MpnDeposit): (verdict bytes: bit 0 the payment's Ed25519 signature, bit 1 the address decompresses; addresses
         n x 64 or None); a malformed record raises"""
@@ -502,6 +508,11 @@ class Bzk:
     def ed25519_verify_batch_dev(self, pk, msg, off, sig, n: int, ok):
         """device buffers: pk n x 32, message bytes, off n + 1 u64, sig n x 64; ok n verdict bytes, written in stream order"""
         self._ck(self.lib.bzk_ed25519_verify_batch_dev(self.h, _ptr(pk), _ptr(msg), _ptr(off), _ptr(sig), n, _ptr(ok)), "ed25519_verify_batch_dev")
+
+    def groth16_verify_batch_dev(self, vk_bincode: bytes, inputs, n_inputs: int, proofs, n: int, ok):
+        """device buffers: inputs n x n_inputs x 32, proofs n x 387; ok n verdict bytes (the key is host bytes); synchronises"""
+        self._ck(self.lib.bzk_groth16_verify_batch_dev(self.h, _ptr(vk_bincode), len(vk_bincode), _ptr(inputs), n_inputs, _ptr(proofs), n, _ptr(ok)),
+                 "groth16_verify_batch_dev")
 
     def merkle4_root_dev(self, leaves, log4: int, nodes=None) -> bytes:
         root = C.create_string_buffer(32)
@@ -1496,6 +1507,21 @@ def _ed25519_verify_batch(ctx_handle, pks: bytes, msgs, sigs: bytes) -> bytes:
 def host_ed25519_verify_batch(pks: bytes, msgs, sigs: bytes) -> bytes:
     """Bzk.ed25519_verify_batch without a device: the same per-lane code on host threads"""
     return _ed25519_verify_batch(None, pks, msgs, sigs)
+
+
+def _groth16_verify_batch(ctx_handle, vk_bincode: bytes, inputs: bytes, n_inputs: int, proofs: bytes) -> bytes:
+    n = len(proofs) // 387
+    if len(proofs) != 387 * n or len(inputs) != 32 * n_inputs * n:
+        raise BzkError("groth16_verify_batch: proofs must hold 387 and inputs 32 n_inputs bytes per proof")
+    ok = C.create_string_buffer(max(n, 1))
+    _st(load_library().bzk_groth16_verify_batch(ctx_handle, _ptr(vk_bincode), len(vk_bincode), _ptr(inputs) if inputs else None, n_inputs,
+                                                _ptr(proofs) if n else None, n, ok), "groth16_verify_batch")
+    return ok.raw[:n]
+
+
+def host_groth16_verify_batch(vk_bincode: bytes, inputs: bytes, n_inputs: int, proofs: bytes) -> bytes:
+    """Bzk.groth16_verify_batch without a device: the same per-proof functions over the host field on host threads"""
+    return _groth16_verify_batch(None, vk_bincode, inputs, n_inputs, proofs)
 
 
 def host_sha512(b: bytes) -> bytes:

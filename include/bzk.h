@@ -419,6 +419,20 @@ int32_t bzk_params_load_bellman(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len
  * aux_data, next_state).  Returns 1 (verifies), 0 (does not - incl. malformed or off-curve points, for which the reference returns
  * false), negative on bad arguments.  ~20 ms on one core. */
 int32_t bzk_groth16_verify(const uint8_t* vk, uint64_t vk_len, const uint8_t* inputs, uint32_t n_inputs, const uint8_t proof[387]);
+/* The same check for n proofs of ONE verifying key (the caller groups its proofs by circuit; MPN has three keys per contract), one GPU lane per
+ * proof: what `apply_tx/update_contract/mod.rs:100` runs per ContractUpdate and `MpnWork::verify` (src/mpn/mod.rs:281-295) per posted solution.
+ * inputs = n x n_inputs Montgomery scalars, proofs = n x 387 bytes; ok[i] = bzk_groth16_verify(vk, vk_len, inputs + 32 n_inputs i, n_inputs,
+ * proofs + 387 i) for any bytes whatever: 1 verifies; 0 does not, a coordinate's limbs are >= p, a point is off its curve, an input's limbs are
+ * >= r, or a line's slope had a zero denominator.  A key the single call refuses with 0 (n_ic != n_inputs + 1, a wrong vk_len, a key point off
+ * its curve or out of range) gives ok[i] = 0 for all i and BZK_OK.  Null pointers with n > 0 or vk_len < 878: BZK_E_ARG, nothing written;
+ * n = 0: BZK_OK.  Once per call the host unpacks the key and builds its window tables, the line coefficients of -gamma and -delta and the
+ * constant Miller value of (-alpha, beta); three kernels (prepare, Miller loop, final exponentiation) then run rounds of at most 2^16 proofs.
+ * ctx = NULL runs the same per-proof functions over the host field on the host's threads; with a context, n_inputs > 16 is routed to that same
+ * host-thread path (same verdicts, no refusal).  The _dev form takes device pointers (vk stays a host pointer) and needs a context. */
+int32_t bzk_groth16_verify_batch(bzk_ctx* ctx, const uint8_t* vk, uint64_t vk_len, const uint8_t* inputs, uint32_t n_inputs,
+                                 const uint8_t* proofs, uint64_t n, uint8_t* ok);
+int32_t bzk_groth16_verify_batch_dev(bzk_ctx* ctx, const uint8_t* vk, uint64_t vk_len, const void* inputs_dev, uint32_t n_inputs,
+                                     const void* proofs_dev, uint64_t n, void* ok_dev);
 /* reads a CRS component back (tests): which = 0 vk (870 B), 1 h, 2 l, 3 a, 4 b_g1, 5 b_g2 */
 int32_t bzk_params_read(bzk_ctx* ctx, const bzk_params* params, int32_t which, uint8_t* out, uint64_t cap, uint64_t* size_out);
 

@@ -21,6 +21,7 @@
 //!   * `Gpu::sha3_merkle_root`  - `MerkleTree::<Sha3Hasher>::new(leaves).root()` (src/crypto/merkle.rs)
 //!   * `Gpu::block_bodies_check` - the body checks of src/blockchain/ops/apply_block.rs:47 and :88 for many blocks in one call
 //!   * `groth16_prove`          - beside `groth16_verify` (src/zk/groth16/mod.rs:67-75), same argument order
+//!   * `groth16_verify_batch`   - `groth16_verify` for n proofs of one key: update_contract/mod.rs:100 and `MpnWork::verify` (src/mpn/mod.rs:281-295)
 //!   * `compress`               - `ZkStateModel::compress::<H>(&data)` (src/zk/mod.rs:392-399)
 //!   * `DeviceStateManager`     - `KvStoreStateManager::{update_contract, root, get_data, prove}` (src/zk/state/mod.rs:218-438) for one
 //!                                contract with the values resident on the GPU
@@ -255,6 +256,30 @@ impl Gpu {
         let mut ok = vec![0u8; n];
         check(self.0, unsafe {
             sys::bzk_ed25519_verify_batch(self.0, pk.as_ptr(), data.as_ptr(), off.as_ptr(), sig.as_ptr(), n as u64, ok.as_mut_ptr())
+        })?;
+        Ok(ok.into_iter().map(|b| b != 0).collect())
+    }
+
+    /// Bulk `groth16_verify` (src/zk/groth16/mod.rs:67-121) for proofs of ONE verifying key, one device lane per proof: what
+    /// src/blockchain/ops/apply_tx/update_contract/mod.rs:100 asks per `ContractUpdate` and `MpnWork::verify` (src/mpn/mod.rs:281-295) per posted
+    /// solution.  `vk` = bincode(Groth16VerifyingKey), every item = (its public inputs as 32-byte Montgomery scalars, the 387-byte proof); all
+    /// items carry the same number of inputs.
+    pub fn groth16_verify_batch(&self, vk: &[u8], items: &[(&[[u8; 32]], &[u8; 387])]) -> Result<Vec<bool>, GpuError> {
+        let n = items.len();
+        let n_inputs = items.first().map_or(0, |(x, _)| x.len());
+        let (mut inputs, mut proofs) = (Vec::with_capacity(32 * n_inputs * n), Vec::with_capacity(387 * n));
+        for (x, p) in items {
+            if x.len() != n_inputs {
+                return Err(GpuError::Status(sys::BZK_E_ARG, "groth16_verify_batch: every proof of a call has the same number of inputs".into()));
+            }
+            for s in x.iter() {
+                inputs.extend_from_slice(&s[..]);
+            }
+            proofs.extend_from_slice(&p[..]);
+        }
+        let mut ok = vec![0u8; n];
+        check(self.0, unsafe {
+            sys::bzk_groth16_verify_batch(self.0, vk.as_ptr(), vk.len() as u64, inputs.as_ptr(), n_inputs as u32, proofs.as_ptr(), n as u64, ok.as_mut_ptr())
         })?;
         Ok(ok.into_iter().map(|b| b != 0).collect())
     }

@@ -1,0 +1,43 @@
+"""Resources of the batched Groth16 verifier's kernels (verify.hip: g16v_prepare_kernel, g16v_miller_kernel, g16v_finalexp_kernel), read from the
+gfx950 code object the build left (tools/kernel_resources.py, as tests/test_l1_code_objects_cpu.py does).  Each exists exactly once, in a code
+object of its own; registers, LDS and private segment equal the figures of the table in DESIGN.md 3.11, so the document cannot drift."""
+import os
+import re
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_resources as kr  # noqa: E402
+
+pytestmark = pytest.mark.skipif(not os.path.isdir(kr.OBJ) or not os.path.exists(os.path.join(kr.OBJ, "verify.o")),
+                                reason="bazuka_amd/csrc/_obj not built (build() compiles it)")
+
+KERNELS = ("g16v_prepare_kernel", "g16v_miller_kernel", "g16v_finalexp_kernel")
+
+
+def _documented():
+    """{kernel: (registers, LDS bytes, private segment bytes)} from the rows `| `kernel` | registers | LDS | private |` of DESIGN.md 3.11"""
+    text = open(os.path.join(ROOT, "DESIGN.md")).read()
+    sec = text[text.index("### 3.11"):]
+    out = {}
+    for m in re.finditer(r"^\| `(g16v_\w+)` \| (\d+) \| (\d+) \| (\d+) \|", sec, re.M):
+        out[m.group(1)] = (int(m.group(2)), int(m.group(3)), int(m.group(4)))
+    return out
+
+
+def test_three_kernels_in_their_own_code_object():
+    rows = [r for r in kr.resources() if r["object"] == "verify"]
+    assert sorted(r["kernel"] for r in rows) == sorted(KERNELS), [r["kernel"] for r in rows]
+    assert [r["kernel"] for r in kr.resources() if r["kernel"].startswith("g16v_") and r["object"] != "verify"] == []
+    for r in rows:
+        assert r["wg"] == 64, r   # one wave per block: a lane never waits for another
+
+
+def test_resources_are_the_documented_ones():
+    doc = _documented()
+    assert sorted(doc) == sorted(KERNELS), doc
+    for r in kr.resources():
+        if r["object"] == "verify":
+            assert (r["vgpr"], r["lds"], r["scratch"]) == doc[r["kernel"]], (r, doc[r["kernel"]])

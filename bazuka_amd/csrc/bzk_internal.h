@@ -70,6 +70,7 @@ struct bzk_ctx {
     // stream priority - read from env BZK_MSM_SPLIT / BZK_MSM_SPLIT_MIN_LOG / BZK_MSM_SPLIT_PRIO when the context is created (tests and A/B runs)
     std::vector<bzk_ctx*> parts;
     int msm_split = 0, msm_split_min_log = 0, msm_split_prio = -1;
+    int msm_front = 0;  // env BZK_MSM_FRONT=sort|partition: how a plain MSM call buckets its pairs (0 = msm_front_plan's measured choice, 1 = radix sort, 2 = partition passes; A/B)
     int msm_split_cuts[4] = {0, 0, 0, 0};  // env BZK_MSM_SPLIT_CUTS="a,b[,c[,d]]": windows per range, highest range first (A/B runs; used when they add up to W)
     bool is_part = false, split_active = false;
     void* split_terms = nullptr;

@@ -122,6 +122,7 @@ bzk_ctx* ctx_lane(bzk_ctx* ctx, size_t i) {
     c->msm_chunk_override = ctx->msm_chunk_override;
     c->msm_reduce2 = ctx->msm_reduce2;
     c->msm_no_endo = ctx->msm_no_endo;
+    c->msm_front = ctx->msm_front;
     return c;
 }
 
@@ -155,6 +156,7 @@ bzk_ctx* ctx_part(bzk_ctx* ctx, size_t i, bool high_prio) {
     c->msm_chunk_override = ctx->msm_chunk_override;
     c->msm_reduce2 = ctx->msm_reduce2;
     c->msm_no_endo = ctx->msm_no_endo;
+    c->msm_front = ctx->msm_front;
     return c;
 }
 
@@ -274,6 +276,10 @@ int32_t bzk_ctx_create(int32_t device_id, void* stream, bzk_ctx** out) {
     if (const char* e = getenv("BZK_MSM_CHUNK")) ctx->msm_chunk_override = atoi(e);
     if (const char* e = getenv("BZK_MSM_REDUCE2")) ctx->msm_reduce2 = atoi(e);
     if (const char* e = getenv("BZK_MSM_NO_ENDO")) ctx->msm_no_endo = atoi(e) != 0;
+    if (const char* e = getenv("BZK_MSM_FRONT")) {
+        ctx->msm_front = !strcmp(e, "sort") ? 1 : !strcmp(e, "partition") ? 2 : 0;
+        if (!ctx->msm_front && *e) fprintf(stderr, "[bzk] BZK_MSM_FRONT=%s is neither sort nor partition: the measured default is used\n", e);
+    }
     if (const char* e = getenv("BZK_MSM_SPLIT")) ctx->msm_split = atoi(e);
     if (const char* e = getenv("BZK_MSM_SPLIT_MIN_LOG")) ctx->msm_split_min_log = atoi(e);
     if (const char* e = getenv("BZK_MSM_SPLIT_PRIO")) ctx->msm_split_prio = atoi(e);

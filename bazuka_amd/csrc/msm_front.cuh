@@ -1,0 +1,145 @@
+// Index arithmetic of the MSM's partition front (msm_impl.cuh section 3d): signed window recoding, the bin of a key, the packed
+// intermediate pair, the layout of the per-tile tables and the plan that picks the shapes.  Everything here is plain integer
+// arithmetic in __host__ __device__ functions: the kernels of section 3d and the CPU model (tests/host/msm_front_check.hip, built
+// with the address and undefined-behaviour sanitizers) run the very same functions, so an index that would leave its array on
+// the device leaves it on the CPU first.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define BZK_FRONT_HD __host__ __device__
+#else
+#define BZK_FRONT_HD
+#endif
+
+namespace bzk {
+
+// ---- signed c-bit window recoding ---------------------------------------------------------------------------------------------
+// digit d in [0, 2^(c-1)] with sign `neg`; raw + carry > 2^(c-1) becomes 2^c - (raw + carry), negative, and carries one into the next window
+struct MsmDigit { uint32_t d, neg; };
+BZK_FRONT_HD inline MsmDigit msm_recode(uint32_t raw, uint32_t& carry, int c) {
+    const uint32_t half = 1u << (c - 1);
+    uint32_t d = raw + carry, neg = 0;
+    if (d > half) {
+        d = (1u << c) - d;
+        neg = 1;
+        carry = 1;
+    } else {
+        carry = 0;
+    }
+    return MsmDigit{d, neg};
+}
+// the w_total signed digits of a canonical 256-bit scalar (8 x 32-bit limbs, little-endian), lowest window first: emit(w, d, neg).
+// The carry out of the top window is dropped (the callers bring the scalar under r < 2^255 first).
+template <class F>
+BZK_FRONT_HD inline void msm_signed_digits(const uint32_t* l, int c, int w_total, F&& emit) {
+    const uint32_t mask = (1u << c) - 1;
+    uint64_t buf = 0;
+    int cnt = 0, w = 0;
+    uint32_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        buf |= (uint64_t)l[j] << cnt;
+        cnt += 32;
+        while (cnt >= c && w < w_total) {
+            const MsmDigit g = msm_recode((uint32_t)buf & mask, carry, c);
+            emit(w, g.d, g.neg);
+            ++w;
+            buf >>= c;
+            cnt -= c;
+        }
+    }
+    while (w < w_total) {
+        const MsmDigit g = msm_recode((uint32_t)buf & mask, carry, c);
+        emit(w, g.d, g.neg);
+        ++w;
+        buf >>= c;
+    }
+}
+
+// ---- shapes ---------------------------------------------------------------------------------------------------------------------
+static constexpr uint32_t FRONT_TILE = 4096;       // scalars per workgroup of the histogram and scatter passes
+static constexpr uint32_t FRONT_THREADS = 1024;    // lanes of those workgroups (FRONT_TILE / FRONT_THREADS scalars per lane)
+static constexpr uint32_t FRONT_GW = 4;            // windows the scatter pass stages in LDS at a time (FRONT_TILE * FRONT_GW values)
+static constexpr uint32_t FRONT_HI_MAX = 7;        // bins per window <= 128: a (tile, window, bin) run is >= 32 values = 128 bytes on average
+static constexpr uint32_t FRONT_LO_MAX = 10;       // buckets per bin <= 1024 (the bin pass's LDS histogram)
+static constexpr uint32_t FRONT_BIN_THREADS = 512; // lanes of a bin-pass workgroup
+static constexpr uint32_t FRONT_BIN_CAP = 12288;   // values a bin-pass workgroup can stage in LDS (48 KiB); fuller bins are scattered straight to memory
+static constexpr uint32_t FRONT_SCAN_BINS = 16;    // bins per workgroup of the scan pass (16 lanes x 4 bytes = one 64-byte line per tile row)
+static constexpr uint32_t FRONT_SCAN_PARTS = 16;   // tile ranges per bin in that workgroup
+
+// Key k = d - 1 in [0, 2^(c-1)) = hi : lo.  A bin is a (window of the group, hi) pair, bins are window-major; the buckets of a bin are its 2^lo_bits keys.
+// Intermediate pair (32 bits, no key array): base index in idx_bits, lo above it, the sign in bit 31 - the window is the bin's.
+struct FrontPlan {
+    bool on = false;  // false: this call keeps the radix sort
+    uint32_t hi_bits = 0, lo_bits = 0, idx_bits = 0;
+    uint32_t n_tiles = 0;
+    BZK_FRONT_HD uint32_t bins_per_window() const { return 1u << hi_bits; }
+    BZK_FRONT_HD uint32_t nbins(uint32_t windows) const { return windows << hi_bits; }
+    BZK_FRONT_HD uint32_t bin_of(uint32_t lw, uint32_t key) const { return (lw << hi_bits) | (key >> lo_bits); }
+    BZK_FRONT_HD uint32_t lo_of(uint32_t key) const { return key & ((1u << lo_bits) - 1); }
+    BZK_FRONT_HD uint32_t pack(uint32_t index, uint32_t key, uint32_t neg) const { return index | (lo_of(key) << idx_bits) | (neg << 31); }
+    BZK_FRONT_HD uint32_t packed_lo(uint32_t v) const { return (v >> idx_bits) & ((1u << lo_bits) - 1); }
+    // the final value of the accumulation's gather list: index | window of the group << 27 | sign << 31 (clean under the mask 0x07ffffff)
+    BZK_FRONT_HD uint32_t final_value(uint32_t v, uint32_t lw) const { return (v & ((1u << idx_bits) - 1)) | (lw << 27) | (v & 0x80000000u); }
+    // first bucket (window-major bucket index of the call: lw * half + key) of bin b
+    BZK_FRONT_HD uint32_t first_bucket(uint32_t b, uint32_t half) const { return (b >> hi_bits) * half + ((b & ((1u << hi_bits) - 1)) << lo_bits); }
+    BZK_FRONT_HD size_t table_at(uint32_t tile, uint32_t bin, uint32_t nbins_) const { return (size_t)tile * nbins_ + bin; }
+};
+
+// tiles [t0, t1) of part q (of FRONT_SCAN_PARTS) in the scan pass
+BZK_FRONT_HD inline void front_scan_range(uint32_t n_tiles, uint32_t q, uint32_t& t0, uint32_t& t1) {
+    const uint32_t per = (n_tiles + FRONT_SCAN_PARTS - 1) / FRONT_SCAN_PARTS;
+    t0 = q * per < n_tiles ? q * per : n_tiles;
+    t1 = t0 + per < n_tiles ? t0 + per : n_tiles;
+}
+
+// ---- the bin pass ---------------------------------------------------------------------------------------------------------------
+// bin b holds [lo, hi) = [bin_base[b], bin_base[b + 1]) of the len intermediate pairs.  A range that would leave the array cannot happen (the tables count
+// what the scatter pass wrote); were it to, the bin is taken as empty, so that its buckets still get a start, a zero count, their iota and population key.
+BZK_FRONT_HD inline void front_bin_range(uint32_t lo, uint32_t hi, uint64_t len, uint32_t& base, uint32_t& cnt) {
+    const bool ok = lo <= hi && (uint64_t)hi <= len;
+    base = ok ? lo : 0u;
+    cnt = ok ? hi - lo : 0u;
+}
+// a bin of cnt values is ordered in LDS while it fits `cap` values (the kernel: FRONT_BIN_CAP), and stored through the running cursors otherwise
+BZK_FRONT_HD inline bool front_bin_staged(uint32_t cnt, uint32_t cap) { return cnt <= (cap < FRONT_BIN_CAP ? cap : FRONT_BIN_CAP); }
+// the population key of a bucket of cn values (what msm_count_kernel writes on the sort path)
+BZK_FRONT_HD inline uint32_t front_pop_key(uint32_t cn, uint32_t clamp) { return cn < clamp ? cn : clamp; }
+
+// The one place that decides whether a call's pairs are bucketed by the partition passes, and in which shapes.
+//   n_index   exclusive bound of the base indices the values carry (points, plus group sums where a call has them)
+//   eligible  the call takes the plain window-in-value digits path: no table, no endomorphism form, no de-duplication
+//   alone     no BZK_F_THROUGHPUT hint and not a window range of a split call (independent calls on other contexts are not seen here: measured below)
+//   mode      bzk_ctx::msm_front: 0 = by the measured crossover below, 1 = always the sort, 2 = the partition wherever it can run
+// hi = min(7, c - 5), lo = c - 1 - hi: c = 16 gives 128 bins of 256 buckets per window; 9 <= c <= 17 keeps lo <= FRONT_LO_MAX and >= 16 bins per window
+// (the scan pass takes FRONT_SCAN_BINS bins per workgroup).  The packed intermediate must hold the index beside lo: n_index <= 2^(31 - lo).
+inline FrontPlan msm_front_plan(uint64_t n, uint64_t n_index, int c, int windows, bool eligible, bool alone, int mode) {
+    FrontPlan P;
+    if (!eligible || mode == 1 || c < 9 || c > 17 || windows < 1 || windows > 16 || n == 0 || n > ((uint64_t)1 << 24)) return P;
+    P.hi_bits = (uint32_t)(c - 5) < FRONT_HI_MAX ? (uint32_t)(c - 5) : FRONT_HI_MAX;
+    P.lo_bits = (uint32_t)(c - 1) - P.hi_bits;
+    P.idx_bits = 31 - P.lo_bits < 27 ? 31 - P.lo_bits : 27;  // the final value keeps 27 index bits under the window
+    if (n_index > ((uint64_t)1 << P.idx_bits)) return P;
+    P.n_tiles = (uint32_t)((n + FRONT_TILE - 1) / FRONT_TILE);
+    if (mode == 2) {
+        P.on = true;
+        return P;
+    }
+    // Measured crossover (uniform scalars; profiles/msm_front_partition_ab.json), ms per call sort -> partition:
+    //   resident G1 set, same process, alternating: 2^20 points (c = 16)  3.41 -> 3.26     2^21  6.43 -> 6.22     2^22  12.18 -> 11.90 (bins beyond
+    //     FRONT_BIN_CAP: the unstaged bin pass, still ahead);
+    //   2^20 over raw bases (the conversion runs on the side stream beside the passes) 3.38 - 3.48 -> 3.25 - 3.33; G2 2^20 10.38 - 10.46 -> 10.11 - 10.38;
+    //     two independent 2^20 calls in flight on two contexts 3.27 - 3.32 -> 3.10 - 3.18 per call, four 3.09 - 3.11 -> 2.90 - 3.00: all of these count as alone;
+    //   2^18 (c = 14) 1.74 - 1.77 -> 1.94 - 2.01 and 2^19 (c = 15) 2.35 - 2.40 -> 2.68 - 2.78 (medians of three runs each, the shipped kernels): those calls
+    //     run as two window ranges in flight: the sort stays.  The likely reason - beside the other range's accumulation the passes' large workgroups
+    //     (80 KiB / 56 KiB of LDS) wait for a CU where rocPRIM's small ones slip in - is a hypothesis: no trace of those calls was taken;
+    //   2^24: the index does not fit beside lo (n_index > 2^23): the sort stays.
+    // So: c = 16 calls of 2^20 .. 2^22 points that are no window range of a split call and carry no throughput hint.  Smaller window sizes and the prover's
+    // overlapping calls keep the sort.
+    P.on = alone && c >= 16 && n >= ((uint64_t)1 << 20) && n <= ((uint64_t)1 << 22);
+    return P;
+}
+
+}  // namespace bzk

@@ -33,6 +33,7 @@
 #include "bzk_internal.h"
 #include "host_fp64.h"
 #include "msm_policy.cuh"
+#include "msm_front.cuh"
 #include "msm_g2pair_tails.cuh"
 
 namespace bzk {
@@ -118,26 +119,13 @@ static __global__ void __launch_bounds__(256) msm_digits_kernel(const U128* __re
         fe_reduce_once<FrParams>(s);
     }
     const uint32_t half = 1u << (c - 1);
-    const uint32_t mask = (1u << c) - 1;
     // table mode (table_stride != 0): the table holds level j = 2^(c wpl j) P_i, window w = j * wpl + w' feeds bucket set
     // w' with table entry [j][i].  wpl = 1 (full table): every window shares ONE bucket set and [w_begin, w_begin + w_cnt)
     // selects levels; wpl > 1 (folded table): the range selects bucket sets and `w_total` is levels * wpl (windows past
     // the real top digit are zero).  Without a table buckets are per window and the value is the base index
     const bool folded = table_stride && table_wpl > 1;
     const uint32_t nb = (table_stride && !folded) ? half : (uint32_t)w_cnt * half;  // sentinel key (sorted behind every bucket)
-    uint64_t buf = 0;
-    int cnt = 0, w = 0;
-    uint32_t carry = 0;
-    auto emit = [&](uint32_t raw) {
-        uint32_t d = raw + carry;
-        uint32_t neg = 0;
-        if (d > half) {
-            d = (1u << c) - d;
-            neg = 1;
-            carry = 1;
-        } else {
-            carry = 0;
-        }
+    msm_signed_digits(s.l, c, w_total, [&](int w, uint32_t d, uint32_t neg) {  // the recoding itself: msm_front.cuh, shared with the partition front
         if (folded) {
             const int lvl = w / table_wpl, ws = w % table_wpl;
             if (ws >= w_begin && ws < w_begin + w_cnt) {
@@ -163,22 +151,7 @@ static __global__ void __launch_bounds__(256) msm_digits_kernel(const U128* __re
                 vals[o] = (rep ? rep[i] : (uint32_t)i) | (neg << 31);
             }
         }
-        ++w;
-    };
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        buf |= (uint64_t)s.l[j] << cnt;
-        cnt += 32;
-        while (cnt >= c && w < w_total) {
-            emit((uint32_t)buf & mask);
-            buf >>= c;
-            cnt -= c;
-        }
-    }
-    while (w < w_total) {
-        emit((uint32_t)buf & mask);
-        buf >>= c;
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -333,8 +306,232 @@ static __global__ void __launch_bounds__(256) msm_count_kernel(const uint32_t* _
 // 16 k-pair tile with LDS cursors, then one workgroup per bin producing the bucket boundaries directly.  Measured on the c = 16
 // sizes: 0.56 ms against 0.47 ms at 2^20 points, 3.1 against 1.7 ms at 2^22, 12.5 against 6.7 ms at 2^24
 // (profiles/r02_run6_psort_ab.txt) - the tile scatter leaves 32-byte runs per bin (uncoalesced 4-byte stores) where onesweep
-// orders a tile in LDS before it writes.  Slower: gone.
+// orders a tile in LDS before it writes.  Slower: gone.  (The partition front of section 3d below is a different design: it writes no pair array at all.)
 // ------------------------------------------------------------------------------------------------
+
+// ------------------------------------------------------------------------------------------------
+// 3d. the partition front: the pairs of a plain window-in-value call bucketed by two partition passes instead of the radix sort.
+// No key array and no unsorted value array exist: the scalars are recoded on the fly, twice.
+//   msm_digits         (histogram) one workgroup per tile of FRONT_TILE scalars: LDS histogram over the (window, hi) bins -> tile_hist[tile][bin];
+//                      zero digits are counted nowhere and never written
+//   msm_front_scan     per bin, over the tiles: tile_off[tile][bin] = the tile's offset inside the bin, bin_total[bin]
+//   msm_front_scatter  per tile, FRONT_GW windows at a time: every workgroup scans bin_total into the bins' bases (2 048 words at most; workgroup 0 leaves
+//                      them, and the number of non-zero pairs behind them, in bin_base[]), ranks each pair inside its (window, hi) with an LDS cursor, stages
+//                      the tile in LDS in bin order and stores each bin's run contiguously: one packed word per pair (FrontPlan::pack)
+//   msm_front_bins     one workgroup per bin: LDS histogram over the bin's 2^lo buckets, scan, then for EVERY bucket of the bin - empty ones included, so
+//                      nothing is filled beforehand - start / count / iota / the clamped population key (what msm_offsets + msm_count wrote), and the values in
+//                      bucket order (staged in LDS while the bin fits FRONT_BIN_CAP, stored through the running cursors otherwise: both sweeps walk the bin in
+//                      strides of the workgroup, so any population is served - an all-equal scalar vector puts a whole window into one bin)
+// Order inside a bucket follows the LDS atomics, not the base index: the bucket sums are the same group elements.
+// This is not the round-2 partition of 3c: that one partitioned MATERIALISED pairs and scattered them with 4-byte stores; here the tile is ordered in LDS
+// before it is written and the boundaries come out of the bin pass.  Shapes and the decision sort / partition: msm_front_plan (msm_front.cuh).
+// ------------------------------------------------------------------------------------------------
+static __device__ __forceinline__ Fr msm_load_canonical(const U128* __restrict__ scalars, uint64_t i, int mont) {
+    Fr s;
+    const U128 a = scalars[2 * i], b = scalars[2 * i + 1];
+    s.l[0] = a.x; s.l[1] = a.y; s.l[2] = a.z; s.l[3] = a.w;
+    s.l[4] = b.x; s.l[5] = b.y; s.l[6] = b.z; s.l[7] = b.w;
+    if (mont) {
+        s = fe_from_mont<FrParams>(s);
+    } else {  // see msm_digits_kernel
+        fe_reduce_once<FrParams>(s);
+        fe_reduce_once<FrParams>(s);
+    }
+    return s;
+}
+// exclusive scan of in[0, n) into out[0, n) (both in LDS; they may be the same array), every lane of the workgroup calls it; returns the total.
+// Each lane owns ceil(n / THREADS) consecutive entries; wave_tmp holds THREADS / 64 words.
+template <uint32_t THREADS>
+static __device__ __forceinline__ uint32_t front_block_excl_scan(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* wave_tmp) {
+    const uint32_t per = (n + THREADS - 1) / THREADS;
+    const uint32_t k0 = min(n, threadIdx.x * per), k1 = min(n, k0 + per);
+    uint32_t s = 0;
+    for (uint32_t k = k0; k < k1; ++k) s += in[k];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t inc = s;
+#pragma unroll
+    for (uint32_t off = 1; off < 64; off <<= 1) {
+        const uint32_t t = __shfl_up(inc, off, 64);
+        if (lane >= off) inc += t;
+    }
+    if (lane == 63) wave_tmp[wave] = inc;
+    __syncthreads();  // also: every lane has read its entries of `in` before any lane writes `out`
+    uint32_t pre = 0, tot = 0;
+    for (uint32_t w = 0; w < THREADS / 64; ++w) {
+        const uint32_t x = wave_tmp[w];
+        if (w < wave) pre += x;
+        tot += x;
+    }
+    uint32_t run = pre + inc - s;
+    for (uint32_t k = k0; k < k1; ++k) {
+        const uint32_t x = in[k];
+        out[k] = run;
+        run += x;
+    }
+    __syncthreads();
+    return tot;
+}
+
+static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_hist_kernel(const U128* __restrict__ scalars, uint64_t n, int mont, int c, int w_total, int w_begin,
+                                                                              int w_cnt, FrontPlan P, uint32_t* __restrict__ tile_hist) {
+    __shared__ uint32_t h[16u << FRONT_HI_MAX];
+    const uint32_t nb = P.nbins((uint32_t)w_cnt), tile = blockIdx.x;
+    for (uint32_t b = threadIdx.x; b < nb; b += FRONT_THREADS) h[b] = 0;
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t j = 0; j < FRONT_TILE / FRONT_THREADS; ++j) {
+        const uint64_t i = (uint64_t)tile * FRONT_TILE + j * FRONT_THREADS + threadIdx.x;
+        if (i >= n) break;
+        const Fr s = msm_load_canonical(scalars, i, mont);
+        msm_signed_digits(s.l, c, w_total, [&](int w, uint32_t d, uint32_t) {
+            if (d && w >= w_begin && w < w_begin + w_cnt) atomicAdd(&h[P.bin_of((uint32_t)(w - w_begin), d - 1)], 1u);
+        });
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < nb; b += FRONT_THREADS) tile_hist[P.table_at(tile, b, nb)] = h[b];
+}
+
+// FRONT_SCAN_BINS bins per workgroup; lane (bin, q) walks the tiles of part q (front_scan_range): sums, the parts' prefix through LDS, then the offsets
+static __global__ void __launch_bounds__(FRONT_SCAN_BINS * FRONT_SCAN_PARTS) msm_front_scan_kernel(const uint32_t* __restrict__ tile_hist, uint32_t n_tiles, uint32_t nb,
+                                                                                                    FrontPlan P, uint32_t* __restrict__ tile_off,
+                                                                                                    uint32_t* __restrict__ bin_total) {
+    __shared__ uint32_t sums[FRONT_SCAN_PARTS][FRONT_SCAN_BINS];
+    const uint32_t bl = threadIdx.x % FRONT_SCAN_BINS, q = threadIdx.x / FRONT_SCAN_BINS;
+    const uint32_t b = blockIdx.x * FRONT_SCAN_BINS + bl;  // nb is a multiple of FRONT_SCAN_BINS (>= 16 bins per window)
+    uint32_t t0, t1;
+    front_scan_range(n_tiles, q, t0, t1);
+    uint32_t s = 0;
+    if (b < nb)
+        for (uint32_t t = t0; t < t1; ++t) s += tile_hist[P.table_at(t, b, nb)];
+    sums[q][bl] = s;
+    __syncthreads();
+    if (b >= nb) return;
+    uint32_t run = 0;
+    for (uint32_t k = 0; k < q; ++k) run += sums[k][bl];
+    for (uint32_t t = t0; t < t1; ++t) {
+        const uint32_t x = tile_hist[P.table_at(t, b, nb)];
+        tile_off[P.table_at(t, b, nb)] = run;
+        run += x;
+    }
+    if (q == FRONT_SCAN_PARTS - 1) bin_total[b] = run;
+}
+
+static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_scatter_kernel(const U128* __restrict__ scalars, uint64_t n, int mont, int c, int w_total, int w_begin,
+                                                                                 int w_cnt, FrontPlan P,
+                                                                                 const uint32_t* __restrict__ tile_hist, const uint32_t* __restrict__ tile_off,
+                                                                                 const uint32_t* __restrict__ bin_total, uint64_t len, uint32_t* __restrict__ bin_base,
+                                                                                 uint32_t* __restrict__ inter) {
+    constexpr uint32_t PER = FRONT_TILE / FRONT_THREADS, STAGE = FRONT_TILE * FRONT_GW, GB = FRONT_GW << FRONT_HI_MAX;
+    __shared__ uint32_t stage[STAGE];
+    __shared__ uint32_t bbase[16u << FRONT_HI_MAX];
+    __shared__ uint32_t cnt_s[GB], tbs_s[GB], cur_s[GB], toff_s[GB];
+    __shared__ uint32_t wave_tmp[FRONT_THREADS / 64];
+    const uint32_t nb = P.nbins((uint32_t)w_cnt), tile = blockIdx.x;
+    for (uint32_t b = threadIdx.x; b < nb; b += FRONT_THREADS) bbase[b] = bin_total[b];
+    __syncthreads();
+    const uint32_t total = front_block_excl_scan<FRONT_THREADS>(bbase, bbase, nb, wave_tmp);
+    if (tile == 0) {  // for the bin pass: bin b holds [bin_base[b], bin_base[b + 1])
+        for (uint32_t b = threadIdx.x; b < nb; b += FRONT_THREADS) bin_base[b] = bbase[b];
+        if (threadIdx.x == 0) bin_base[nb] = total;
+    }
+    uint32_t sl[PER][8], idx[PER];
+    bool have[PER];
+#pragma unroll
+    for (uint32_t j = 0; j < PER; ++j) {
+        const uint64_t i = (uint64_t)tile * FRONT_TILE + j * FRONT_THREADS + threadIdx.x;
+        have[j] = i < n;
+        idx[j] = 0;
+        if (have[j]) {
+            const Fr s = msm_load_canonical(scalars, i, mont);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sl[j][k] = s.l[k];
+            idx[j] = (uint32_t)i;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sl[j][k] = 0;
+        }
+    }
+#pragma unroll 1
+    for (uint32_t g0 = 0; g0 < (uint32_t)w_cnt; g0 += FRONT_GW) {
+        const uint32_t gw = min(FRONT_GW, (uint32_t)w_cnt - g0), nbl = gw << P.hi_bits, b0 = g0 << P.hi_bits;
+        for (uint32_t b = threadIdx.x; b < nbl; b += FRONT_THREADS) {
+            cnt_s[b] = tile_hist[P.table_at(tile, b0 + b, nb)];
+            toff_s[b] = tile_off[P.table_at(tile, b0 + b, nb)];
+        }
+        __syncthreads();
+        front_block_excl_scan<FRONT_THREADS>(cnt_s, tbs_s, nbl, wave_tmp);
+        for (uint32_t b = threadIdx.x; b < nbl; b += FRONT_THREADS) cur_s[b] = tbs_s[b];
+        __syncthreads();
+#pragma unroll
+        for (uint32_t j = 0; j < PER; ++j) {
+            if (!have[j]) continue;
+            msm_signed_digits(sl[j], c, w_total, [&](int w, uint32_t d, uint32_t neg) {
+                const int lw = w - w_begin - (int)g0;  // window inside this group of FRONT_GW
+                if (d && lw >= 0 && lw < (int)gw) {
+                    const uint32_t pos = atomicAdd(&cur_s[P.bin_of((uint32_t)lw, d - 1)], 1u);
+                    if (pos < STAGE) stage[pos] = P.pack(idx[j], d - 1, neg);
+                }
+            });
+        }
+        __syncthreads();
+        // 32 lanes per bin: the bin's run of this tile leaves as one contiguous store
+        for (uint32_t b = threadIdx.x >> 5; b < nbl; b += FRONT_THREADS / 32) {
+            const uint32_t cn = cnt_s[b], src = tbs_s[b];
+            const uint64_t dst = (uint64_t)bbase[b0 + b] + toff_s[b];
+            for (uint32_t e = threadIdx.x & 31u; e < cn; e += 32)
+                if (dst + e < len && src + e < STAGE) inter[dst + e] = stage[src + e];
+        }
+        __syncthreads();
+    }
+}
+
+static __global__ void __launch_bounds__(FRONT_BIN_THREADS) msm_front_bins_kernel(const uint32_t* __restrict__ inter, const uint32_t* __restrict__ bin_base, FrontPlan P,
+                                                                                  uint32_t half, uint64_t len, uint32_t nbk, uint32_t clamp,
+                                                                                  uint32_t* __restrict__ vals_s, uint32_t* __restrict__ start,
+                                                                                  uint32_t* __restrict__ count, uint32_t* __restrict__ iota,
+                                                                                  uint32_t* __restrict__ ckey) {
+    __shared__ uint32_t stage[FRONT_BIN_CAP];
+    __shared__ uint32_t h[1u << FRONT_LO_MAX], cur[1u << FRONT_LO_MAX];
+    __shared__ uint32_t wave_tmp[FRONT_BIN_THREADS / 64];
+    const uint32_t b = blockIdx.x, nbu = 1u << P.lo_bits, lw = b >> P.hi_bits;
+    uint32_t base, cnt;
+    front_bin_range(bin_base[b], bin_base[b + 1], len, base, cnt);  // out of range (cannot happen): an empty bin, its buckets still written
+    const uint32_t g0 = P.first_bucket(b, half);
+    for (uint32_t k = threadIdx.x; k < nbu; k += FRONT_BIN_THREADS) h[k] = 0;
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < cnt; e += FRONT_BIN_THREADS) atomicAdd(&h[P.packed_lo(inter[base + e])], 1u);
+    __syncthreads();
+    front_block_excl_scan<FRONT_BIN_THREADS>(h, cur, nbu, wave_tmp);
+    for (uint32_t k = threadIdx.x; k < nbu; k += FRONT_BIN_THREADS) {
+        const uint32_t g = g0 + k, cn = h[k];
+        if (g < nbk) {
+            start[g] = base + cur[k];
+            count[g] = cn;
+            iota[g] = g;
+            ckey[g] = front_pop_key(cn, clamp);
+        }
+    }
+    __syncthreads();
+    const bool staged = front_bin_staged(cnt, FRONT_BIN_CAP);
+    // the bin arrives in tile order, i.e. by ascending base index up to a tile: a barrier per stride keeps that order inside every bucket up to the stride, so
+    // the lanes of an accumulating wave still walk the base array together (without it the waves drift apart, the order is lost and the gathers of
+    // msm_accumulate miss the L2 more often: 2.22 -> 2.30 ms at 2^20 points)
+    for (uint32_t e0 = 0; e0 < cnt; e0 += FRONT_BIN_THREADS) {
+        const uint32_t e = e0 + threadIdx.x;
+        if (e < cnt) {
+            const uint32_t v = inter[base + e];
+            const uint32_t pos = atomicAdd(&cur[P.packed_lo(v)], 1u);
+            const uint32_t fv = P.final_value(v, lw);
+            if (pos < cnt) {
+                if (staged) stage[pos] = fv;
+                else vals_s[base + pos] = fv;
+            }
+        }
+        __syncthreads();
+    }
+    if (!staged) return;
+    for (uint32_t e = threadIdx.x; e < cnt; e += FRONT_BIN_THREADS) vals_s[base + e] = stage[e];
+}
 
 // ------------------------------------------------------------------------------------------------
 // 4b. base conversion to the policy's internal form (G1: 14 x 28-bit limbs); one pass per call
@@ -1574,32 +1771,36 @@ struct BucketArrays {
     Pt* partial;
     Pt* wide = nullptr;  // chunk sums of giant buckets (msm_fold_wide_kernel): msm_fold_wide_cap(capacity of `partial`) points, or null = one-level fold
 };
+static bool msm_small_pop(uint64_t len, uint32_t nb) { return len / nb <= 64; }  // the clamp of the population sort's keys (msm_count_kernel)
 template <class C>
 static int32_t bucket_accumulate(bzk_ctx* ctx, const void* bases, const uint32_t* keys_s, const uint32_t* vals_s, uint64_t len, uint32_t nb,
                                  uint32_t seg, const BucketArrays<typename C::Pt>& A, typename C::Pt* buckets, void* tmp_buf, size_t tmp,
                                  bool group_sums = false, uint32_t wiv_half = 0, const void* bases2 = nullptr, uint32_t n_split = 0xffffffffu,
-                                 uint32_t ibits = 31, uint32_t stride1 = 0, uint32_t stride2 = 0, HeavyScope* heavy = nullptr) {
-    // start[] and count[] are taken from the workspace back to back: one fill covers both
-    if ((const char*)A.count > (const char*)A.start && (size_t)((const char*)A.count - (const char*)A.start) <= (size_t)nb * 4 + 256) {
-        BZK_HIP(ctx, hipMemsetAsync(A.start, 0, (size_t)((const char*)A.count - (const char*)A.start) + (size_t)nb * 4, ctx->stream));
-    } else {
-        BZK_HIP(ctx, hipMemsetAsync(A.start, 0, (size_t)nb * 4, ctx->stream));
-        BZK_HIP(ctx, hipMemsetAsync(A.count, 0, (size_t)nb * 4, ctx->stream));
-    }
+                                 uint32_t ibits = 31, uint32_t stride1 = 0, uint32_t stride2 = 0, HeavyScope* heavy = nullptr, bool pre_bucketed = false) {
     const uint32_t vmask = wiv_half ? 0x07ffffffu : 0x7fffffffu;
-    if (wiv_half) {
-        BZK_LAUNCH(ctx, "msm_offsets", msm_offsets_wiv_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, keys_s, vals_s, len, wiv_half,
-                   A.start, A.count);
-    } else {
-        BZK_LAUNCH(ctx, "msm_offsets", msm_offsets_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, keys_s, len, nb, A.start, A.count);
-    }
-    // counts, identity permutation and the clamped population keys in one pass: A.ntask holds the keys until msm_ntask overwrites it,
-    // A.tbase receives the (unused) sorted keys
     // one radix pass over 8-bit keys while the mean population is small, two over 16-bit keys otherwise (msm_count_kernel)
-    const bool small_pop = len / nb <= 64;
+    const bool small_pop = msm_small_pop(len, nb);
     const uint32_t pop_clamp = small_pop ? 255u : 65535u;
     const int pop_bits = small_pop ? 8 : 16;
-    BZK_LAUNCH(ctx, "msm_count", msm_count_kernel, dim3((nb + 255) / 256), dim3(256), 0, A.start, A.count, A.iota, A.ntask, nb, pop_clamp);
+    // pre_bucketed: the partition front (section 3d) has written start / count / iota / the population keys (in A.ntask) and vals_s already
+    if (!pre_bucketed) {
+        // start[] and count[] are taken from the workspace back to back: one fill covers both
+        if ((const char*)A.count > (const char*)A.start && (size_t)((const char*)A.count - (const char*)A.start) <= (size_t)nb * 4 + 256) {
+            BZK_HIP(ctx, hipMemsetAsync(A.start, 0, (size_t)((const char*)A.count - (const char*)A.start) + (size_t)nb * 4, ctx->stream));
+        } else {
+            BZK_HIP(ctx, hipMemsetAsync(A.start, 0, (size_t)nb * 4, ctx->stream));
+            BZK_HIP(ctx, hipMemsetAsync(A.count, 0, (size_t)nb * 4, ctx->stream));
+        }
+        if (wiv_half) {
+            BZK_LAUNCH(ctx, "msm_offsets", msm_offsets_wiv_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, keys_s, vals_s, len, wiv_half,
+                       A.start, A.count);
+        } else {
+            BZK_LAUNCH(ctx, "msm_offsets", msm_offsets_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, keys_s, len, nb, A.start, A.count);
+        }
+        // counts, identity permutation and the clamped population keys in one pass: A.ntask holds the keys until msm_ntask overwrites it,
+        // A.tbase receives the (unused) sorted keys
+        BZK_LAUNCH(ctx, "msm_count", msm_count_kernel, dim3((nb + 255) / 256), dim3(256), 0, A.start, A.count, A.iota, A.ntask, nb, pop_clamp);
+    }
     {
         ProfScope ps(ctx, "msm_sort_buckets");
         size_t t = tmp;
@@ -1883,6 +2084,10 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
     // windows are processed in groups so that one group's pair list stays below 2^30 entries
     int group = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)(w_end - w_begin), ((uint64_t)1 << 30) / n));
     if (table || E > 1) group = w_end - w_begin;  // shared bucket sets: all requested windows in one pass
+    // the partition front (section 3d) buckets window-in-value pairs, at most 16 windows at a time: where it takes the call, the groups are cut to that
+    const bool front_eligible = !wiv_off && !table && E == 1 && !dedup && (uint64_t)n + m_max < ((uint64_t)1 << 27);
+    const bool front_alone = !(flags & BZK_F_THROUGHPUT) && !ctx->is_part && !ctx->split_active;
+    if (group > 16 && msm_front_plan(n, (uint64_t)n + m_max, c, 16, front_eligible, front_alone, ctx->msm_front).on) group = 16;
     const uint64_t len_max = (uint64_t)group * n * (folded ? (uint64_t)levels : (uint64_t)E);
     if (len_max >= ((uint64_t)1 << 31)) return BZK_E_ARG;
     const uint32_t nb_max = (table && !folded) ? half : (uint32_t)group * half;
@@ -1939,8 +2144,12 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
     const size_t n_sets_max = (table && !folded) ? 1 : (size_t)group;
     const size_t n_terms = (size_t)c / 2 + 1;  // per bucket set: ceil((c - 1) / 2) digit terms + the plain sum (msm_bitsum_quad_kernel)
     // every buffer of the call, declared once; what a configuration does not take stays null
+    const bool wiv = !wiv_off && !table && group <= 16 && (uint64_t)n + m_max < ((uint64_t)1 << 27);
+    // partition front (section 3d) or the radix sort: decided in one place for every group of this call
+    const FrontPlan front = msm_front_plan(n, (uint64_t)n + m_max, c, group, wiv && front_eligible, front_alone, ctx->msm_front);
     WsLayout ws("msm_run");
-    uint32_t *keys, *vals, *keys_s, *vals_s;
+    uint32_t *keys = nullptr, *vals, *keys_s = nullptr, *vals_s;
+    uint32_t *f_hist = nullptr, *f_off = nullptr, *f_total = nullptr, *f_base = nullptr;
     BucketArrays<Pt> BA;
     Pt *buckets, *chunk_out, *chunk_tot = nullptr, *wpart, *rc_buf = nullptr;
     StdPt *win_out, *terms_out = nullptr;
@@ -1950,7 +2159,8 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
     U128* scal2 = nullptr;
     typename C::Fld* pref = nullptr;
     char* tmp_buf;
-    ws.take(keys, len_max); ws.take(vals, len_max); ws.take(keys_s, len_max); ws.take(vals_s, len_max);
+    if (!front.on) { ws.take(keys, len_max); ws.take(keys_s, len_max); }  // the partition front writes no key array
+    ws.take(vals, len_max); ws.take(vals_s, len_max);
     ws.take(BA.start, nb_alloc); ws.take(BA.count, nb_alloc); ws.take(BA.count_s, nb_alloc); ws.take(BA.iota, nb_alloc);
     ws.take(BA.order, nb_alloc); ws.take(BA.ntask, nb_alloc); ws.take(BA.tbase, nb_alloc);
     ws.take(BA.partial, t_cap);  // per-task partial sums (multi-task buckets only)
@@ -1969,6 +2179,10 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
         ws.take(hkey, n); ws.take(hkey_s, n); ws.take(didx, n); ws.take(didx_s, n); ws.take(head, n); ws.take(mhead, n);
         ws.take(gid_ex, n); ws.take(mid_ex, n); ws.take(key2, n); ws.take(rep, n); ws.take(gof, n);
         ws.take(scal2, 2 * n); ws.take(pref, m_max);
+    }
+    if (front.on) {
+        const size_t nbins = front.nbins((uint32_t)group);
+        ws.take(f_hist, (size_t)front.n_tiles * nbins); ws.take(f_off, (size_t)front.n_tiles * nbins); ws.take(f_total, nbins); ws.take(f_base, nbins + 1);
     }
     ws.take(tmp_buf, tmp);
     BZK_TRY(ws.commit(ctx));
@@ -2068,14 +2282,24 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
     }
 
     const int mont = (flags & BZK_F_CANONICAL) ? 0 : 1;
-    const bool wiv = !wiv_off && !table && group <= 16 && (uint64_t)n + m_max < ((uint64_t)1 << 27);
     std::vector<StdPt> wsum((size_t)(w_end - w_begin) * (bitsum ? n_terms : 1));  // window sums, or (section 6b) the terms of every bucket set
     for (int wb = w_begin; wb < w_end; wb += group) {
         const int wc = std::min(group, w_end - wb);
         const uint64_t len = (uint64_t)wc * n_eff * (folded ? (uint64_t)levels : (uint64_t)E);
         const uint32_t nb = (table && !folded) ? half : (uint32_t)wc * half;
         const int n_red_win = (table && !folded) ? 1 : wc;  // bucket sets to reduce
-        if (E > 1) {
+        if (front.on) {
+            // histogram, scan, scatter, bin pass: vals_s, start, count, iota and the population keys come out of the last one (`vals` holds the packed intermediate)
+            const uint32_t nbins = front.nbins((uint32_t)wc);
+            BZK_LAUNCH(ctx, "msm_digits", msm_front_hist_kernel, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total, wb, wc,
+                       front, f_hist);
+            BZK_LAUNCH(ctx, "msm_front_scan", msm_front_scan_kernel, dim3(nbins / FRONT_SCAN_BINS), dim3(FRONT_SCAN_BINS * FRONT_SCAN_PARTS), 0, (const uint32_t*)f_hist,
+                       front.n_tiles, nbins, front, f_off, f_total);
+            BZK_LAUNCH(ctx, "msm_front_scatter", msm_front_scatter_kernel, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total,
+                       wb, wc, front, (const uint32_t*)f_hist, (const uint32_t*)f_off, (const uint32_t*)f_total, len, f_base, vals);
+            BZK_LAUNCH(ctx, "msm_front_bins", msm_front_bins_kernel, dim3(nbins), dim3(FRONT_BIN_THREADS), 0, (const uint32_t*)vals, (const uint32_t*)f_base, front,
+                       half, len, nb, msm_small_pop(len, nb) ? 255u : 65535u, vals_s, BA.start, BA.count, BA.iota, BA.ntask);
+        } else if (E > 1) {
             BZK_LAUNCH(ctx, "msm_digits_endo", (msm_digits_endo_kernel<C::ENDO>), dim3((unsigned)((n_eff + 255) / 256)), dim3(256), 0, (const U128*)scal_eff,
                        n_eff, mont, c, w_total, ibits, (const uint32_t*)(dedup ? rep : nullptr), keys, vals);
         } else {
@@ -2083,7 +2307,7 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
                        mont, c, folded ? levels * table->wpl : w_total, wb, wc, (uint32_t)(table ? table->n : 0), table ? table->wpl : 1,
                        (const uint32_t*)(dedup ? rep : nullptr), wiv ? 1 : 0, keys, vals);
         }
-        {
+        if (!front.on) {
             ProfScope ps(ctx, "msm_sort_pairs");
             size_t t = tmp;
             hipError_t e = rocprim::radix_sort_pairs(tmp_buf, t, keys, keys_s, vals, vals_s, (size_t)len, 0, bits_for(wiv ? half : nb), ctx->stream);
@@ -2092,7 +2316,7 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
         aux.join();
         HeavyScope heavy(ctx);  // accumulation, folds, bucket reduction; left before the window sums (latency-bound trees of a few workgroups)
         BZK_TRY(bucket_accumulate<C>(ctx, bases, keys_s, vals_s, len, nb, seg, BA, buckets, tmp_buf, tmp, false, wiv ? half : 0u, sums_aff, n_split,
-                                     (uint32_t)ibits, E > 1 ? (uint32_t)prep->n : 0u, E > 1 ? m_max : 0u, &heavy));
+                                     (uint32_t)ibits, E > 1 ? (uint32_t)prep->n : 0u, E > 1 ? m_max : 0u, &heavy, front.on));
         if constexpr (!C::PARK_REDUCE) {
             if (bitsum) {
                 G1X28* const rows = (G1X28*)rc_buf;
@@ -2222,6 +2446,9 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
 // for whole-MSM calls over a resident base set that are not flagged BZK_F_THROUGHPUT (those overlap with other calls already) or BZK_F_DEDUP.
 // Same result bytes: the same window terms enter the same Horner.  env (read when a context is created) BZK_MSM_SPLIT = 1 (off) | 2 | 3 | 4,
 // BZK_MSM_SPLIT_MIN_LOG (default 18), BZK_MSM_SPLIT_PRIO = 1: the children's streams at the highest priority (A/B).
+// The partition front (section 3d) is not decided here: every range is an msm_run of its own, which asks msm_front_plan with alone = false while
+// bzk_ctx::is_part (a child context) or bzk_ctx::split_active (the parent, for the range it runs itself) is set - so by default a range keeps the sort, and
+// BZK_MSM_FRONT=partition reaches the ranges through the same call.  Whoever adds a third way to run a range must set one of the two flags.
 template <class C>
 static int msm_split_parts(const bzk_ctx* ctx, uint64_t n, uint32_t flags, const MsmBases* prep) {
     // measured (profiles/r06_run20..23): two ranges gain 13 - 16 % at 2^18 and 2^19 points, nothing (+- 1 %) from 2^20 up - there the ranges' accumulations

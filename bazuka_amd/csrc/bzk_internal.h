@@ -188,6 +188,24 @@ struct DpSoA {
 int32_t mpn_deposit_verify_run(bzk_ctx* ctx, const DpSoA& t, uint64_t n, uint8_t* ok, uint8_t* xy_out);
 // eddsa.hip: the same per-lane Ed25519 code on the host, for record i
 uint8_t mpn_deposit_sig_host(const DpSoA& t, uint64_t i);
+// eddsa.hip: the Ed25519 verifier's fixed-base table on the device (built on the context's first use)
+int32_t ed25519_table_dev(bzk_ctx* ctx, const uint32_t** out);
+// verify.hip: the batched Groth16 verifier as a stage of another call.  g16v_declare adds the verifier's buffers for up to n proofs per launch
+// round to the CALLER's layout; after the caller's commit, g16v_enqueue runs n proofs of one valid prepared key (device pointers, stream order;
+// `up` must outlive the work; sync: wait for it).  g16v_host_run: the same per-proof functions on host threads (every verdict 0 for an invalid key).
+namespace hp {
+struct KeyHost;
+struct KeyUpload;
+}  // namespace hp
+struct G16vBufs {
+    uint32_t *slab = nullptr, *flags = nullptr, *sc = nullptr;
+    uint8_t* dkey = nullptr;
+    uint32_t stride = 0;
+};
+void g16v_declare(WsLayout& ws, G16vBufs& b, uint32_t n_inputs, uint64_t n, size_t key_bytes);
+int32_t g16v_enqueue(bzk_ctx* ctx, const G16vBufs& b, const hp::KeyHost& K, const hp::KeyUpload& up, const uint8_t* inputs_dev,
+                     const uint8_t* proofs_dev, uint64_t n, uint8_t* ok_dev, bool sync);
+void g16v_host_run(const hp::KeyHost& K, const uint8_t* inputs, const uint8_t* proofs, uint64_t n, uint8_t* ok);
 int32_t ntt_run(bzk_ctx* ctx, void* data_dev, uint32_t log_n, int inverse, int coset);  // ntt.hip
 int32_t ntt_h_chain(bzk_ctx* ctx, void* a, void* b, void* c, uint32_t log_m);              // ntt.hip: the h polynomial's 7 transforms, fused
 // msm_g1.hip / msm_g2.hip: windows [w_begin, w_end) (w_end < 0: all) of an MSM over a resident base set (or raw bases when `bases` is

@@ -377,7 +377,7 @@ int32_t mpn_withdraw_verify_run(bzk_ctx* ctx, const WdSoA& t, uint64_t n, uint8_
     return BZK_OK;
 }
 
-static int32_t ed25519_table_dev(bzk_ctx* ctx, const uint32_t** out) {
+int32_t ed25519_table_dev(bzk_ctx* ctx, const uint32_t** out) {
     if (!ctx->ed25519_tab) {
         void* d = nullptr;
         BZK_HIP(ctx, hipMalloc(&d, ed25519::BASE_TAB_WORDS * 4));

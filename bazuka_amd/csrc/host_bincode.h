@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "bzk_l1.h"
+#include "bzk_updates.h"
 #include "host_mpn_types.h"
 
 namespace bzk {
@@ -668,6 +669,120 @@ inline void skip_contract_update(BinReader& r, uint32_t flags) {
     r.u64("ContractUpdate.reward");
     skip_zk_proof(r);
 }
+// ---- rd_contract_update: skip_contract_update's recording twin.  Structure only: where the pieces lie, and whether a payment names the update's
+// contract and circuit.  No hashing and no field arithmetic.
+inline bool contract_id_is(BinReader& r, const uint8_t cid[32]) {  // reads a ContractId; true where its scalar's bytes are cid's
+    uint8_t b[32];
+    rd_contract_id(r).to_bytes(b);
+    return r.ok && memcmp(b, cid, 32) == 0;
+}
+inline void rd_update_payment(BinReader& r, uint32_t flags, bool deposit, const uint8_t cid[32], uint32_t circuit_id, size_t rec0, upd::PayRec& p) {
+    const size_t p0 = r.pos;
+    p.off = (uint32_t)(p0 - rec0);
+    p.flags = 0;
+    p.tag_off = p.src_off = p.sig_off = p.pad = 0;
+    skip_string(r);  // memo
+    if (contract_id_is(r, cid)) p.flags |= upd::PAY_CONTRACT;
+    if (r.u32("circuit id of the payment") == circuit_id && r.ok) p.flags |= upd::PAY_CIRCUIT;
+    p.cd_off = (uint32_t)(r.pos - p0);
+    r.bytes(32, "calldata");
+    if (r.u64("ed25519 public key length") != 32) r.fail("ed25519 public key length");
+    p.src_off = (uint32_t)(r.pos - p0);
+    r.bytes(32, "ed25519 public key");  // src of a deposit, dst of a withdrawal
+    p.amt_off = (uint32_t)(r.pos - p0);
+    rd_money(r);
+    p.fee_off = (uint32_t)(r.pos - p0);
+    rd_money(r);
+    if (deposit) {
+        r.u32("nonce");
+        p.tag_off = (uint32_t)(r.pos - p0);
+        const uint8_t some = r.u8("Option<Signature> tag");
+        if (r.ok && some > 1) r.fail("Option tag");
+        if (r.ok && some) {
+            if (flags & BZK_WORK_SIG_LEN_PREFIXED)
+                if (r.u64("ed25519 signature length") != 64) r.fail("ed25519 signature length");
+            p.sig_off = (uint32_t)(r.pos - p0);
+            r.bytes(64, "ed25519 signature");
+            p.flags |= upd::PAY_HAS_SIG;
+        }
+    }
+    p.len = (uint32_t)(r.pos - p0);
+}
+// u: kind, circuit id, payment range and offsets; its payments are appended to pays with upd = index
+inline void rd_contract_update(BinReader& r, uint32_t flags, const uint8_t cid[32], uint32_t index, upd::UpdRec& u, std::vector<upd::PayRec>& pays) {
+    const size_t p0 = r.pos;
+    u = upd::UpdRec();
+    u.at = p0;
+    u.slot = upd::NO_SLOT;
+    u.circuit_id = r.u32("ContractUpdate.circuit_id");
+    u.kind = r.u32("ContractUpdateData tag");
+    if (!r.ok) return;
+    u.pay0 = (uint32_t)pays.size();
+    u.data_off = (uint32_t)(r.pos - p0);
+    if (u.kind == upd::DEPOSIT || u.kind == upd::WITHDRAW) {
+        const bool deposit = u.kind == upd::DEPOSIT;
+        const uint64_t k = r.len(deposit ? 117 : 112, deposit ? "ContractUpdateData::Deposit length" : "ContractUpdateData::Withdraw length");
+        for (uint64_t i = 0; i < k && r.ok; ++i) {
+            upd::PayRec p;
+            p.upd = index;
+            p.slot = (uint32_t)i;
+            rd_update_payment(r, flags, deposit, cid, u.circuit_id, p0, p);
+            if (r.ok) pays.push_back(p);
+        }
+        u.pay_n = (uint32_t)(pays.size() - u.pay0);
+    } else if (u.kind == upd::CALL) {
+        rd_money(r);
+    } else if (u.kind == upd::MINT) {
+        r.u64("Mint.amount");
+    } else {
+        r.fail("ContractUpdateData variant");
+    }
+    u.next_off = (uint32_t)(r.pos - p0);
+    skip_compressed_state(r);
+    u.commit_off = (uint32_t)(r.pos - p0);
+    skip_l1_pub(r);
+    r.u64("ContractUpdate.reward");
+    if (r.u32("ZkProof tag") != 0) r.fail("ZkProof variant (only Groth16 = 0 exists outside cfg(test))");
+    u.proof_off = (uint32_t)(r.pos - p0);
+    r.bytes(upd::PROOF_BYTES, "Groth16Proof");
+    if (r.ok && r.pos - p0 > upd::RECORD_MAX) r.fail("record longer than 1048576 bytes");
+}
+struct UpdParsed {
+    const uint8_t* bytes = nullptr;
+    uint64_t len = 0;
+    std::vector<upd::UpdRec> rec;   // n
+    std::vector<upd::PayRec> pay;   // every payment of the call, in record order
+    uint64_t end(uint64_t i) const { return i + 1 < rec.size() ? rec[i + 1].at : len; }  // where record i ends
+};
+// false with err naming the record when the bytes are not n well-formed ContractUpdate records
+inline bool parse_contract_updates(const uint8_t* bytes, uint64_t len, uint64_t n, uint32_t flags, const uint8_t cid[32], UpdParsed& P, std::string& err) {
+    if (n > len / 495) {  // the shortest record: 4 + 4 + 8 + 40 + 40 + 8 + 4 + 387
+        err = "record " + std::to_string(len / 495) + ": the input ends before it (" + std::to_string(n) + " ContractUpdate records need 495 bytes each)";
+        return false;
+    }
+    P.bytes = bytes;
+    P.len = len;
+    P.rec.resize(n);
+    P.pay.clear();
+    BinReader r(bytes, (size_t)len);
+    for (uint64_t i = 0; i < n && r.ok; ++i) {
+        rd_contract_update(r, flags, cid, (uint32_t)i, P.rec[i], P.pay);
+        if (r.ok && P.pay.size() >= ((uint64_t)1 << 31)) r.fail("more than 2^31 payments in one call");
+        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
+    }
+    if (r.ok && r.pos != len) {
+        r.fail("bytes after the last record");
+        if (n) r.err = "record " + std::to_string(n - 1) + ": " + r.err;
+    }
+    err = r.err;
+    return r.ok;
+}
+// what bzk_l1_tx_updates collects while rd_l1_tx walks an UpdateContract: (transaction, offset in the input, length) of every update of contract cid
+struct UpdSpans {
+    const uint8_t* cid;
+    uint64_t tx = 0;
+    std::vector<uint64_t> out;
+};
 // an Option in the middle of the record that the signature leaves out: [cut_a, cut_b) where it is Some, empty otherwise
 template <class Skip>
 inline void rd_cut_option(BinReader& r, size_t p0, l1::L1Rec& o, const char* what, Skip skip) {
@@ -679,7 +794,7 @@ inline void rd_cut_option(BinReader& r, size_t p0, l1::L1Rec& o, const char* wha
         o.cut_b = (uint32_t)(r.pos - p0);
     }
 }
-inline void rd_l1_tx(BinReader& r, uint32_t flags, bool and_delta, l1::L1Rec& o) {
+inline void rd_l1_tx(BinReader& r, uint32_t flags, bool and_delta, l1::L1Rec& o, UpdSpans* spans = nullptr) {
     const size_t p0 = r.pos;
     o = l1::L1Rec();
     if (rd_option_tag(r, "Option<src> tag")) {
@@ -719,9 +834,13 @@ inline void rd_l1_tx(BinReader& r, uint32_t flags, bool and_delta, l1::L1Rec& o)
         rd_cut_option(r, p0, o, "Option<ZkDataPairs> tag", skip_data_pairs);
         break;
     case 6: {  // UpdateContract { contract_id, updates, delta: Option<ZkDeltaPairs> }
-        rd_contract_id(r);
+        const bool listed = spans ? contract_id_is(r, spans->cid) : (rd_contract_id(r), false);
         const uint64_t k = r.len(495, "UpdateContract updates");
-        for (uint64_t i = 0; i < k && r.ok; ++i) skip_contract_update(r, flags);
+        for (uint64_t i = 0; i < k && r.ok; ++i) {
+            const size_t a = r.pos;
+            skip_contract_update(r, flags);
+            if (listed && r.ok) spans->out.insert(spans->out.end(), {spans->tx, (uint64_t)a, (uint64_t)(r.pos - a)});
+        }
         rd_cut_option(r, p0, o, "Option<ZkDeltaPairs> tag", skip_delta_pairs);
         break;
     }
@@ -750,7 +869,8 @@ struct L1Parsed {
     L1SoA soa() const { return {txs, rec_off.data(), rec.data()}; }
 };
 // and_delta: the records are TransactionAndDelta.  false with err naming the record when the bytes are not n well-formed records
-inline bool parse_l1_txs(const uint8_t* txs, uint64_t len, uint64_t n, bool and_delta, uint32_t flags, L1Parsed& P, std::string& err) {
+inline bool parse_l1_txs(const uint8_t* txs, uint64_t len, uint64_t n, bool and_delta, uint32_t flags, L1Parsed& P, std::string& err,
+                         UpdSpans* spans = nullptr) {
     if (n > len / 29) {  // the shortest record: 1 + 4 + (4 + 8) + 4 + 8 + 4, and a TransactionAndDelta's tag
         err = "record " + std::to_string(len / 29) + ": the input ends before it (" + std::to_string(n) + " Transaction records need 29 bytes each)";
         return false;
@@ -761,7 +881,8 @@ inline bool parse_l1_txs(const uint8_t* txs, uint64_t len, uint64_t n, bool and_
     BinReader r(txs, (size_t)len);
     for (uint64_t i = 0; i < n && r.ok; ++i) {
         P.rec_off[i] = r.pos;
-        rd_l1_tx(r, flags, and_delta, P.rec[i]);
+        if (spans) spans->tx = i;
+        rd_l1_tx(r, flags, and_delta, P.rec[i], spans);
         if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
     }
     if (r.ok) P.rec_off[n] = r.pos;

@@ -2940,3 +2940,81 @@ int32_t bzk_block_bodies_check(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, c
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Wire-form ContractUpdates: bincode(ContractUpdate) records of one contract in, per-update verdict bits, aux data and commitments out
+// (bzk_contract_updates_check); and the parse-only helper that cuts those records out of L1 transactions (bzk_l1_tx_updates).  The parser is
+// host_bincode.h's parse_contract_updates (structure only); everything computed is updates.hip's, on the device or on host threads.
+// ------------------------------------------------------------------------------------------------
+namespace bzk {
+int32_t contract_updates_run(bzk_ctx* ctx, const bzk_contract_desc& c, UpdParsed& P, const uint64_t* count, uint64_t m, uint64_t height0,
+                             const uint8_t state0[32], uint8_t* ok, uint8_t* aux_out, uint8_t* commit_out);  // updates.hip
+}
+
+extern "C" {
+
+int32_t bzk_contract_updates_check(bzk_ctx* ctx, const bzk_contract_desc* c, const uint8_t* updates, uint64_t len, const uint64_t* count, uint64_t m,
+                                   uint64_t height0, const uint8_t state0[32], uint8_t* ok, uint8_t* aux_out, uint8_t* commit_out) {
+    if (m && !count) {
+        g_work_error = "count is NULL with transactions to check";
+        return BZK_E_ARG;
+    }
+    uint64_t n = 0;
+    for (uint64_t j = 0; j < m; ++j) {
+        if (count[j] > len) {  // a record is hundreds of bytes: also keeps the sum from wrapping
+            g_work_error = "the counts name more records than the input can hold";
+            return BZK_E_ARG;
+        }
+        n += count[j];
+    }
+    if (n == 0 && len == 0) return BZK_OK;
+    if (!c || (n && (!updates || !state0 || !ok))) {
+        g_work_error = "a pointer is NULL with records to check";
+        return BZK_E_ARG;
+    }
+    if ((c->n_deposit_fns && !c->deposit_fns) || (c->n_withdraw_fns && !c->withdraw_fns) || (c->n_fns && !c->fns)) {
+        g_work_error = "a function table is NULL with a non-zero count";
+        return BZK_E_ARG;
+    }
+    const bzk_contract_fn* tab[3] = {c->deposit_fns, c->withdraw_fns, c->fns};
+    const uint32_t cnt[3] = {c->n_deposit_fns, c->n_withdraw_fns, c->n_fns};
+    for (int t = 0; t < 3; ++t)
+        for (uint32_t k = 0; k < cnt[t]; ++k) {
+            if (!tab[t][k].vk || tab[t][k].vk_len < 878) {
+                g_work_error = "function " + std::to_string(k) + ": a verifying key is at least 878 bytes";
+                return BZK_E_ARG;
+            }
+            if (t < 2 && tab[t][k].log4_payment_capacity > upd::MAX_CAPACITY) {
+                g_work_error = "function " + std::to_string(k) + ": log4_payment_capacity above 8";
+                return BZK_E_ARG;
+            }
+        }
+    try {
+        UpdParsed P;
+        if (!parse_contract_updates(updates, len, n, g_wire_flags.load(), c->contract_id, P, g_work_error)) return BZK_E_ARG;
+        return contract_updates_run(ctx, *c, P, count, m, height0, state0, ok, aux_out, commit_out);
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+int32_t bzk_l1_tx_updates(const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, const uint8_t contract_id[32], uint64_t* spans_out, uint64_t cap,
+                          uint64_t* n_out) {
+    if (form > BZK_L1_FORM_TX_AND_DELTA || !contract_id || !n_out || (n && !txs) || (cap && !spans_out)) return BZK_E_ARG;
+    *n_out = 0;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        L1Parsed P;
+        UpdSpans S;
+        S.cid = contract_id;
+        if (!parse_l1_txs(txs, len, n, form == BZK_L1_FORM_TX_AND_DELTA, g_wire_flags.load(), P, g_work_error, &S)) return BZK_E_ARG;
+        const uint64_t found = S.out.size() / 3;
+        if (found && cap) memcpy(spans_out, S.out.data(), (size_t)std::min(found, cap) * 24);
+        *n_out = found;
+        return BZK_OK;
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+}  // extern "C"

@@ -371,6 +371,25 @@ static int32_t poseidon_consts_dev(bzk_ctx* ctx, int t, const void** out, int* r
 }
 // the same table for witfill.hip (pass 1 of the deferred witness values hashes with poseidon29_hash too)
 int32_t poseidon_consts_dev_shared(bzk_ctx* ctx, int t, const void** out, int* rf, int* rp) { return poseidon_consts_dev(ctx, t, out, rf, rp); }
+// the same constants in host memory, for the ctx = NULL entries that run poseidon29_hash on host threads (updates.hip); built once per width
+int32_t poseidon_consts_host29(int t, const Fr29** out, int* rf, int* rp) {
+    static std::mutex mu;
+    static std::vector<Fr29> tab[9];
+    if (t < 2 || t > 8) return BZK_E_ARG;
+    const HostParams& P = host_params(t);
+    *rf = P.rf;
+    *rp = P.rp;
+    std::lock_guard<std::mutex> lk(mu);
+    if (tab[t].empty()) {
+        std::vector<Fr> flat;
+        if (!poseidon_optimize(t, P.rf, P.rp, P.rc, P.mds, flat)) return BZK_E_INTERNAL;
+        std::vector<Fr29> f29(flat.size());
+        for (size_t i = 0; i < flat.size(); ++i) f29[i] = fr29::norm(fr29::to29(flat[i]));
+        tab[t].swap(f29);
+    }
+    *out = tab[t].data();
+    return BZK_OK;
+}
 
 
 // ------------------------------------------------------------------------------------------------

@@ -90,6 +90,15 @@ void host_run(const KeyHost& K, const uint8_t* inputs, const uint8_t* proofs, ui
     });
 }
 
+// one round of launches over m <= G16V_ROUND proofs whose inputs, proofs and verdict bytes are device pointers
+int32_t launch_round(bzk_ctx* ctx, const G16vBufs& b, const KeyDev& k, const uint8_t* rin, const uint8_t* rpr, uint32_t m, uint8_t* rok) {
+    const dim3 grid((m + G16V_BLOCK - 1) / G16V_BLOCK), block(G16V_BLOCK);
+    BZK_LAUNCH(ctx, "g16v_prepare", g16v_prepare_kernel, grid, block, 0, k, rin, rpr, m, b.slab, b.stride, b.sc, b.flags);
+    BZK_LAUNCH(ctx, "g16v_miller", g16v_miller_kernel, grid, block, 0, k, m, b.slab, b.stride, b.flags);
+    BZK_LAUNCH(ctx, "g16v_finalexp", g16v_finalexp_kernel, grid, block, 0, k, m, b.slab, b.stride, (const uint32_t*)b.flags, rok);
+    return BZK_OK;
+}
+
 // inputs / proofs / ok: host pointers (staged per round, verdicts read back once) when `staged`, device pointers otherwise
 int32_t device_run(bzk_ctx* ctx, const char* who, const KeyHost& K, const uint8_t* inputs, const uint8_t* proofs, uint64_t n, uint8_t* ok, bool staged) {
     (void)hipSetDevice(ctx->device);
@@ -103,45 +112,59 @@ int32_t device_run(bzk_ctx* ctx, const char* who, const KeyHost& K, const uint8_
     }
     const KeyUpload up(K);   // the tables in the device field
     const uint64_t cap = std::min<uint64_t>(n, G16V_ROUND);
-    const uint32_t stride = (uint32_t)((cap + G16V_BLOCK - 1) / G16V_BLOCK * G16V_BLOCK);
     const size_t in_bytes = (size_t)32 * K.n_inputs;
     WsLayout ws(who);
-    uint32_t *slab, *flags, *sc;
-    uint8_t *dkey, *din = nullptr, *dpr = nullptr, *dok = nullptr;
-    ws.take(slab, (size_t)pairing::slot::COUNT * 14 * stride);
-    ws.take(flags, stride);
-    ws.take(sc, (size_t)8 * K.n_inputs * stride + 1);
-    ws.take(dkey, up.bytes.size());
+    G16vBufs b;
+    uint8_t *din = nullptr, *dpr = nullptr, *dok = nullptr;
+    g16v_declare(ws, b, K.n_inputs, n, up.bytes.size());
     if (staged) {
         ws.take(din, in_bytes * cap + 1);
         ws.take(dpr, (size_t)387 * cap);
         ws.take(dok, n);
     }
     BZK_TRY(ws.commit(ctx));
-    BZK_HIP(ctx, hipMemcpyAsync(dkey, up.bytes.data(), up.bytes.size(), hipMemcpyHostToDevice, ctx->stream));
-    const KeyDev k = up.view(K, dkey);
+    if (!staged) return g16v_enqueue(ctx, b, K, up, inputs, proofs, n, ok, true);
+    BZK_HIP(ctx, hipMemcpyAsync(b.dkey, up.bytes.data(), up.bytes.size(), hipMemcpyHostToDevice, ctx->stream));
+    const KeyDev k = up.view(K, b.dkey);
     for (uint64_t a = 0; a < n; a += G16V_ROUND) {
         const uint32_t m = (uint32_t)std::min<uint64_t>(n - a, G16V_ROUND);
-        const uint8_t *rin = inputs + in_bytes * a, *rpr = proofs + 387 * a;
-        uint8_t* rok = ok + a;
-        if (staged) {
-            if (in_bytes) BZK_HIP(ctx, hipMemcpyAsync(din, rin, in_bytes * m, hipMemcpyHostToDevice, ctx->stream));
-            BZK_HIP(ctx, hipMemcpyAsync(dpr, rpr, (size_t)387 * m, hipMemcpyHostToDevice, ctx->stream));
-            rin = din;
-            rpr = dpr;
-            rok = dok + a;
-        }
-        const dim3 grid((m + G16V_BLOCK - 1) / G16V_BLOCK), block(G16V_BLOCK);
-        BZK_LAUNCH(ctx, "g16v_prepare", g16v_prepare_kernel, grid, block, 0, k, rin, rpr, m, slab, stride, sc, flags);
-        BZK_LAUNCH(ctx, "g16v_miller", g16v_miller_kernel, grid, block, 0, k, m, slab, stride, flags);
-        BZK_LAUNCH(ctx, "g16v_finalexp", g16v_finalexp_kernel, grid, block, 0, k, m, slab, stride, (const uint32_t*)flags, rok);
+        if (in_bytes) BZK_HIP(ctx, hipMemcpyAsync(din, inputs + in_bytes * a, in_bytes * m, hipMemcpyHostToDevice, ctx->stream));
+        BZK_HIP(ctx, hipMemcpyAsync(dpr, proofs + 387 * a, (size_t)387 * m, hipMemcpyHostToDevice, ctx->stream));
+        BZK_TRY(launch_round(ctx, b, k, din, dpr, m, dok + a));
     }
-    if (staged) BZK_HIP(ctx, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
+    BZK_HIP(ctx, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
     BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the key's upload buffer and the layout go out of scope here
     return BZK_OK;
 }
 
 }  // namespace
+
+// ---- the verifier as a stage of another call (updates.hip): that call declares these buffers in ITS layout, commits once, and enqueues here.
+// A context takes one committed layout at a time (the slab moves when it grows), so a call cannot nest bzk_groth16_verify_batch_dev in its own.
+void g16v_declare(WsLayout& ws, G16vBufs& b, uint32_t n_inputs, uint64_t n, size_t key_bytes) {
+    const uint64_t cap = std::min<uint64_t>(n, G16V_ROUND);
+    b.stride = (uint32_t)((cap + G16V_BLOCK - 1) / G16V_BLOCK * G16V_BLOCK);
+    ws.take(b.slab, (size_t)pairing::slot::COUNT * 14 * b.stride);
+    ws.take(b.flags, b.stride);
+    ws.take(b.sc, (size_t)8 * n_inputs * b.stride + 1);
+    ws.take(b.dkey, key_bytes);
+}
+// n proofs of the valid key K on a committed layout: the key's tables go up, then rounds of G16V_ROUND proofs.  Device pointers; `up` must outlive
+// the stream's work.  sync: wait for it here
+int32_t g16v_enqueue(bzk_ctx* ctx, const G16vBufs& b, const KeyHost& K, const KeyUpload& up, const uint8_t* inputs_dev, const uint8_t* proofs_dev,
+                     uint64_t n, uint8_t* ok_dev, bool sync) {
+    BZK_HIP(ctx, hipMemcpyAsync(b.dkey, up.bytes.data(), up.bytes.size(), hipMemcpyHostToDevice, ctx->stream));
+    const KeyDev k = up.view(K, b.dkey);
+    const size_t in_bytes = (size_t)32 * K.n_inputs;
+    for (uint64_t a = 0; a < n; a += G16V_ROUND) {
+        const uint32_t m = (uint32_t)std::min<uint64_t>(n - a, G16V_ROUND);
+        BZK_TRY(launch_round(ctx, b, k, inputs_dev + in_bytes * a, proofs_dev + 387 * a, m, ok_dev + a));
+    }
+    if (sync) BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BZK_OK;
+}
+void g16v_host_run(const KeyHost& K, const uint8_t* inputs, const uint8_t* proofs, uint64_t n, uint8_t* ok) { host_run(K, inputs, proofs, n, ok); }
+
 }  // namespace bzk
 
 using namespace bzk;

@@ -65,6 +65,8 @@ SIGNATURES = {
     "bzk_sha3_merkle_roots": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "bzk_sha3_merkle_roots_dev": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "bzk_block_bodies_check": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "bzk_contract_updates_check": (_i32, [_vp, _vp, _vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "bzk_l1_tx_updates": (_i32, [_vp, _u64, _u64, C.c_uint32, _vp, _vp, _u64, _vp]),
     "bzk_merkle4_root": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_merkle4_root_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_state_compress": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
@@ -456,6 +458,11 @@ class Bzk:
         """the bodies of len(counts) blocks as bincode(Transaction) back to back, counts[j] per block: (sig_ok m bytes, roots m x 32, tx_ok n
         bytes or None, hashes n x 32 or None); a malformed record raises"""
         return _block_bodies_check(self.h, txs, counts, want_tx)
+
+    def contract_updates_check(self, contract, updates: bytes, counts, height0: int, state0: bytes):
+        """`update_contract`'s per-update checks for the ContractUpdates of len(counts) consecutive transactions of one contract (a
+        ContractDesc): (BZK_UPD_* bits n bytes, aux_data.state_hash n x 32, commitments n x 32); a malformed record raises"""
+        return _contract_updates_check(self.h, contract, updates, counts, height0, state0)
 
     def merkle4_root(self, leaves: bytes, log4: int, want_nodes: bool = False):
         root = C.create_string_buffer(32)
@@ -1606,3 +1613,72 @@ def _block_bodies_check(ctx_handle, txs: bytes, counts, want_tx: bool):
 def host_block_bodies_check(txs: bytes, counts, want_tx: bool = True):
     """Bzk.block_bodies_check without a device"""
     return _block_bodies_check(None, txs, counts, want_tx)
+
+
+UPD_PROOF, UPD_SIGS, UPD_ROUTE, UPD_UNSUPPORTED = 1, 2, 4, 0x80   # bzk_contract_updates_check's verdict bits
+
+
+class _ContractFn(C.Structure):
+    _fields_ = [("vk", C.c_void_p), ("vk_len", C.c_uint64), ("log4_payment_capacity", C.c_uint8)]
+
+
+class _ContractDescStruct(C.Structure):
+    _fields_ = [("contract_id", C.c_uint8 * 32), ("deposit_fns", C.c_void_p), ("n_deposit_fns", C.c_uint32), ("withdraw_fns", C.c_void_p),
+                ("n_withdraw_fns", C.c_uint32), ("fns", C.c_void_p), ("n_fns", C.c_uint32)]
+
+
+class ContractDesc:
+    """bzk_contract_desc: contract_id = the 32 Montgomery bytes of the ContractId's scalar; deposit_fns / withdraw_fns = [(bincode(Groth16VerifyingKey),
+    log4_payment_capacity)], fns = [bincode(Groth16VerifyingKey)].  Keeps the key bytes alive as long as it lives."""
+
+    def __init__(self, contract_id: bytes, deposit_fns=(), withdraw_fns=(), fns=()):
+        assert len(contract_id) == 32
+        self._keep = []
+        self.c = _ContractDescStruct()
+        self.c.contract_id[:] = contract_id
+        for name, table in (("deposit_fns", list(deposit_fns)), ("withdraw_fns", list(withdraw_fns)), ("fns", [(vk, 0) for vk in fns])):
+            arr = (_ContractFn * max(len(table), 1))()
+            for k, (vk, cap) in enumerate(table):
+                buf = C.create_string_buffer(bytes(vk), len(vk))
+                self._keep.append(buf)
+                arr[k].vk, arr[k].vk_len, arr[k].log4_payment_capacity = C.addressof(buf), len(vk), cap
+            self._keep.append(arr)
+            setattr(self.c, name, C.addressof(arr))
+            setattr(self.c, "n_" + name, len(table))
+
+
+def _contract_updates_check(ctx_handle, contract: ContractDesc, updates: bytes, counts, height0: int, state0: bytes):
+    lib = load_library()
+    m, n = len(counts), sum(counts)
+    cnt = (C.c_uint64 * max(m, 1))(*counts)
+    ok = C.create_string_buffer(max(n, 1))
+    aux = C.create_string_buffer(max(32 * n, 1))
+    commit = C.create_string_buffer(max(32 * n, 1))
+    st = lib.bzk_contract_updates_check(ctx_handle, C.byref(contract.c), _ptr(updates) if updates else None, len(updates), cnt, m, height0,
+                                        _ptr(state0), ok, aux, commit)
+    if st != 0:
+        raise BzkError(f"contract_updates_check: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+    return ok.raw[:n], aux.raw[: 32 * n], commit.raw[: 32 * n]
+
+
+def host_contract_updates_check(contract: ContractDesc, updates: bytes, counts, height0: int, state0: bytes):
+    """Bzk.contract_updates_check without a device: the same per-lane functions on host threads"""
+    return _contract_updates_check(None, contract, updates, counts, height0, state0)
+
+
+def l1_tx_updates(txs: bytes, n: int, contract_id: bytes, form: int = L1_FORM_TX, cap=None):
+    """host only: (found, [(transaction index, offset, length)]) of every ContractUpdate of every UpdateContract of contract_id among n
+    Transaction / TransactionAndDelta records; at most cap spans are returned (None: all of them)"""
+    lib = load_library()
+    found = C.c_uint64(0)
+
+    def call(k):
+        spans = (C.c_uint64 * max(3 * k, 1))()
+        st = lib.bzk_l1_tx_updates(_ptr(txs) if txs else None, len(txs), n, form, _ptr(contract_id), spans, k, C.byref(found))
+        if st != 0:
+            raise BzkError(f"l1_tx_updates: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+        return [tuple(spans[3 * i:3 * i + 3]) for i in range(min(k, found.value))]
+    out = call(0 if cap is None else cap)
+    if cap is None and found.value:
+        out = call(found.value)
+    return found.value, out

@@ -211,6 +211,53 @@ int32_t bzk_sha3_merkle_roots_dev(bzk_ctx* ctx, const void* leaves_dev, const vo
 int32_t bzk_block_bodies_check(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, const uint64_t* count, uint64_t m, uint8_t* sig_ok_out,
                                uint8_t* root_out, uint8_t* tx_ok_out, uint8_t* hash_out);
 
+/* ---- wire-form ContractUpdates: commitment, aux data, deposit signatures and proof -------------------------------
+ * What `update_contract` (src/blockchain/ops/apply_tx/update_contract/mod.rs:28-116) computes and verifies per ContractUpdate before and when
+ * it calls zk::check_proof, for the updates of m consecutive UpdateContract transactions of ONE contract: the commitment
+ * ZkScalar::new(sha3(bincode((prover, reward)))), aux_data.state_hash (the root of the payments' list for Deposit / Withdraw, deposit.rs:16-55 and
+ * withdraw.rs:16-72, with every withdrawal's fingerprint; H2(token, fee) for FunctionCall, function_call.rs:28-44), every deposit's Ed25519
+ * signature (apply_deposit.rs:8) and the Groth16 proof over (commit, height, state, aux, next_state).  The host parses the records' structure
+ * only; hashing, field arithmetic, signatures and pairings run on the device.  Balances, nonces and fees, Mint, and the delta / state-root check
+ * after the updates stay with the node. */
+typedef struct { const uint8_t* vk; uint64_t vk_len; uint8_t log4_payment_capacity; } bzk_contract_fn;   /* bincode(Groth16VerifyingKey) */
+typedef struct {
+    uint8_t contract_id[32];                    /* the scalar the circuits use for ContractId (Null 0, Ziesha 1, Custom its scalar): Montgomery limbs */
+    const bzk_contract_fn* deposit_fns;  uint32_t n_deposit_fns;    /* ZkContract.deposit_functions  */
+    const bzk_contract_fn* withdraw_fns; uint32_t n_withdraw_fns;   /* ZkContract.withdraw_functions */
+    const bzk_contract_fn* fns;          uint32_t n_fns;            /* ZkContract.functions; capacity ignored */
+} bzk_contract_desc;
+#define BZK_UPD_PROOF 1u        /* zk::check_proof(circuit, commit, height, state, aux, next_state, proof) */
+#define BZK_UPD_SIGS  2u        /* every deposit's verify_signature (apply_deposit.rs:8); 1 for the other kinds */
+#define BZK_UPD_ROUTE 4u        /* circuit_id names a function of its kind; every payment carries this contract_id and this circuit id
+                                   (DepositWithdrawPassedToWrongFunction); payments <= 4^capacity (batch_set's locator rule) */
+#define BZK_UPD_UNSUPPORTED 128u   /* 0x80.  ContractUpdateData::Mint: left to the node; the other bits are 0 */
+/* updates = n = sum of count bincode(ContractUpdate) records back to back; count[j] of them belong to transaction j.  Every update of
+ * transaction j is checked at height height0 + j (update_contract reads prev_account.height once per transaction).  The first update of the call
+ * is checked against state0, every later one against the next_state.state_hash that the update BEFORE it claims - whatever that update's own
+ * verdict is.  The chain is optimistic: ok[i] says "valid given its predecessor's claim", and the first update with (ok[i] & 7) != 7 is where
+ * the sequence breaks; nothing after it may be applied.
+ * ok[i]: the BZK_UPD_* bits.  With ROUTE clear the proof is not looked at and PROOF is 0.  A key the single verifier refuses (n_ic != 6, a point
+ * off its curve) gives PROOF 0 for all of its updates, as bzk_groth16_verify_batch does; a state0 or next_state.state_hash whose limbs are >= r
+ * gives PROOF 0, not an error.  aux_out (n x 32, may be NULL): aux_data.state_hash, zeros where ROUTE fails or for a Mint; commit_out (n x 32,
+ * may be NULL): the commitments.  BZK_E_ARG with bzk_mpn_work_last_error() naming the record when the bytes are not n well-formed records, a
+ * record is longer than 2^20 bytes, a log4_payment_capacity is above 8, a key is shorter than 878 bytes, or a pointer is NULL with n > 0;
+ * nothing is written then.  n = 0 is a no-op.  Signatures inside deposits are read as bzk_mpn_set_wire_flags says.  ctx = NULL: the same
+ * per-lane functions on host threads.  Payments are staged in rounds that end at an update boundary before 2^16 payments or 64 MiB of record
+ * bytes; the proofs of each (kind, circuit_id) run as one batch of the verifier, the batches one after another.  Synchronises.
+ * Memory: the five inputs and the proof of every routed update (547 bytes) and 70 bytes of aux, commitment, bits and slot per update stay on the device
+ * for the whole call, beside one round's records (at most 64 MiB + one record) and the verifier's slab (at most 2^16 proofs): the workspace grows
+ * by about 0.62 GB per million updates.  There is no limit on n but the device's memory (BZK_E_ALLOC beyond it); a caller syncing more than a
+ * few million updates of a contract splits them into calls, passing the last next_state.state_hash of one as state0 of the next. */
+int32_t bzk_contract_updates_check(bzk_ctx* ctx, const bzk_contract_desc* c, const uint8_t* updates, uint64_t len, const uint64_t* count, uint64_t m,
+                                   uint64_t height0, const uint8_t state0[32], uint8_t* ok, uint8_t* aux_out, uint8_t* commit_out);
+/* Host only, parses and nothing else: for n Transaction / TransactionAndDelta records (form: BZK_L1_FORM_*) lists every ContractUpdate of every
+ * UpdateContract whose contract_id equals the given scalar.  spans_out: up to cap entries of three words (transaction index, offset in txs,
+ * length); *n_out = the number found, even beyond cap (set to 0 before parsing: that is what a refused call leaves there; spans_out is not
+ * written then).  Refusals as bzk_l1_tx_verify_batch.  With it a caller goes from
+ * bzk_block_bodies_check's input to bzk_contract_updates_check's. */
+int32_t bzk_l1_tx_updates(const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, const uint8_t contract_id[32], uint64_t* spans_out, uint64_t cap,
+                          uint64_t* n_out);
+
 /* ---- K2: dense 4-ary ZkState tree re-hash ----------------------------------------------------
  * Root of `ZkStateModel::List{log4_size, Scalar}` with every leaf present, as
  * `ZkStateBuilder::compress` / `KvStoreStateManager::root` would give (src/zk/state/mod.rs:66-90,

@@ -20,6 +20,9 @@
 //!                                transactions at once, the signed form hashed in place on the device
 //!   * `Gpu::sha3_merkle_root`  - `MerkleTree::<Sha3Hasher>::new(leaves).root()` (src/crypto/merkle.rs)
 //!   * `Gpu::block_bodies_check` - the body checks of src/blockchain/ops/apply_block.rs:47 and :88 for many blocks in one call
+//!   * `Gpu::check_contract_updates` - what `update_contract` (src/blockchain/ops/apply_tx/update_contract/mod.rs:28-116) computes and verifies
+//!                                per `ContractUpdate`: commitment, aux data, deposit signatures, proof - for many transactions of one contract
+//!   * `contract_update_spans`  - where the `ContractUpdate`s of one contract lie in serialized transactions (host only)
 //!   * `groth16_prove`          - beside `groth16_verify` (src/zk/groth16/mod.rs:67-75), same argument order
 //!   * `groth16_verify_batch`   - `groth16_verify` for n proofs of one key: update_contract/mod.rs:100 and `MpnWork::verify` (src/mpn/mod.rs:281-295)
 //!   * `compress`               - `ZkStateModel::compress::<H>(&data)` (src/zk/mod.rs:392-399)
@@ -36,13 +39,13 @@
 //!
 //! Layout assumptions (already relied upon by the reference's own `transmute`s, src/zk/groth16/mod.rs:7-17): `ZkScalar` is
 //! `[u64; 4]` little-endian Montgomery limbs; bincode 1.3 with default options; `Groth16Proof` = 97 + 193 + 97 bytes under bincode.
-use bazuka::core::{Address, Block, MpnDeposit, MpnWithdraw, Transaction};
+use bazuka::core::{Address, Block, ContractId, ContractUpdate, MpnDeposit, MpnWithdraw, Transaction};
 use bazuka::crypto::jubjub::{PublicKey, Signature};
 use bazuka::mpn::MpnWork;
 use bazuka::zk::groth16::Groth16Proof;
 use bazuka::zk::{
     MpnTransaction, StateManagerError, ZkCompressedState, ZkDataLocator, ZkDataPairs, ZkDeltaPairs, ZkHasher, ZkLocatorError, ZkProof, ZkScalar,
-    ZkStateModel,
+    ZkContract, ZkStateModel, ZkVerifierKey,
 };
 use bzk_sys as sys;
 use std::ffi::CStr;
@@ -239,6 +242,67 @@ impl Gpu {
         }
         check(self.0, st)?;
         Ok(ok.iter().zip(roots.chunks_exact(32)).map(|(b, r)| (*b != 0, r.try_into().unwrap())).collect())
+    }
+
+    /// The per-update checks of `update_contract` (src/blockchain/ops/apply_tx/update_contract/mod.rs:28-116) for the `UpdateContract`
+    /// transactions `txs` of ONE contract, in chain order: transaction j's updates are checked at `height0 + j`, the first update against
+    /// `state0`, every later one against the `next_state` its predecessor claims.  Per update: the `BZK_UPD_*` bits (PROOF, SIGS, ROUTE; 0x80
+    /// alone for a Mint), `aux_data.state_hash` and the commitment.  The first update whose bits are not all set is where the sequence breaks.
+    /// Balances, nonces, fees and the delta / state-root check after the updates stay with the caller.
+    pub fn check_contract_updates(&self, contract_id: ContractId, contract: &ZkContract, txs: &[&[ContractUpdate]], height0: u64,
+                                  state0: ZkScalar) -> Result<Vec<(u8, ZkScalar, ZkScalar)>, GpuError> {
+        fn key_bytes(vk: &ZkVerifierKey) -> Result<Vec<u8>, GpuError> {
+            #[allow(unreachable_patterns)]
+            match vk {
+                ZkVerifierKey::Groth16(k) => Ok(bincode::serialize(&**k)?),
+                _ => Ok(Vec::new()), // no Groth16 key: refused by the call
+            }
+        }
+        let mut keys: Vec<(Vec<u8>, u8)> = Vec::new();
+        for f in &contract.deposit_functions {
+            keys.push((key_bytes(&f.verifier_key)?, f.log4_payment_capacity));
+        }
+        for f in &contract.withdraw_functions {
+            keys.push((key_bytes(&f.verifier_key)?, f.log4_payment_capacity));
+        }
+        for f in &contract.functions {
+            keys.push((key_bytes(&f.verifier_key)?, 0));
+        }
+        let fns: Vec<sys::bzk_contract_fn> =
+            keys.iter().map(|(k, c)| sys::bzk_contract_fn { vk: k.as_ptr(), vk_len: k.len() as u64, log4_payment_capacity: *c }).collect();
+        let (nd, nw) = (contract.deposit_functions.len(), contract.withdraw_functions.len());
+        let id: ZkScalar = contract_id.into();
+        let mut desc = sys::bzk_contract_desc {
+            contract_id: [0u8; 32],
+            deposit_fns: fns.as_ptr(),
+            n_deposit_fns: nd as u32,
+            withdraw_fns: unsafe { fns.as_ptr().add(nd) },
+            n_withdraw_fns: nw as u32,
+            fns: unsafe { fns.as_ptr().add(nd + nw) },
+            n_fns: contract.functions.len() as u32,
+        };
+        desc.contract_id.copy_from_slice(unsafe { std::slice::from_raw_parts(scalars_ptr(std::slice::from_ref(&id)), 32) });
+        let (mut bytes, mut count) = (Vec::new(), Vec::with_capacity(txs.len()));
+        for updates in txs {
+            for u in updates.iter() {
+                bytes.extend_from_slice(&bincode::serialize(u)?);
+            }
+            count.push(updates.len() as u64);
+        }
+        let n: usize = txs.iter().map(|u| u.len()).sum();
+        let mut ok = vec![0u8; n];
+        let (mut aux, mut commit) = (vec![ZkScalar::default(); n], vec![ZkScalar::default(); n]);
+        let st = unsafe {
+            sys::bzk_contract_updates_check(self.0, &desc, bytes.as_ptr(), bytes.len() as u64, count.as_ptr(), txs.len() as u64, height0,
+                                            scalars_ptr(std::slice::from_ref(&state0)), ok.as_mut_ptr(), aux.as_mut_ptr() as *mut u8,
+                                            commit.as_mut_ptr() as *mut u8)
+        };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(self.0, st)?;
+        Ok(ok.into_iter().zip(aux).zip(commit).map(|((o, a), c)| (o, a, c)).collect())
     }
 
     /// Bulk `Ed25519::verify(pk, msg, sig)` (src/crypto/ed25519.rs:81-83: ed25519-dalek 1 `PublicKey::verify`, the non-strict verifier) over raw
@@ -729,4 +793,30 @@ impl Drop for DeviceGroup {
     fn drop(&mut self) {
         unsafe { sys::bzk_mg_destroy(self.0) }
     }
+}
+
+/// Host only, parses and nothing else: (transaction index, offset, length) of every `ContractUpdate` of every `UpdateContract` of `contract_id`
+/// inside `bytes`, the bincode of `n` consecutive `TransactionAndDelta` (`with_delta`) or `Transaction` records - what `Gpu::block_bodies_check`
+/// serializes.  The spans re-slice to the input of `bzk_contract_updates_check`.
+pub fn contract_update_spans(bytes: &[u8], n: usize, with_delta: bool, contract_id: ContractId) -> Result<Vec<(u64, u64, u64)>, GpuError> {
+    let id: ZkScalar = contract_id.into();
+    let form: u32 = if with_delta { 1 } else { 0 }; // BZK_L1_FORM_TX_AND_DELTA / BZK_L1_FORM_TX
+    let mut found = 0u64;
+    let mut spans: Vec<u64> = Vec::new();
+    for _ in 0..2 {
+        let st = unsafe {
+            sys::bzk_l1_tx_updates(bytes.as_ptr(), bytes.len() as u64, n as u64, form, scalars_ptr(std::slice::from_ref(&id)), spans.as_mut_ptr(),
+                                   (spans.len() / 3) as u64, &mut found)
+        };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(ptr::null_mut(), st)?;
+        if spans.len() as u64 >= 3 * found {
+            break;
+        }
+        spans = vec![0u64; 3 * found as usize];
+    }
+    Ok(spans.chunks_exact(3).take(found as usize).map(|s| (s[0], s[1], s[2])).collect())
 }

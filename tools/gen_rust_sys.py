@@ -83,7 +83,11 @@ def parse(src: str):
             else:
                 ty, n = decl.rsplit(" ", 1)
                 stars = len(n) - len(n.lstrip("*"))
-                fields.append((n.lstrip("*"), ty + " *" * stars))
+                arr = re.match(r"^(\w+)\[(\d+)\]$", n.lstrip("*"))  # `uint8_t contract_id[32]`: an array INSIDE the struct, not a pointer
+                if arr:
+                    fields.append((arr.group(1), ty + " *" * stars, int(arr.group(2))))
+                else:
+                    fields.append((n.lstrip("*"), ty + " *" * stars))
         structs.append((m.group(2), fields))
     body_nostruct = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", "", body, flags=re.S)
     for m in re.finditer(r"typedef\s+struct\s+(\w+)\s+(\w+)\s*;", body_nostruct):
@@ -139,8 +143,9 @@ def generate() -> str:
         o.append("#[repr(C)]")
         o.append("#[derive(Clone, Copy)]")
         o.append(f"pub struct {n} {{")
-        for fn_, ty in fields:
-            o.append(f"    pub {ident(fn_)}: {rust_type(ty, names)},")
+        for fn_, ty, *count in fields:
+            rt = rust_type(ty, names)
+            o.append(f"    pub {ident(fn_)}: {f'[{rt}; {count[0]}]' if count else rt},")
         o.append("}")
         o.append("")
     o.append('#[link(name = "bzk")]')

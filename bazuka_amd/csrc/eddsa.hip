@@ -9,13 +9,12 @@
 #include "bzk_keccak.cuh"
 #include "bzk_ed25519.cuh"
 #include "bzk_l1.cuh"
-#include <atomic>
-#include <thread>
 #include "bzk_internal.h"
+#include "bzk_rounds.h"
+#include "host_threads.h"
 
 namespace bzk {
 
-int host_default_threads();  // host_zk.hip
 int32_t poseidon_consts_dev_shared(bzk_ctx* ctx, int t, const void** out, int* rf, int* rp);  // poseidon.hip
 int32_t poseidon_launch(bzk_ctx* ctx, const void* in_dev, uint32_t arity, uint64_t n, void* out_dev);       // poseidon.hip
 
@@ -270,7 +269,7 @@ int32_t jubjub_decompress_launch(bzk_ctx* ctx, const void* x_dev, const void* od
     return BZK_OK;
 }
 
-// MpnTransaction::verify_signature for n parsed transactions (mpn.hip parses; TxSoA is what it hands over): per chunk one decompress launch over
+// MpnTransaction::verify_signature for n parsed transactions (TxSoA from wire.hip, parsed by host_bincode.h): per chunk one decompress launch over
 // the 2 m keys (src keys first, so that their points are the verifier's key array as they stand), the hash inputs, the arity-7 Poseidon batch, the
 // signature kernel, the verdicts.  No field arithmetic on the host.  639 bytes of workspace per transaction.
 int32_t mpn_tx_verify_run(bzk_ctx* ctx, const TxSoA& t, uint64_t n, uint8_t* ok, uint8_t* hash_out, uint8_t* src_xy_out, uint8_t* dst_xy_out) {
@@ -320,7 +319,7 @@ int32_t sha3_256_launch(bzk_ctx* ctx, const void* data_dev, const void* begin_de
     return BZK_OK;
 }
 
-// MpnWithdraw::verify_signature and verify_calldata for n parsed records (mpn.hip parses; WdSoA is what it hands over).  A chunk ends at
+// MpnWithdraw::verify_signature and verify_calldata for n parsed records (WdSoA from wire.hip, parsed by host_bincode.h).  A chunk ends at
 // MPN_TX_CHUNK records or MPN_WD_CHUNK_BYTES of payment bytes, whichever comes first (a payment is at most MPN_WD_PAYMENT_MAX bytes, so a chunk
 // always holds a record); its records' bytes go up as they stand, headers included, and the kernels index the payments inside them.  Per chunk:
 // fingerprints (SHA3 with the calldata blanked, then ZkScalar::new), one decompress launch, the hash inputs, H2, H6, the signature kernel, the
@@ -328,20 +327,14 @@ int32_t sha3_256_launch(bzk_ctx* ctx, const void* data_dev, const void* begin_de
 int32_t mpn_withdraw_verify_run(bzk_ctx* ctx, const WdSoA& t, uint64_t n, uint8_t* ok, uint8_t* fp_out, uint8_t* xy_out) {
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    std::vector<uint64_t> chunk_at(1, 0), begin(n), end(n);  // payment ranges relative to their chunk's first byte
-    uint64_t cap = 0, cap_bytes = 0;
-    for (uint64_t a = 0; a < n;) {
-        uint64_t b = a, pay = 0;
-        while (b < n && b - a < MPN_TX_CHUNK && (b == a || pay + t.pay_len[b] <= MPN_WD_CHUNK_BYTES)) pay += t.pay_len[b++];
-        for (uint64_t i = a; i < b; ++i) {
-            begin[i] = t.pay_off[i] - t.rec_off[a];
+    const std::vector<uint64_t> chunk_at = cut_rounds(n, MPN_TX_CHUNK, MPN_WD_CHUNK_BYTES, [&](uint64_t i) { return (uint64_t)t.pay_len[i]; });
+    const auto [cap, cap_bytes] = round_caps(chunk_at, t.rec_off);
+    std::vector<uint64_t> begin(n), end(n);  // payment ranges relative to their chunk's first byte
+    for (size_t c = 0; c + 1 < chunk_at.size(); ++c)
+        for (uint64_t i = chunk_at[c]; i < chunk_at[c + 1]; ++i) {
+            begin[i] = t.pay_off[i] - t.rec_off[chunk_at[c]];
             end[i] = begin[i] + t.pay_len[i];
         }
-        cap = std::max(cap, b - a);
-        cap_bytes = std::max(cap_bytes, t.rec_off[b] - t.rec_off[a]);
-        chunk_at.push_back(b);
-        a = b;
-    }
     WsLayout ws("mpn_withdraw_verify_run");
     uint8_t *dbytes, *dbeg, *dend, *dcd, *dnonce, *dkx, *dfp, *dmsg, *dcall, *dxy, *dh2, *dsig, *dh6, *dodd, *dkok, *dfit, *dver, *dok;
     ws.take(dbytes, cap_bytes); ws.take(dbeg, cap * 8); ws.take(dend, cap * 8); ws.take(dcd, cap * 4); ws.take(dnonce, cap * 4);
@@ -421,24 +414,6 @@ static int32_t ed25519_verify_launch(bzk_ctx* ctx, const void* pk_dev, const voi
     return BZK_OK;
 }
 
-// fn(i) for every i < n on up to `threads` host threads
-template <class F>
-static void host_for_each(uint64_t n, int threads, F fn) {
-    std::atomic<uint64_t> next(0);
-    auto worker = [&] {
-        for (;;) {
-            const uint64_t i = next.fetch_add(1);
-            if (i >= n) break;
-            fn(i);
-        }
-    };
-    std::vector<std::thread> th;
-    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(threads, 1), n);
-    for (int k = 1; k < nt; ++k) th.emplace_back(worker);
-    worker();
-    for (auto& x : th) x.join();
-}
-
 uint8_t mpn_deposit_sig_host(const DpSoA& t, uint64_t i) {
     if (!t.has_sig[i]) return 0;
     const uint8_t* pay = t.txs + t.pay_off[i];
@@ -447,29 +422,22 @@ uint8_t mpn_deposit_sig_host(const DpSoA& t, uint64_t i) {
     return ed25519::verify_host(pay + t.src_off[i], pay + t.sig_off[i], body);
 }
 
-// ContractDeposit::verify_signature and the address decompression for n parsed MpnDeposits (mpn.hip parses; DpSoA is what it hands over).  Chunks
+// ContractDeposit::verify_signature and the address decompression for n parsed MpnDeposits (DpSoA from wire.hip, parsed by host_bincode.h).  Chunks
 // as mpn_withdraw_verify_run cuts them; a chunk's records go up as they stand and the verifier reads key, signature and signed bytes inside them.
 // Per chunk: one Ed25519 launch, one decompress launch, the verdicts.  No hashing and no field arithmetic on the host.
 int32_t mpn_deposit_verify_run(bzk_ctx* ctx, const DpSoA& t, uint64_t n, uint8_t* ok, uint8_t* xy_out) {
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    std::vector<uint64_t> chunk_at(1, 0), begin(n), end(n), pk_at(n), sig_at(n);  // relative to their chunk's first byte
-    uint64_t cap = 0, cap_bytes = 0;
-    for (uint64_t a = 0; a < n;) {
-        uint64_t b = a, pay = 0;
-        while (b < n && b - a < MPN_TX_CHUNK && (b == a || pay + (t.rec_off[b + 1] - t.pay_off[b]) <= MPN_WD_CHUNK_BYTES))
-            pay += t.rec_off[b + 1] - t.pay_off[b], ++b;
-        for (uint64_t i = a; i < b; ++i) {
-            begin[i] = t.pay_off[i] - t.rec_off[a];
+    const std::vector<uint64_t> chunk_at = cut_rounds(n, MPN_TX_CHUNK, MPN_WD_CHUNK_BYTES, [&](uint64_t i) { return t.rec_off[i + 1] - t.pay_off[i]; });
+    const auto [cap, cap_bytes] = round_caps(chunk_at, t.rec_off);
+    std::vector<uint64_t> begin(n), end(n), pk_at(n), sig_at(n);  // relative to their chunk's first byte
+    for (size_t c = 0; c + 1 < chunk_at.size(); ++c)
+        for (uint64_t i = chunk_at[c]; i < chunk_at[c + 1]; ++i) {
+            begin[i] = t.pay_off[i] - t.rec_off[chunk_at[c]];
             end[i] = begin[i] + t.tag_off[i];
             pk_at[i] = begin[i] + t.src_off[i];
             sig_at[i] = begin[i] + t.sig_off[i];
         }
-        cap = std::max(cap, b - a);
-        cap_bytes = std::max(cap_bytes, t.rec_off[b] - t.rec_off[a]);
-        chunk_at.push_back(b);
-        a = b;
-    }
     WsLayout ws("mpn_deposit_verify_run");
     uint8_t *dbytes, *dbeg, *dend, *dpk, *dsg, *dkx, *dxy, *dodd, *dhas, *dkok, *dver, *dok;
     ws.take(dbytes, cap_bytes); ws.take(dbeg, cap * 8); ws.take(dend, cap * 8); ws.take(dpk, cap * 8); ws.take(dsg, cap * 8);
@@ -496,19 +464,9 @@ int32_t mpn_deposit_verify_run(bzk_ctx* ctx, const DpSoA& t, uint64_t n, uint8_t
     return BZK_OK;
 }
 
-// the chunks of a host batch of messages: at most `chunk` messages or `chunk_bytes` bytes each, and at least one message
-static void message_chunks(const uint64_t* off, uint64_t n, uint64_t chunk, uint64_t chunk_bytes, std::vector<uint64_t>& chunk_at, uint64_t& cap,
-                           uint64_t& cap_bytes) {
-    chunk_at.assign(1, 0);
-    cap = cap_bytes = 0;
-    for (uint64_t a = 0; a < n;) {
-        uint64_t b = a + 1;
-        while (b < n && b - a < chunk && off[b + 1] - off[a] <= chunk_bytes) ++b;
-        cap = std::max(cap, b - a);
-        cap_bytes = std::max(cap_bytes, off[b] - off[a]);
-        chunk_at.push_back(b);
-        a = b;
-    }
+// the rounds of a host batch of messages (off: n + 1 byte offsets): at most `chunk` messages or `chunk_bytes` bytes each, and at least one message
+static std::vector<uint64_t> message_rounds(const uint64_t* off, uint64_t n, uint64_t chunk, uint64_t chunk_bytes) {
+    return cut_rounds(n, chunk, chunk_bytes, [off](uint64_t i) { return off[i + 1] - off[i]; });
 }
 static bool offsets_ok(const uint64_t* off, uint64_t n) {
     if (off[0] != 0) return false;
@@ -635,10 +593,8 @@ int32_t l1_check_run(bzk_ctx* ctx, const L1SoA& t, uint64_t n, const uint64_t* c
     (void)hipSetDevice(ctx->device);
     MerklePlan P;
     if (count && !P.build(count, m)) return BZK_E_ARG;
-    std::vector<uint64_t> chunk_at;
-    uint64_t cap = 0, cap_bytes = 0;
-    if (n) message_chunks(t.rec_off, n, l1::CHUNK, l1::CHUNK_BYTES, chunk_at, cap, cap_bytes);
-    else chunk_at.assign(1, 0);
+    const std::vector<uint64_t> chunk_at = message_rounds(t.rec_off, n, l1::CHUNK, l1::CHUNK_BYTES);
+    const auto [cap, cap_bytes] = round_caps(chunk_at, t.rec_off);
     const bool want_hash = hash_out || count;
     WsLayout ws("l1_check_run");
     uint8_t *dbytes, *dok, *dhash, *dnodes, *droots, *dall;
@@ -797,17 +753,8 @@ int32_t bzk_sha3_256_batch(bzk_ctx* ctx, const uint8_t* data, const uint64_t* of
     for (uint64_t i = 0; i < n; ++i)
         if (off[i + 1] < off[i]) return BZK_E_ARG;
     (void)hipSetDevice(ctx->device);
-    constexpr uint64_t CHUNK = (uint64_t)1 << 20, CHUNK_BYTES = (uint64_t)64 << 20;  // a chunk: so many messages or bytes, and at least one message
-    std::vector<uint64_t> chunk_at(1, 0);
-    uint64_t cap = 0, cap_bytes = 0;
-    for (uint64_t a = 0; a < n;) {
-        uint64_t b = a + 1;
-        while (b < n && b - a < CHUNK && off[b + 1] - off[a] <= CHUNK_BYTES) ++b;
-        cap = std::max(cap, b - a);
-        cap_bytes = std::max(cap_bytes, off[b] - off[a]);
-        chunk_at.push_back(b);
-        a = b;
-    }
+    const std::vector<uint64_t> chunk_at = message_rounds(off, n, (uint64_t)1 << 20, (uint64_t)64 << 20);
+    const auto [cap, cap_bytes] = round_caps(chunk_at, off);
     WsLayout ws("bzk_sha3_256_batch");
     uint8_t *ddata, *doff, *ddig, *dsc;
     ws.take(ddata, cap_bytes ? cap_bytes : 1); ws.take(doff, (cap + 1) * 8); ws.take(ddig, cap * 32); ws.take(dsc, cap * 32);
@@ -843,9 +790,8 @@ int32_t bzk_sha512_batch(bzk_ctx* ctx, const uint8_t* data, const uint64_t* off,
         return BZK_OK;
     }
     (void)hipSetDevice(ctx->device);
-    std::vector<uint64_t> chunk_at;
-    uint64_t cap, cap_bytes;
-    message_chunks(off, n, (uint64_t)1 << 20, (uint64_t)64 << 20, chunk_at, cap, cap_bytes);
+    const std::vector<uint64_t> chunk_at = message_rounds(off, n, (uint64_t)1 << 20, (uint64_t)64 << 20);
+    const auto [cap, cap_bytes] = round_caps(chunk_at, off);
     WsLayout ws("bzk_sha512_batch");
     uint8_t *ddata, *doff, *ddig;
     ws.take(ddata, cap_bytes ? cap_bytes : 1); ws.take(doff, (cap + 1) * 8); ws.take(ddig, cap * 64);
@@ -881,9 +827,8 @@ int32_t bzk_ed25519_verify_batch(bzk_ctx* ctx, const uint8_t* pk, const uint8_t*
         return BZK_OK;
     }
     (void)hipSetDevice(ctx->device);
-    std::vector<uint64_t> chunk_at;
-    uint64_t cap, cap_bytes;
-    message_chunks(off, n, (uint64_t)1 << 20, (uint64_t)64 << 20, chunk_at, cap, cap_bytes);
+    const std::vector<uint64_t> chunk_at = message_rounds(off, n, (uint64_t)1 << 20, (uint64_t)64 << 20);
+    const auto [cap, cap_bytes] = round_caps(chunk_at, off);
     WsLayout ws("bzk_ed25519_verify_batch");
     uint8_t *ddata, *doff, *dpk, *dsig, *dok;
     ws.take(ddata, cap_bytes ? cap_bytes : 1); ws.take(doff, (cap + 1) * 8); ws.take(dpk, cap * 32); ws.take(dsig, cap * 64); ws.take(dok, cap);

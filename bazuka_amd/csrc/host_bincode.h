@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "bzk_l1.h"
+#include "bzk_mpn_wire.h"
 #include "bzk_updates.h"
 #include "host_mpn_types.h"
 
@@ -539,6 +540,158 @@ inline ZkScalar mpn_work_commitment(const uint8_t prover_pub[32], uint64_t rewar
     w.raw(prover_pub, 32);
     w.u64(reward);
     return hash_to_scalar(w.b.data(), w.b.size());
+}
+
+// ---- wire-form MPN records (bzk_mpn_wire.h): structure only --------------------------------------------------------------------------------
+// parse_txs / parse_withdraws / parse_deposits cut n consecutive bincode(MpnTransaction) / bincode(MpnWithdraw) / bincode(MpnDeposit) records into
+// the arrays the device stages (TxSoA / WdSoA / DpSoA).  They only cut byte ranges, read integers and tags and map ContractId tags: no hashing
+// and no field arithmetic, so that the device paths (eddsa.hip mpn_*_verify_run) leave none on the host.
+struct TxParsed {
+    std::vector<uint8_t> src_x, dst_x, src_odd, dst_odd, tok, sig;
+    std::vector<uint64_t> nums;
+    TxSoA soa() const { return {src_x.data(), dst_x.data(), src_odd.data(), dst_odd.data(), tok.data(), nums.data(), sig.data()}; }
+};
+// ContractId as the scalar the circuits use, copied as bytes (Null = 0, Ziesha = 1: constants)
+inline void parse_contract_id(BinReader& r, uint8_t out[32]) {
+    const uint32_t tag = r.u32("ContractId tag");
+    memset(out, 0, 32);
+    if (tag == 0) return;
+    if (tag == 1) return ZkScalar::one().to_bytes(out);
+    if (tag == 2) {
+        if (const uint8_t* b = r.bytes(32, "ContractId::Custom")) memcpy(out, b, 32);
+        return;
+    }
+    r.fail("ContractId variant");
+}
+inline bool parse_txs(const uint8_t* txs, uint64_t len, uint64_t n, TxParsed& P, std::string& err) {
+    if (n > len / 190) {  // the shortest record: 4 + 2 x 33 + 2 x 12 + 96
+        err = "fewer bytes than " + std::to_string(n) + " MpnTransaction records need";
+        return false;
+    }
+    P.src_x.resize(n * 32); P.dst_x.resize(n * 32); P.src_odd.resize(n); P.dst_odd.resize(n);
+    P.tok.resize(n * 64); P.sig.resize(n * 96); P.nums.resize(n * 3);
+    BinReader r(txs, (size_t)len);
+    for (uint64_t i = 0; i < n && r.ok; ++i) {
+        P.nums[3 * i] = r.u32("MpnTransaction.nonce");
+        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.src_x[32 * i], b, 32);
+        P.src_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
+        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.dst_x[32 * i], b, 32);
+        P.dst_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
+        parse_contract_id(r, &P.tok[64 * i]);
+        P.nums[3 * i + 1] = r.u64("Amount");
+        parse_contract_id(r, &P.tok[64 * i + 32]);
+        P.nums[3 * i + 2] = r.u64("Amount");
+        if (const uint8_t* b = r.bytes(96, "Signature")) memcpy(&P.sig[96 * i], b, 96);
+        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
+    }
+    if (r.ok && r.pos != len) r.fail("bytes after the last record");
+    err = r.err;
+    return r.ok;
+}
+struct WdParsed {
+    const uint8_t* txs = nullptr;
+    std::vector<uint64_t> rec_off, pay_off, amounts;  // amounts n x 2: amount, fee
+    std::vector<uint32_t> pay_len, cd_off, nonce, circuit;
+    std::vector<uint8_t> key_x, key_odd, sig, cid, tok;  // cid n x 32: payment.contract_id as a scalar; tok n x 64: amount | fee token ids
+    WdSoA soa() const {
+        return {txs, rec_off.data(), pay_off.data(), pay_len.data(), cd_off.data(), key_x.data(), key_odd.data(), nonce.data(), sig.data()};
+    }
+};
+inline bool parse_withdraws(const uint8_t* txs, uint64_t len, uint64_t n, WdParsed& P, std::string& err) {
+    if (n > len / 245) {  // the shortest record: 33 + 4 + 96 + (8 + 4 + 4 + 32 + 40 + 2 x 12)
+        err = "fewer bytes than " + std::to_string(n) + " MpnWithdraw records need";
+        return false;
+    }
+    P.txs = txs;
+    P.rec_off.resize(n + 1); P.pay_off.resize(n); P.amounts.resize(2 * n);
+    P.pay_len.resize(n); P.cd_off.resize(n); P.nonce.resize(n); P.circuit.resize(n);
+    P.key_x.resize(n * 32); P.key_odd.resize(n); P.sig.resize(n * 96); P.cid.resize(n * 32); P.tok.resize(n * 64);
+    BinReader r(txs, (size_t)len);
+    for (uint64_t i = 0; i < n && r.ok; ++i) {
+        P.rec_off[i] = r.pos;
+        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.key_x[32 * i], b, 32);
+        P.key_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
+        P.nonce[i] = r.u32("MpnWithdraw.mpn_withdraw_nonce");
+        if (const uint8_t* b = r.bytes(96, "Signature")) memcpy(&P.sig[96 * i], b, 96);
+        P.pay_off[i] = r.pos;
+        skip_string(r);
+        parse_contract_id(r, &P.cid[32 * i]);
+        P.circuit[i] = r.u32("withdraw_circuit_id");
+        P.cd_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
+        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail("ContractWithdraw longer than 65536 bytes");
+        r.bytes(32, "calldata");
+        skip_l1_pub(r);
+        parse_contract_id(r, &P.tok[64 * i]);
+        P.amounts[2 * i] = r.u64("Amount");
+        parse_contract_id(r, &P.tok[64 * i + 32]);
+        P.amounts[2 * i + 1] = r.u64("Amount");
+        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail("ContractWithdraw longer than 65536 bytes");
+        P.pay_len[i] = (uint32_t)(r.pos - P.pay_off[i]);
+        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
+    }
+    if (r.ok) P.rec_off[n] = r.pos;
+    if (r.ok && r.pos != len) r.fail("bytes after the last record");
+    err = r.err;
+    return r.ok;
+}
+struct DpParsed {
+    const uint8_t* txs = nullptr;
+    std::vector<uint64_t> rec_off, pay_off, amount;
+    std::vector<uint32_t> pay_len, tag_off, src_off, sig_off, circuit;
+    std::vector<uint8_t> has_sig, key_x, key_odd, cid, tok;  // cid n x 32: payment.contract_id as a scalar; tok n x 32: amount.token_id
+    DpSoA soa() const {
+        return {txs, rec_off.data(), pay_off.data(), tag_off.data(), src_off.data(), sig_off.data(), has_sig.data(), key_x.data(), key_odd.data()};
+    }
+};
+inline bool parse_deposits(const uint8_t* txs, uint64_t len, uint64_t n, uint32_t flags, DpParsed& P, std::string& err) {
+    if (n > len / 150) {  // the shortest record: 33 + (8 + 4 + 4 + 32 + 40 + 2 x 12 + 4 + 1)
+        err = "fewer bytes than " + std::to_string(n) + " MpnDeposit records need";
+        return false;
+    }
+    P.txs = txs;
+    P.rec_off.resize(n + 1); P.pay_off.resize(n); P.amount.resize(n);
+    P.pay_len.resize(n); P.tag_off.resize(n); P.src_off.resize(n); P.sig_off.resize(n); P.circuit.resize(n);
+    P.has_sig.resize(n); P.key_x.resize(n * 32); P.key_odd.resize(n); P.cid.resize(n * 32); P.tok.resize(n * 32);
+    BinReader r(txs, (size_t)len);
+    uint8_t fee_tok[32];
+    const char* too_long = "ContractDeposit longer than 65536 bytes";
+    for (uint64_t i = 0; i < n && r.ok; ++i) {
+        P.rec_off[i] = r.pos;
+        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.key_x[32 * i], b, 32);
+        P.key_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
+        P.pay_off[i] = r.pos;
+        skip_string(r);
+        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail(too_long);
+        parse_contract_id(r, &P.cid[32 * i]);
+        P.circuit[i] = r.u32("deposit_circuit_id");
+        r.bytes(32, "calldata");
+        if (r.u64("ed25519 public key length") != 32) r.fail("ed25519 public key length");
+        P.src_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
+        r.bytes(32, "ed25519 public key");
+        parse_contract_id(r, &P.tok[32 * i]);
+        P.amount[i] = r.u64("Amount");
+        parse_contract_id(r, fee_tok);
+        r.u64("Amount");
+        r.u32("nonce");
+        P.tag_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
+        const uint8_t some = r.u8("Option<Signature> tag");
+        if (r.ok && some > 1) r.fail("Option tag");
+        P.has_sig[i] = some == 1;
+        P.sig_off[i] = 0;
+        if (r.ok && some) {
+            if (flags & BZK_WORK_SIG_LEN_PREFIXED)
+                if (r.u64("ed25519 signature length") != 64) r.fail("ed25519 signature length");
+            P.sig_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
+            r.bytes(64, "ed25519 signature");
+        }
+        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail(too_long);
+        P.pay_len[i] = (uint32_t)(r.pos - P.pay_off[i]);
+        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
+    }
+    if (r.ok) P.rec_off[n] = r.pos;
+    if (r.ok && r.pos != len) r.fail("bytes after the last record");
+    err = r.err;
+    return r.ok;
 }
 
 // ---- L1 transactions (src/core/transaction.rs:313-363): structure only ------------------------------------------------------------------

@@ -23,111 +23,10 @@
 
 #include "bzk_internal.h"
 #include "host_r1cs.h"
-
-namespace bzk {
-
-// ------------------------------------------------------------------------------------------------
-// sparse 4-ary Poseidon tree
-// ------------------------------------------------------------------------------------------------
-struct SparseTree4 {
-    int depth;
-    std::vector<ZkScalar> defaults;                              // [0] = leaf default ... [depth] = empty root
-    std::vector<std::unordered_map<uint64_t, ZkScalar>> level;   // level[0] = leaves
-    SparseTree4(int d, const ZkScalar& leaf_default) : depth(d), level(d + 1) {
-        defaults.push_back(leaf_default);
-        for (int i = 0; i < d; ++i) {
-            ZkScalar c[4] = {defaults.back(), defaults.back(), defaults.back(), defaults.back()};
-            defaults.push_back(poseidon_hash(c, 4));
-        }
-    }
-    ZkScalar get(int lv, uint64_t i) const {
-        auto it = level[lv].find(i);
-        return it == level[lv].end() ? defaults[lv] : it->second;
-    }
-    ZkScalar root() const { return get(depth, 0); }
-    void set_leaf(uint64_t i, const ZkScalar& v) {
-        level[0][i] = v;
-        for (int lv = 0; lv < depth; ++lv) {
-            const uint64_t base = i & ~(uint64_t)3;
-            ZkScalar c[4] = {get(lv, base), get(lv, base + 1), get(lv, base + 2), get(lv, base + 3)};
-            i >>= 2;
-            level[lv + 1][i] = poseidon_hash(c, 4);
-        }
-    }
-    // sibling triples, leaf level first (src/zk/state/mod.rs:218-264)
-    std::vector<std::array<ZkScalar, 3>> prove(uint64_t i) const {
-        std::vector<std::array<ZkScalar, 3>> out;
-        for (int lv = 0; lv < depth; ++lv) {
-            const uint64_t base = i & ~(uint64_t)3;
-            std::array<ZkScalar, 3> t;
-            int k = 0;
-            for (uint64_t j = 0; j < 4; ++j)
-                if (base + j != i) t[k++] = get(lv, base + j);
-            out.push_back(t);
-            i >>= 2;
-        }
-        return out;
-    }
-};
-
-}  // namespace bzk
-
-#include "host_mpn_types.h"  // Money, MpnAccount, MpnTx, {Update,Deposit,Withdraw}Transition
+#include "host_mpn_world.h"  // SparseTree4, struct bzk_mpn, g_work_error
 #include "host_bincode.h"    // MpnWork <-> bincode bytes (f-2: the prover's wire format)
 
 using namespace bzk;
-
-// ------------------------------------------------------------------------------------------------
-// the MPN world (RAM state) - opaque handle of the C ABI
-// ------------------------------------------------------------------------------------------------
-struct bzk_mpn {
-    int L, T;
-    ZkScalar token_default, tokens_tree_default, account_default;
-    std::unique_ptr<SparseTree4> accounts, empty_tokens;
-    std::map<uint64_t, MpnAccount> acct;
-    std::map<uint64_t, JubjubPrivateKey> keys;
-    std::vector<MpnTx> mempool;
-    std::vector<DepositTx> deposit_queue;
-    std::vector<WithdrawTx> withdraw_queue;
-    uint64_t height = 0;
-    ZkScalar contract_id = ZkScalar::from_u64(0x4D504E);  // ContractId::Custom of the MPN contract (payments of synthetic txs)
-    int threads = host_default_threads();  // the CPUs this process may use (visible ones capped by the cgroup quota); bzk_mpn_set_threads overrides
-    bzk_ctx* dev = nullptr;  // bzk_mpn_set_device: the witness builders hash their Merkle updates in batches on this context
-    bool defer = false;      // bzk_mpn_set_defer: witness-only Update instances leave the hash-dependent values to the device (host_r1cs.h DeferProgram)
-    bool defer_sig = false;  // bzk_mpn_set_defer_sig: ... and the signature gadget's ladders (implies `defer`)
-    std::string dev_error;
-
-    bzk_mpn(int l, int t) : L(l), T(t) {
-        token_default = token_leaf(Money());
-        empty_tokens.reset(new SparseTree4(T, token_default));
-        tokens_tree_default = empty_tokens->root();
-        account_default = account_hash(MpnAccount());
-        accounts.reset(new SparseTree4(L, account_default));
-    }
-    SparseTree4 tokens_tree(const MpnAccount& a) const {
-        SparseTree4 t = *empty_tokens;  // copy of the empty tree (defaults computed once)
-        for (auto& kv : a.tokens) t.set_leaf(kv.first, token_leaf(kv.second));
-        return t;
-    }
-    void set_with_tokens_root(uint64_t i, const MpnAccount& a, const ZkScalar& tokens_root) {
-        acct[i] = a;
-        ZkScalar v[5] = {ZkScalar::from_u64(a.tx_nonce), ZkScalar::from_u64(a.withdraw_nonce), a.address.x, a.address.y, tokens_root};
-        accounts->set_leaf(i, poseidon_hash(v, 5));
-    }
-    ZkScalar tokens_hash(const MpnAccount& a) const { return a.tokens.empty() ? tokens_tree_default : tokens_tree(a).root(); }
-    ZkScalar account_hash(const MpnAccount& a) const {
-        ZkScalar v[5] = {ZkScalar::from_u64(a.tx_nonce), ZkScalar::from_u64(a.withdraw_nonce), a.address.x, a.address.y, tokens_hash(a)};
-        return poseidon_hash(v, 5);
-    }
-    MpnAccount get(uint64_t i) const {
-        auto it = acct.find(i);
-        return it == acct.end() ? MpnAccount() : it->second;
-    }
-    void set(uint64_t i, const MpnAccount& a) {
-        acct[i] = a;
-        accounts->set_leaf(i, account_hash(a));
-    }
-};
 
 struct bzk_r1cs {
     ConstraintSystem cs;
@@ -2037,8 +1936,9 @@ struct bzk_mpn_work {
     MpnWork w;
 };
 
+thread_local std::string bzk::g_work_error;  // host_mpn_world.h
+
 namespace {
-thread_local std::string g_work_error;
 
 // root of the 4-ary tree after the leaf at `index` is replaced (calc_root of the merkle gadget, natively)
 ZkScalar root_from_path(const Proof4& proof, uint64_t index, ZkScalar node) {
@@ -2403,618 +2303,6 @@ int32_t bzk_host_jubjub_verify(const uint8_t pub_xy[64], const uint8_t msg[32], 
     PointAffine pk = {ZkScalar::from_bytes(pub_xy), ZkScalar::from_bytes(pub_xy + 32)};
     JubjubSignature s = {{ZkScalar::from_bytes(sig), ZkScalar::from_bytes(sig + 32)}, ZkScalar::from_bytes(sig + 64)};
     return jubjub_verify(pk, ZkScalar::from_bytes(msg), s) ? 1 : 0;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Wire-form transactions: bincode(MpnTransaction) records in, signature verdicts out (bzk_mpn_tx_verify_batch), accepted ones queued
-// (bzk_mpn_push_txs).  The parser below only cuts byte ranges, reads integers and maps ContractId tags: no field arithmetic, so that the device
-// path (eddsa.hip mpn_tx_verify_run) leaves none on the host.
-// ------------------------------------------------------------------------------------------------
-namespace bzk {
-namespace {
-struct TxParsed {
-    std::vector<uint8_t> src_x, dst_x, src_odd, dst_odd, tok, sig;
-    std::vector<uint64_t> nums;
-    TxSoA soa() const { return {src_x.data(), dst_x.data(), src_odd.data(), dst_odd.data(), tok.data(), nums.data(), sig.data()}; }
-};
-// ContractId as the scalar the circuits use, copied as bytes (Null = 0, Ziesha = 1: constants)
-void parse_contract_id(BinReader& r, uint8_t out[32]) {
-    const uint32_t tag = r.u32("ContractId tag");
-    memset(out, 0, 32);
-    if (tag == 0) return;
-    if (tag == 1) return ZkScalar::one().to_bytes(out);
-    if (tag == 2) {
-        if (const uint8_t* b = r.bytes(32, "ContractId::Custom")) memcpy(out, b, 32);
-        return;
-    }
-    r.fail("ContractId variant");
-}
-bool parse_txs(const uint8_t* txs, uint64_t len, uint64_t n, TxParsed& P, std::string& err) {
-    if (n > len / 190) {  // the shortest record: 4 + 2 x 33 + 2 x 12 + 96
-        err = "fewer bytes than " + std::to_string(n) + " MpnTransaction records need";
-        return false;
-    }
-    P.src_x.resize(n * 32); P.dst_x.resize(n * 32); P.src_odd.resize(n); P.dst_odd.resize(n);
-    P.tok.resize(n * 64); P.sig.resize(n * 96); P.nums.resize(n * 3);
-    BinReader r(txs, (size_t)len);
-    for (uint64_t i = 0; i < n && r.ok; ++i) {
-        P.nums[3 * i] = r.u32("MpnTransaction.nonce");
-        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.src_x[32 * i], b, 32);
-        P.src_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
-        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.dst_x[32 * i], b, 32);
-        P.dst_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
-        parse_contract_id(r, &P.tok[64 * i]);
-        P.nums[3 * i + 1] = r.u64("Amount");
-        parse_contract_id(r, &P.tok[64 * i + 32]);
-        P.nums[3 * i + 2] = r.u64("Amount");
-        if (const uint8_t* b = r.bytes(96, "Signature")) memcpy(&P.sig[96 * i], b, 96);
-        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
-    }
-    if (r.ok && r.pos != len) r.fail("bytes after the last record");
-    err = r.err;
-    return r.ok;
-}
-bool limbs_of_a_residue(const uint8_t b[32]) {  // value < r (`from_repr` refuses anything else)
-    uint32_t l[8];
-    memcpy(l, b, 32);
-    uint64_t borrow = 0;
-    for (int i = 0; i < 8; ++i) borrow = (((uint64_t)l[i] - FrParams::MOD[i] - borrow) >> 63) & 1;
-    return borrow != 0;
-}
-// PointCompressed::decompress with the reference's panic (no square root) and a non-residue's limbs reported as false
-bool decompress_checked(const uint8_t x[32], bool odd, PointAffine& out) {
-    out = PointAffine();
-    if (!limbs_of_a_residue(x)) return false;
-    const ZkScalar xs = ZkScalar::from_bytes(x), xx = xs.square();
-    ZkScalar y;
-    if (!((ZkScalar::one() - jubjub_d() * xx).invert() * (ZkScalar::one() + xx)).sqrt(&y)) return false;
-    if (y.is_odd() != odd) y = -y;
-    out = {xs, y};
-    return true;
-}
-// record i on the host: the verdict, and the transaction with its keys decompressed (hash_ok: dst decompressed and the token ids are residues)
-bool tx_verify_host(const TxParsed& P, uint64_t i, MpnTx& tx, bool& hash_ok) {
-    const bool src_ok = decompress_checked(&P.src_x[32 * i], P.src_odd[i] != 0, tx.src_pub);
-    const bool dst_ok = decompress_checked(&P.dst_x[32 * i], P.dst_odd[i] != 0, tx.dst_pub);
-    hash_ok = dst_ok && limbs_of_a_residue(&P.tok[64 * i]) && limbs_of_a_residue(&P.tok[64 * i + 32]);
-    bool sig_ok = true;
-    for (int k = 0; k < 3; ++k) sig_ok = sig_ok && limbs_of_a_residue(&P.sig[96 * i + 32 * k]);
-    tx.nonce = (uint32_t)P.nums[3 * i];
-    tx.amount = Money{ZkScalar::from_bytes(&P.tok[64 * i]), P.nums[3 * i + 1]};
-    tx.fee = Money{ZkScalar::from_bytes(&P.tok[64 * i + 32]), P.nums[3 * i + 2]};
-    tx.sig = {{ZkScalar::from_bytes(&P.sig[96 * i]), ZkScalar::from_bytes(&P.sig[96 * i + 32])}, ZkScalar::from_bytes(&P.sig[96 * i + 64])};
-    return src_ok && hash_ok && sig_ok && jubjub_verify(tx.src_pub, tx.hash(), tx.sig);
-}
-// all records: on the device when ctx is set, else on `threads` host threads.  txs_out (may be null): the transactions with decompressed keys
-int32_t tx_verify_all(bzk_ctx* ctx, int threads, const TxParsed& P, uint64_t n, uint8_t* ok, uint8_t* hash_out, std::vector<MpnTx>* txs_out) {
-    if (txs_out) txs_out->assign(n, MpnTx());
-    if (ctx) {
-        std::vector<uint8_t> sxy, dxy;
-        if (txs_out) { sxy.resize(n * 64); dxy.resize(n * 64); }
-        BZK_TRY(mpn_tx_verify_run(ctx, P.soa(), n, ok, hash_out, txs_out ? sxy.data() : nullptr, txs_out ? dxy.data() : nullptr));
-        for (uint64_t i = 0; txs_out && i < n; ++i) {
-            if (!ok[i]) continue;  // only verified records are looked at again
-            MpnTx& tx = (*txs_out)[i];
-            tx.nonce = (uint32_t)P.nums[3 * i];
-            tx.src_pub = {ZkScalar::from_bytes(&sxy[64 * i]), ZkScalar::from_bytes(&sxy[64 * i + 32])};
-            tx.dst_pub = {ZkScalar::from_bytes(&dxy[64 * i]), ZkScalar::from_bytes(&dxy[64 * i + 32])};
-            tx.amount = Money{ZkScalar::from_bytes(&P.tok[64 * i]), P.nums[3 * i + 1]};
-            tx.fee = Money{ZkScalar::from_bytes(&P.tok[64 * i + 32]), P.nums[3 * i + 2]};
-            tx.sig = {{ZkScalar::from_bytes(&P.sig[96 * i]), ZkScalar::from_bytes(&P.sig[96 * i + 32])}, ZkScalar::from_bytes(&P.sig[96 * i + 64])};
-        }
-        return BZK_OK;
-    }
-    std::atomic<uint64_t> next(0);
-    auto worker = [&] {
-        for (;;) {
-            const uint64_t i = next.fetch_add(1);
-            if (i >= n) break;
-            MpnTx local;
-            MpnTx& tx = txs_out ? (*txs_out)[i] : local;
-            bool hash_ok;
-            ok[i] = tx_verify_host(P, i, tx, hash_ok) ? 1 : 0;
-            if (hash_out) {
-                if (hash_ok) tx.hash().to_bytes(hash_out + 32 * i);
-                else memset(hash_out + 32 * i, 0, 32);
-            }
-        }
-    };
-    std::vector<std::thread> th;
-    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(threads, 1), n);
-    for (int k = 1; k < nt; ++k) th.emplace_back(worker);
-    worker();
-    for (auto& x : th) x.join();
-    return BZK_OK;
-}
-}  // namespace
-}  // namespace bzk
-
-extern "C" {
-
-int32_t bzk_mpn_tx_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* hash_out) {
-    if (n && (!txs || !ok)) return BZK_E_ARG;
-    if (n == 0 && len == 0) return BZK_OK;
-    try {
-        TxParsed P;
-        if (!parse_txs(txs, len, n, P, g_work_error)) return BZK_E_ARG;
-        return tx_verify_all(ctx, host_default_threads(), P, n, ok, hash_out, nullptr);
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    }
-}
-
-int32_t bzk_mpn_push_txs(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out) {
-    if (!w || (n && !txs)) return BZK_E_ARG;
-    if (accepted_out) *accepted_out = 0;
-    if (n == 0 && len == 0) return BZK_OK;
-    try {
-        TxParsed P;
-        if (!parse_txs(txs, len, n, P, g_work_error)) return BZK_E_ARG;
-        std::vector<uint8_t> ok(n);
-        std::vector<MpnTx> parsed;
-        if (const int32_t st = tx_verify_all(w->dev, w->threads, P, n, ok.data(), nullptr, &parsed); st != BZK_OK) {
-            if (w->dev) w->dev_error = bzk_last_error(w->dev);
-            return st;
-        }
-        uint64_t accepted = 0;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (!ok[i]) continue;
-            w->mempool.push_back(parsed[i]);
-            ++accepted;
-        }
-        if (ok_out) memcpy(ok_out, ok.data(), n);
-        if (accepted_out) *accepted_out = accepted;
-        return BZK_OK;
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    }
-}
-
-int32_t bzk_host_jubjub_decompress(const uint8_t x[32], int32_t odd, uint8_t xy_out[64]) {
-    if (!x || !xy_out) return BZK_E_ARG;
-    PointAffine p;
-    const bool ok = decompress_checked(x, odd != 0, p);
-    p.x.to_bytes(xy_out);
-    p.y.to_bytes(xy_out + 32);
-    return ok ? 1 : 0;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Wire-form withdrawals: bincode(MpnWithdraw) records in, verdicts and fingerprints out (bzk_mpn_withdraw_verify_batch), accepted ones queued with
-// their payment bytes (bzk_mpn_push_withdraws).  As above the parser only cuts byte ranges, reads integers and maps ContractId tags: no hashing
-// and no field arithmetic, so that the device path (eddsa.hip mpn_withdraw_verify_run) leaves none on the host.
-// ------------------------------------------------------------------------------------------------
-namespace bzk {
-namespace {
-struct WdParsed {
-    const uint8_t* txs = nullptr;
-    std::vector<uint64_t> rec_off, pay_off, amounts;  // amounts n x 2: amount, fee
-    std::vector<uint32_t> pay_len, cd_off, nonce, circuit;
-    std::vector<uint8_t> key_x, key_odd, sig, cid, tok;  // cid n x 32: payment.contract_id as a scalar; tok n x 64: amount | fee token ids
-    WdSoA soa() const {
-        return {txs, rec_off.data(), pay_off.data(), pay_len.data(), cd_off.data(), key_x.data(), key_odd.data(), nonce.data(), sig.data()};
-    }
-};
-bool parse_withdraws(const uint8_t* txs, uint64_t len, uint64_t n, WdParsed& P, std::string& err) {
-    if (n > len / 245) {  // the shortest record: 33 + 4 + 96 + (8 + 4 + 4 + 32 + 40 + 2 x 12)
-        err = "fewer bytes than " + std::to_string(n) + " MpnWithdraw records need";
-        return false;
-    }
-    P.txs = txs;
-    P.rec_off.resize(n + 1); P.pay_off.resize(n); P.amounts.resize(2 * n);
-    P.pay_len.resize(n); P.cd_off.resize(n); P.nonce.resize(n); P.circuit.resize(n);
-    P.key_x.resize(n * 32); P.key_odd.resize(n); P.sig.resize(n * 96); P.cid.resize(n * 32); P.tok.resize(n * 64);
-    BinReader r(txs, (size_t)len);
-    for (uint64_t i = 0; i < n && r.ok; ++i) {
-        P.rec_off[i] = r.pos;
-        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.key_x[32 * i], b, 32);
-        P.key_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
-        P.nonce[i] = r.u32("MpnWithdraw.mpn_withdraw_nonce");
-        if (const uint8_t* b = r.bytes(96, "Signature")) memcpy(&P.sig[96 * i], b, 96);
-        P.pay_off[i] = r.pos;
-        skip_string(r);
-        parse_contract_id(r, &P.cid[32 * i]);
-        P.circuit[i] = r.u32("withdraw_circuit_id");
-        P.cd_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
-        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail("ContractWithdraw longer than 65536 bytes");
-        r.bytes(32, "calldata");
-        skip_l1_pub(r);
-        parse_contract_id(r, &P.tok[64 * i]);
-        P.amounts[2 * i] = r.u64("Amount");
-        parse_contract_id(r, &P.tok[64 * i + 32]);
-        P.amounts[2 * i + 1] = r.u64("Amount");
-        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail("ContractWithdraw longer than 65536 bytes");
-        P.pay_len[i] = (uint32_t)(r.pos - P.pay_off[i]);
-        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
-    }
-    if (r.ok) P.rec_off[n] = r.pos;
-    if (r.ok && r.pos != len) r.fail("bytes after the last record");
-    err = r.err;
-    return r.ok;
-}
-// record i on the host: the two verdict bits, the fingerprint, and the withdrawal with its key decompressed
-uint8_t withdraw_verify_host(const WdParsed& P, uint64_t i, WithdrawTx& tx) {
-    const bool key_ok = decompress_checked(&P.key_x[32 * i], P.key_odd[i] != 0, tx.mpn_address);
-    bool sig_ok = true;
-    for (int k = 0; k < 3; ++k) sig_ok = sig_ok && limbs_of_a_residue(&P.sig[96 * i + 32 * k]);
-    tx.nonce = P.nonce[i];
-    tx.sig = {{ZkScalar::from_bytes(&P.sig[96 * i]), ZkScalar::from_bytes(&P.sig[96 * i + 32])}, ZkScalar::from_bytes(&P.sig[96 * i + 64])};
-    tx.amount = Money{ZkScalar::from_bytes(&P.tok[64 * i]), P.amounts[2 * i]};
-    tx.fee = Money{ZkScalar::from_bytes(&P.tok[64 * i + 32]), P.amounts[2 * i + 1]};
-    tx.payment.assign(P.txs + P.pay_off[i], P.txs + P.pay_off[i] + P.pay_len[i]);
-    std::vector<uint8_t> blanked = tx.payment;
-    memset(blanked.data() + P.cd_off[i], 0, 32);
-    tx.fingerprint = hash_to_scalar(blanked.data(), blanked.size());
-    if (!key_ok || !sig_ok) return 0;
-    uint8_t calldata[32];
-    tx.calldata().to_bytes(calldata);
-    return (uint8_t)((jubjub_verify(tx.mpn_address, tx.sign_message(), tx.sig) ? 1 : 0) |
-                     (memcmp(calldata, tx.payment.data() + P.cd_off[i], 32) == 0 ? 2 : 0));
-}
-// all records: on the device when ctx is set, else on `threads` host threads.  out (may be null): the withdrawals as they would be queued
-int32_t withdraw_verify_all(bzk_ctx* ctx, int threads, const WdParsed& P, uint64_t n, uint8_t* ok, uint8_t* fp_out, std::vector<WithdrawTx>* out) {
-    if (out) out->assign(n, WithdrawTx());
-    if (ctx) {
-        std::vector<uint8_t> xy, fp;
-        if (out) { xy.resize(n * 64); fp.resize(n * 32); }
-        uint8_t* fpp = out ? fp.data() : fp_out;
-        BZK_TRY(mpn_withdraw_verify_run(ctx, P.soa(), n, ok, fpp, out ? xy.data() : nullptr));
-        if (out && fp_out) memcpy(fp_out, fp.data(), n * 32);
-        for (uint64_t i = 0; out && i < n; ++i) {
-            if (ok[i] != 3) continue;  // only admissible records are looked at again
-            WithdrawTx& tx = (*out)[i];
-            tx.mpn_address = {ZkScalar::from_bytes(&xy[64 * i]), ZkScalar::from_bytes(&xy[64 * i + 32])};
-            tx.nonce = P.nonce[i];
-            tx.sig = {{ZkScalar::from_bytes(&P.sig[96 * i]), ZkScalar::from_bytes(&P.sig[96 * i + 32])}, ZkScalar::from_bytes(&P.sig[96 * i + 64])};
-            tx.amount = Money{ZkScalar::from_bytes(&P.tok[64 * i]), P.amounts[2 * i]};
-            tx.fee = Money{ZkScalar::from_bytes(&P.tok[64 * i + 32]), P.amounts[2 * i + 1]};
-            tx.fingerprint = ZkScalar::from_bytes(&fp[32 * i]);
-            tx.payment.assign(P.txs + P.pay_off[i], P.txs + P.pay_off[i] + P.pay_len[i]);
-        }
-        return BZK_OK;
-    }
-    std::atomic<uint64_t> next(0);
-    auto worker = [&] {
-        for (;;) {
-            const uint64_t i = next.fetch_add(1);
-            if (i >= n) break;
-            WithdrawTx local;
-            WithdrawTx& tx = out ? (*out)[i] : local;
-            ok[i] = withdraw_verify_host(P, i, tx);
-            if (fp_out) tx.fingerprint.to_bytes(fp_out + 32 * i);
-        }
-    };
-    std::vector<std::thread> th;
-    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(threads, 1), n);
-    for (int k = 1; k < nt; ++k) th.emplace_back(worker);
-    worker();
-    for (auto& x : th) x.join();
-    return BZK_OK;
-}
-}  // namespace
-}  // namespace bzk
-
-extern "C" {
-
-int32_t bzk_mpn_withdraw_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* fingerprint_out) {
-    if (n && (!txs || !ok)) return BZK_E_ARG;
-    if (n == 0 && len == 0) return BZK_OK;
-    try {
-        WdParsed P;
-        if (!parse_withdraws(txs, len, n, P, g_work_error)) return BZK_E_ARG;
-        return withdraw_verify_all(ctx, host_default_threads(), P, n, ok, fingerprint_out, nullptr);
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    }
-}
-
-int32_t bzk_mpn_push_withdraws(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out) {
-    if (!w || (n && !txs)) return BZK_E_ARG;
-    if (accepted_out) *accepted_out = 0;
-    if (n == 0 && len == 0) return BZK_OK;
-    try {
-        WdParsed P;
-        if (!parse_withdraws(txs, len, n, P, g_work_error)) return BZK_E_ARG;
-        std::vector<uint8_t> ok(n);
-        std::vector<WithdrawTx> parsed;
-        if (const int32_t st = withdraw_verify_all(w->dev, w->threads, P, n, ok.data(), nullptr, &parsed); st != BZK_OK) {
-            if (w->dev) w->dev_error = bzk_last_error(w->dev);
-            return st;
-        }
-        uint8_t world_id[32];
-        w->contract_id.to_bytes(world_id);
-        uint64_t accepted = 0;
-        for (uint64_t i = 0; i < n; ++i) {
-            // mempool.rs:246-258 for a withdrawal: the payment is for this contract's withdraw circuit 0 and signed; calldata as withdraw.rs:77 checks it
-            const bool admit = ok[i] == 3 && memcmp(&P.cid[32 * i], world_id, 32) == 0 && P.circuit[i] == 0 &&
-                               limbs_of_a_residue(&P.tok[64 * i]) && limbs_of_a_residue(&P.tok[64 * i + 32]);
-            ok[i] = admit ? 1 : 0;
-            if (!admit) continue;
-            w->withdraw_queue.push_back(std::move(parsed[i]));
-            ++accepted;
-        }
-        if (ok_out) memcpy(ok_out, ok.data(), n);
-        if (accepted_out) *accepted_out = accepted;
-        return BZK_OK;
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    }
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Wire-form deposits: bincode(MpnDeposit) records in, verdicts and decompressed addresses out (bzk_mpn_deposit_verify_batch), accepted ones queued
-// with their payment bytes (bzk_mpn_push_deposits).  The parser only cuts byte ranges and reads integers and tags; the Ed25519 check of
-// ContractDeposit::verify_signature (src/core/transaction.rs:192-202) is eddsa.hip's, on the device or - the same per-lane code - on host threads.
-// ------------------------------------------------------------------------------------------------
-namespace bzk {
-namespace {
-std::atomic<uint32_t> g_wire_flags(0);  // bzk_mpn_set_wire_flags
-struct DpParsed {
-    const uint8_t* txs = nullptr;
-    std::vector<uint64_t> rec_off, pay_off, amount;
-    std::vector<uint32_t> pay_len, tag_off, src_off, sig_off, circuit;
-    std::vector<uint8_t> has_sig, key_x, key_odd, cid, tok;  // cid n x 32: payment.contract_id as a scalar; tok n x 32: amount.token_id
-    DpSoA soa() const {
-        return {txs, rec_off.data(), pay_off.data(), tag_off.data(), src_off.data(), sig_off.data(), has_sig.data(), key_x.data(), key_odd.data()};
-    }
-};
-bool parse_deposits(const uint8_t* txs, uint64_t len, uint64_t n, uint32_t flags, DpParsed& P, std::string& err) {
-    if (n > len / 150) {  // the shortest record: 33 + (8 + 4 + 4 + 32 + 40 + 2 x 12 + 4 + 1)
-        err = "fewer bytes than " + std::to_string(n) + " MpnDeposit records need";
-        return false;
-    }
-    P.txs = txs;
-    P.rec_off.resize(n + 1); P.pay_off.resize(n); P.amount.resize(n);
-    P.pay_len.resize(n); P.tag_off.resize(n); P.src_off.resize(n); P.sig_off.resize(n); P.circuit.resize(n);
-    P.has_sig.resize(n); P.key_x.resize(n * 32); P.key_odd.resize(n); P.cid.resize(n * 32); P.tok.resize(n * 32);
-    BinReader r(txs, (size_t)len);
-    uint8_t fee_tok[32];
-    const char* too_long = "ContractDeposit longer than 65536 bytes";
-    for (uint64_t i = 0; i < n && r.ok; ++i) {
-        P.rec_off[i] = r.pos;
-        if (const uint8_t* b = r.bytes(32, "PointCompressed.0")) memcpy(&P.key_x[32 * i], b, 32);
-        P.key_odd[i] = r.boolean("PointCompressed.1") ? 1 : 0;
-        P.pay_off[i] = r.pos;
-        skip_string(r);
-        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail(too_long);
-        parse_contract_id(r, &P.cid[32 * i]);
-        P.circuit[i] = r.u32("deposit_circuit_id");
-        r.bytes(32, "calldata");
-        if (r.u64("ed25519 public key length") != 32) r.fail("ed25519 public key length");
-        P.src_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
-        r.bytes(32, "ed25519 public key");
-        parse_contract_id(r, &P.tok[32 * i]);
-        P.amount[i] = r.u64("Amount");
-        parse_contract_id(r, fee_tok);
-        r.u64("Amount");
-        r.u32("nonce");
-        P.tag_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
-        const uint8_t some = r.u8("Option<Signature> tag");
-        if (r.ok && some > 1) r.fail("Option tag");
-        P.has_sig[i] = some == 1;
-        P.sig_off[i] = 0;
-        if (r.ok && some) {
-            if (flags & BZK_WORK_SIG_LEN_PREFIXED)
-                if (r.u64("ed25519 signature length") != 64) r.fail("ed25519 signature length");
-            P.sig_off[i] = (uint32_t)(r.pos - P.pay_off[i]);
-            r.bytes(64, "ed25519 signature");
-        }
-        if (r.ok && r.pos - P.pay_off[i] > MPN_WD_PAYMENT_MAX) r.fail(too_long);
-        P.pay_len[i] = (uint32_t)(r.pos - P.pay_off[i]);
-        if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
-    }
-    if (r.ok) P.rec_off[n] = r.pos;
-    if (r.ok && r.pos != len) r.fail("bytes after the last record");
-    err = r.err;
-    return r.ok;
-}
-// all records: on the device when ctx is set, else on `threads` host threads; xy n x 64: the decompressed addresses (zeros where there is none)
-int32_t deposit_verify_all(bzk_ctx* ctx, int threads, const DpParsed& P, uint64_t n, uint8_t* ok, uint8_t* xy) {
-    if (ctx) return mpn_deposit_verify_run(ctx, P.soa(), n, ok, xy);
-    const DpSoA t = P.soa();
-    std::atomic<uint64_t> next(0);
-    auto worker = [&] {
-        for (;;) {
-            const uint64_t i = next.fetch_add(1);
-            if (i >= n) break;
-            PointAffine a;
-            const bool key_ok = decompress_checked(&P.key_x[32 * i], P.key_odd[i] != 0, a);
-            ok[i] = (uint8_t)(mpn_deposit_sig_host(t, i) | (key_ok ? 2 : 0));
-            if (xy) {
-                a.x.to_bytes(xy + 64 * i);
-                a.y.to_bytes(xy + 64 * i + 32);
-            }
-        }
-    };
-    std::vector<std::thread> th;
-    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(threads, 1), n);
-    for (int k = 1; k < nt; ++k) th.emplace_back(worker);
-    worker();
-    for (auto& x : th) x.join();
-    return BZK_OK;
-}
-}  // namespace
-}  // namespace bzk
-
-extern "C" {
-
-int32_t bzk_mpn_set_wire_flags(uint32_t flags) {
-    if (flags & ~BZK_WORK_SIG_LEN_PREFIXED) return BZK_E_ARG;
-    g_wire_flags.store(flags);
-    return BZK_OK;
-}
-
-int32_t bzk_mpn_deposit_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* addr_xy_out) {
-    if (n && (!txs || !ok)) return BZK_E_ARG;
-    if (n == 0 && len == 0) return BZK_OK;
-    try {
-        DpParsed P;
-        if (!parse_deposits(txs, len, n, g_wire_flags.load(), P, g_work_error)) return BZK_E_ARG;
-        return deposit_verify_all(ctx, host_default_threads(), P, n, ok, addr_xy_out);
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    }
-}
-
-int32_t bzk_mpn_push_deposits(bzk_mpn* w, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok_out, uint64_t* accepted_out) {
-    if (!w || (n && !txs)) return BZK_E_ARG;
-    if (accepted_out) *accepted_out = 0;
-    if (n == 0 && len == 0) return BZK_OK;
-    try {
-        DpParsed P;
-        if (!parse_deposits(txs, len, n, g_wire_flags.load(), P, g_work_error)) return BZK_E_ARG;
-        std::vector<uint8_t> ok(n), xy(n * 64);
-        if (const int32_t st = deposit_verify_all(w->dev, w->threads, P, n, ok.data(), xy.data()); st != BZK_OK) {
-            if (w->dev) w->dev_error = bzk_last_error(w->dev);
-            return st;
-        }
-        uint8_t world_id[32];
-        w->contract_id.to_bytes(world_id);
-        uint64_t accepted = 0;
-        for (uint64_t i = 0; i < n; ++i) {
-            // mempool.rs:241-258 for a deposit: the payment is for this contract's deposit circuit 0 and signed; the address as apply_deposit.rs:8 needs it
-            const bool admit = ok[i] == 3 && memcmp(&P.cid[32 * i], world_id, 32) == 0 && P.circuit[i] == 0 && limbs_of_a_residue(&P.tok[32 * i]);
-            ok[i] = admit ? 1 : 0;
-            if (!admit) continue;
-            DepositTx tx;
-            tx.mpn_address = {ZkScalar::from_bytes(&xy[64 * i]), ZkScalar::from_bytes(&xy[64 * i + 32])};
-            tx.amount = Money{ZkScalar::from_bytes(&P.tok[32 * i]), P.amount[i]};
-            tx.payment.assign(P.txs + P.pay_off[i], P.txs + P.pay_off[i] + P.pay_len[i]);
-            w->deposit_queue.push_back(std::move(tx));
-            ++accepted;
-        }
-        if (ok_out) memcpy(ok_out, ok.data(), n);
-        if (accepted_out) *accepted_out = accepted;
-        return BZK_OK;
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    }
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Wire-form L1 transactions: bincode(Transaction) / bincode(TransactionAndDelta) records in, verify_signature verdicts and Transaction::hash out
-// (bzk_l1_tx_verify_batch); whole block bodies in, per-block verdict and Merkle root out (bzk_block_bodies_check).  The parser is
-// host_bincode.h's parse_l1_txs (structure only); hashing, Ed25519 and the trees are eddsa.hip's, on the device or on host threads.
-// ------------------------------------------------------------------------------------------------
-extern "C" {
-
-int32_t bzk_l1_tx_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, uint8_t* ok, uint8_t* hash_out) {
-    if (form > BZK_L1_FORM_TX_AND_DELTA || (n && (!txs || !ok))) return BZK_E_ARG;
-    if (n == 0 && len == 0) return BZK_OK;
-    try {
-        L1Parsed P;
-        if (!parse_l1_txs(txs, len, n, form == BZK_L1_FORM_TX_AND_DELTA, g_wire_flags.load(), P, g_work_error)) return BZK_E_ARG;
-        if (ctx) return l1_check_run(ctx, P.soa(), n, nullptr, 0, ok, hash_out, nullptr, nullptr);
-        return l1_check_host(host_default_threads(), P.soa(), n, nullptr, 0, ok, hash_out, nullptr, nullptr);
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    }
-}
-
-int32_t bzk_block_bodies_check(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, const uint64_t* count, uint64_t m, uint8_t* sig_ok_out,
-                               uint8_t* root_out, uint8_t* tx_ok_out, uint8_t* hash_out) {
-    if (m && (!count || !sig_ok_out || !root_out)) return BZK_E_ARG;
-    if (m == 0 && len == 0) return BZK_OK;
-    uint64_t n = 0;
-    for (uint64_t j = 0; j < m; ++j) {
-        if (count[j] > len) return BZK_E_ARG;  // a record is tens of bytes: also keeps the sum from wrapping
-        n += count[j];
-    }
-    if (n && !txs) return BZK_E_ARG;
-    try {
-        L1Parsed P;
-        if (!parse_l1_txs(txs, len, n, false, g_wire_flags.load(), P, g_work_error)) return BZK_E_ARG;
-        if (ctx) return l1_check_run(ctx, P.soa(), n, count, m, tx_ok_out, hash_out, sig_ok_out, root_out);
-        return l1_check_host(host_default_threads(), P.soa(), n, count, m, tx_ok_out, hash_out, sig_ok_out, root_out);
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    }
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------------------
-// Wire-form ContractUpdates: bincode(ContractUpdate) records of one contract in, per-update verdict bits, aux data and commitments out
-// (bzk_contract_updates_check); and the parse-only helper that cuts those records out of L1 transactions (bzk_l1_tx_updates).  The parser is
-// host_bincode.h's parse_contract_updates (structure only); everything computed is updates.hip's, on the device or on host threads.
-// ------------------------------------------------------------------------------------------------
-namespace bzk {
-int32_t contract_updates_run(bzk_ctx* ctx, const bzk_contract_desc& c, UpdParsed& P, const uint64_t* count, uint64_t m, uint64_t height0,
-                             const uint8_t state0[32], uint8_t* ok, uint8_t* aux_out, uint8_t* commit_out);  // updates.hip
-}
-
-extern "C" {
-
-int32_t bzk_contract_updates_check(bzk_ctx* ctx, const bzk_contract_desc* c, const uint8_t* updates, uint64_t len, const uint64_t* count, uint64_t m,
-                                   uint64_t height0, const uint8_t state0[32], uint8_t* ok, uint8_t* aux_out, uint8_t* commit_out) {
-    if (m && !count) {
-        g_work_error = "count is NULL with transactions to check";
-        return BZK_E_ARG;
-    }
-    uint64_t n = 0;
-    for (uint64_t j = 0; j < m; ++j) {
-        if (count[j] > len) {  // a record is hundreds of bytes: also keeps the sum from wrapping
-            g_work_error = "the counts name more records than the input can hold";
-            return BZK_E_ARG;
-        }
-        n += count[j];
-    }
-    if (n == 0 && len == 0) return BZK_OK;
-    if (!c || (n && (!updates || !state0 || !ok))) {
-        g_work_error = "a pointer is NULL with records to check";
-        return BZK_E_ARG;
-    }
-    if ((c->n_deposit_fns && !c->deposit_fns) || (c->n_withdraw_fns && !c->withdraw_fns) || (c->n_fns && !c->fns)) {
-        g_work_error = "a function table is NULL with a non-zero count";
-        return BZK_E_ARG;
-    }
-    const bzk_contract_fn* tab[3] = {c->deposit_fns, c->withdraw_fns, c->fns};
-    const uint32_t cnt[3] = {c->n_deposit_fns, c->n_withdraw_fns, c->n_fns};
-    for (int t = 0; t < 3; ++t)
-        for (uint32_t k = 0; k < cnt[t]; ++k) {
-            if (!tab[t][k].vk || tab[t][k].vk_len < 878) {
-                g_work_error = "function " + std::to_string(k) + ": a verifying key is at least 878 bytes";
-                return BZK_E_ARG;
-            }
-            if (t < 2 && tab[t][k].log4_payment_capacity > upd::MAX_CAPACITY) {
-                g_work_error = "function " + std::to_string(k) + ": log4_payment_capacity above 8";
-                return BZK_E_ARG;
-            }
-        }
-    try {
-        UpdParsed P;
-        if (!parse_contract_updates(updates, len, n, g_wire_flags.load(), c->contract_id, P, g_work_error)) return BZK_E_ARG;
-        return contract_updates_run(ctx, *c, P, count, m, height0, state0, ok, aux_out, commit_out);
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    }
-}
-
-int32_t bzk_l1_tx_updates(const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, const uint8_t contract_id[32], uint64_t* spans_out, uint64_t cap,
-                          uint64_t* n_out) {
-    if (form > BZK_L1_FORM_TX_AND_DELTA || !contract_id || !n_out || (n && !txs) || (cap && !spans_out)) return BZK_E_ARG;
-    *n_out = 0;
-    if (n == 0 && len == 0) return BZK_OK;
-    try {
-        L1Parsed P;
-        UpdSpans S;
-        S.cid = contract_id;
-        if (!parse_l1_txs(txs, len, n, form == BZK_L1_FORM_TX_AND_DELTA, g_wire_flags.load(), P, g_work_error, &S)) return BZK_E_ARG;
-        const uint64_t found = S.out.size() / 3;
-        if (found && cap) memcpy(spans_out, S.out.data(), (size_t)std::min(found, cap) * 24);
-        *n_out = found;
-        return BZK_OK;
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    }
 }
 
 }  // extern "C"

@@ -14,18 +14,16 @@
 // Stage 2, per key group, one after another: verify.hip's three kernels over the group's inputs and proofs, in rounds of 2^16 proofs.
 // Stage 3: upd_verdict scatters the group verdicts back to update order and ORs in the bits.
 // Aux values, commitments, bits and the groups' arrays of all n updates stay on the device between rounds; everything is one WsLayout.
-#include <atomic>
 #include <memory>
-#include <thread>
 
 #include "bzk_updates.cuh"
 #include "bzk_internal.h"
 #include "host_bincode.h"
 #include "host_pairing.h"
+#include "host_threads.h"
 
 namespace bzk {
 
-int host_default_threads();                                                         // host_zk.hip
 int32_t poseidon_consts_dev_shared(bzk_ctx* ctx, int t, const void** out, int* rf, int* rp);  // poseidon.hip
 int32_t poseidon_consts_host29(int t, const Fr29** out, int* rf, int* rp);          // poseidon.hip
 
@@ -103,24 +101,6 @@ __global__ void __launch_bounds__(256) upd_verdict_kernel(const uint32_t* __rest
     if (i >= n) return;
     const uint32_t s = slot[i];
     ok[i] = (uint8_t)(bits[i] | ((s != upd::NO_SLOT && verdict[s]) ? BZK_UPD_PROOF : 0));
-}
-
-// fn(i) for every i < n on up to `threads` host threads
-template <class F>
-void host_for_each(uint64_t n, int threads, F fn) {
-    std::atomic<uint64_t> next(0);
-    auto worker = [&] {
-        for (;;) {
-            const uint64_t i = next.fetch_add(1);
-            if (i >= n) break;
-            fn(i);
-        }
-    };
-    std::vector<std::thread> th;
-    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(threads, 1), n);
-    for (int k = 1; k < nt; ++k) th.emplace_back(worker);
-    worker();
-    for (auto& x : th) x.join();
 }
 
 // ---- the plan: everything below is arithmetic on counts and on the function table; no byte of a payment's values is read

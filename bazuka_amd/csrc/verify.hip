@@ -4,16 +4,11 @@
 // two entry points.  A proof's state lives in its column of a limb-major slab of the call's workspace (pairing::slot), never in private arrays:
 // the kernels differ only in which step they run, so each stays one instruction cache long, has its own launch bounds, and a fault names its stage.
 // No lane waits for another (no LDS, no barrier): a lane that has its verdict simply returns.
-#include <atomic>
-#include <thread>
-
 #include "bzk_internal.h"
 #include "host_pairing.h"
+#include "host_threads.h"
 
 namespace bzk {
-
-int host_default_threads();  // host_zk.hip
-
 namespace {
 
 using pairing::KeyView;
@@ -55,23 +50,6 @@ __global__ void __launch_bounds__(G16V_BLOCK) g16v_finalexp_kernel(KeyDev k, uin
     ok[i] = pairing::finalexp_one(Lane28{slab + i, stride}, k) ? 1 : 0;
 }
 
-// fn(i) for every i < n on up to `threads` host threads
-template <class F>
-void host_for_each(uint64_t n, int threads, F fn) {
-    std::atomic<uint64_t> next(0);
-    auto worker = [&] {
-        for (;;) {
-            const uint64_t i = next.fetch_add(1);
-            if (i >= n) break;
-            fn(i);
-        }
-    };
-    std::vector<std::thread> th;
-    const int nt = (int)std::min<uint64_t>((uint64_t)std::max(threads, 1), n);
-    for (int k = 1; k < nt; ++k) th.emplace_back(worker);
-    worker();
-    for (auto& x : th) x.join();
-}
 // the per-lane functions over the host field, one proof per task
 void host_run(const KeyHost& K, const uint8_t* inputs, const uint8_t* proofs, uint64_t n, uint8_t* ok) {
     if (!K.valid) {

@@ -74,6 +74,11 @@ struct bzk_ctx {
     int msm_front = 0;  // env BZK_MSM_FRONT=sort|partition: how a plain MSM call buckets its pairs (0 = msm_front_plan's measured choice, 1 = radix sort, 2 = partition passes; A/B)
     int msm_split_cuts[4] = {0, 0, 0, 0};  // env BZK_MSM_SPLIT_CUTS="a,b[,c[,d]]": windows per range, highest range first (A/B runs; used when they add up to W)
     bool is_part = false, split_active = false;
+    // env BZK_MSM_BASES_TABLE / BZK_MSM_BASES_TABLE_C (msm_impl.cuh msm_bases_table_plan): -1 = a resident G1 set of 2^19 < n <= 2^20 points is loaded with a
+    // c = 20 window table, 0 = never, 1 = every G1 set whose table fits; the window of the table, 11 .. 20 (0 = 20; tests reach every shape at small n).
+    // is_child: a lane or a window-range child - its calls never take a set's table; msm_split_env: some BZK_MSM_SPLIT* variable was set when the context was created
+    int msm_bases_table = -1, msm_bases_table_c = 0;
+    bool is_child = false, msm_split_env = false;
     void* split_terms = nullptr;
     size_t split_terms_bytes = 0;
     void* split_conv = nullptr;  // internal form of the raw bases of a split call (msm_entry_dev), grow-only; released by bzk_ctx_trim
@@ -170,6 +175,9 @@ int32_t msm_g1_windows_dev(bzk_ctx* ctx, const bzk_msm_bases* bases, const void*
                            int w_begin, int w_end, void* d_win, int32_t info[5]);
 int32_t msm_g2_windows_dev(bzk_ctx* ctx, const bzk_msm_bases* bases, const void* bases_raw, const void* scalars, uint64_t n, uint32_t flags,
                            int w_begin, int w_end, void* d_win, int32_t info[5]);
+// msm_g1.hip: bzk_msm_g1_bases_load_dev without a window table, whatever BZK_MSM_BASES_TABLE says - for the loaders whose calls can never take one
+// (the prover's queries: throughput-flagged or de-duplicated; the device groups: window ranges)
+int32_t msm_g1_bases_load_plain(bzk_ctx* ctx, const void* bases_dev, uint64_t n, bzk_msm_bases** out);
 int msm_window_bits(uint64_t n);
 int msm_g1_window_terms(uint64_t n);  // 0: a window-range G1 call leaves window sums at d_win; k > 0: the k terms of every bucket set (info[4] of the call agrees)
 int32_t g1_horner_terms_packed(const void* T, int count, int c, int w0, uint8_t* out);

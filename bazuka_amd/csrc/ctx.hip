@@ -111,6 +111,7 @@ bzk_ctx* ctx_lane(bzk_ctx* ctx, size_t i) {
             return nullptr;
         }
         if (s) c->own_stream = true;  // created here, destroyed with the lane
+        c->is_child = true;
         ctx->lanes.push_back(c);
     }
     bzk_ctx* c = ctx->lanes[i];
@@ -145,6 +146,7 @@ bzk_ctx* ctx_part(bzk_ctx* ctx, size_t i, bool high_prio) {
         }
         if (s) c->own_stream = true;
         c->is_part = true;
+        c->is_child = true;
         ctx->parts.push_back(c);
     }
     bzk_ctx* c = ctx->parts[i];
@@ -280,6 +282,13 @@ int32_t bzk_ctx_create(int32_t device_id, void* stream, bzk_ctx** out) {
         ctx->msm_front = !strcmp(e, "sort") ? 1 : !strcmp(e, "partition") ? 2 : 0;
         if (!ctx->msm_front && *e) fprintf(stderr, "[bzk] BZK_MSM_FRONT=%s is neither sort nor partition: the measured default is used\n", e);
     }
+    if (const char* e = getenv("BZK_MSM_BASES_TABLE")) ctx->msm_bases_table = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = getenv("BZK_MSM_BASES_TABLE_C")) {
+        const int v = atoi(e);
+        if (v >= 11 && v <= 20) ctx->msm_bases_table_c = v;
+        else fprintf(stderr, "[bzk] BZK_MSM_BASES_TABLE_C=%s is outside 11 .. 20: the table keeps its 20-bit window\n", e);
+    }
+    ctx->msm_split_env = getenv("BZK_MSM_SPLIT") || getenv("BZK_MSM_SPLIT_MIN_LOG") || getenv("BZK_MSM_SPLIT_PRIO") || getenv("BZK_MSM_SPLIT_CUTS");
     if (const char* e = getenv("BZK_MSM_SPLIT")) ctx->msm_split = atoi(e);
     if (const char* e = getenv("BZK_MSM_SPLIT_MIN_LOG")) ctx->msm_split_min_log = atoi(e);
     if (const char* e = getenv("BZK_MSM_SPLIT_PRIO")) ctx->msm_split_prio = atoi(e);

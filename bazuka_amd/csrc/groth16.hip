@@ -370,7 +370,7 @@ static void crs_prepare(bzk_ctx* ctx, CrsShared* c) {
         if (crs_fits(n_cat * (96 + 112), reserve) && hipMalloc(&cat, n_cat * 96) == hipSuccess) {
             bool ok = hipMemcpyAsync(cat, c->l, (size_t)c->n_aux * 96, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess &&
                       hipMemcpyAsync((char*)cat + (size_t)c->n_aux * 96, c->b_g1, (size_t)c->n_b * 96, hipMemcpyDeviceToDevice, ctx->stream) == hipSuccess;
-            if (ok) ok = bzk_msm_g1_bases_load_dev(ctx, cat, n_cat, &c->rlb1) == BZK_OK;
+            if (ok) ok = bzk::msm_g1_bases_load_plain(ctx, cat, n_cat, &c->rlb1) == BZK_OK;
             (void)hipStreamSynchronize(ctx->stream);
             (void)hipFree(cat);
             if (!ok) c->rlb1 = nullptr;
@@ -383,7 +383,7 @@ static void crs_prepare(bzk_ctx* ctx, CrsShared* c) {
     for (auto& q : qs) {
         if (!q.raw || !q.n) continue;
         if (!crs_fits((size_t)q.n * (q.g2 ? 224 : 112), reserve)) continue;
-        const int32_t st = q.g2 ? bzk_msm_g2_bases_load_dev(ctx, q.raw, q.n, q.dst) : bzk_msm_g1_bases_load_dev(ctx, q.raw, q.n, q.dst);
+        const int32_t st = q.g2 ? bzk_msm_g2_bases_load_dev(ctx, q.raw, q.n, q.dst) : bzk::msm_g1_bases_load_plain(ctx, q.raw, q.n, q.dst);
         if (st != BZK_OK) { *q.dst = nullptr; (void)hipGetLastError(); }
     }
 }
@@ -604,6 +604,25 @@ static int32_t groth16_prove_entry(bzk_ctx* ctx, bzk_params* p, const bzk_assign
 }
 
 // explicit control of the h table (1: build it now if it fits, 0: drop it - only while this slot is the CRS's sole user)
+int32_t bzk_params_resident_info(bzk_params* p, uint32_t* sets, uint64_t* device_bytes, uint64_t* table_bytes) {
+    if (!p) return BZK_E_ARG;
+    CrsShared* c = p->crs;
+    std::lock_guard<std::mutex> lk(c->m);
+    uint32_t k = 0;
+    uint64_t bytes = 0, tab = 0;
+    for (const bzk_msm_bases* b : {c->rl, c->ra, c->rb1, c->rb2, c->rh, c->rlb1}) {
+        uint64_t db = 0, tb = 0;
+        if (!b || bzk_msm_bases_info(b, nullptr, nullptr, &db) != BZK_OK || bzk_msm_bases_table_info(b, nullptr, nullptr, &tb) != BZK_OK) continue;
+        ++k;
+        bytes += db;
+        tab += tb;
+    }
+    if (sets) *sets = k;
+    if (device_bytes) *device_bytes = bytes;
+    if (table_bytes) *table_bytes = tab;
+    return BZK_OK;
+}
+
 int32_t bzk_params_h_table(bzk_ctx* ctx, bzk_params* p, int32_t on) {
     if (!ctx || !p) return BZK_E_ARG;
     (void)hipSetDevice(ctx->device);

@@ -614,7 +614,7 @@ static int32_t mg_bases_load(bzk_mg* mg, int g2, const uint8_t* host, const void
             if (hipMemcpyAsync(tmp, host, n * raw, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipFree(tmp); return BZK_E_DEVICE; }
             src = tmp;
         }
-        const int32_t s = g2 ? bzk_msm_g2_bases_load_dev(c, src, n, &B->per_dev[i]) : bzk_msm_g1_bases_load_dev(c, src, n, &B->per_dev[i]);
+        const int32_t s = g2 ? bzk_msm_g2_bases_load_dev(c, src, n, &B->per_dev[i]) : bzk::msm_g1_bases_load_plain(c, src, n, &B->per_dev[i]);
         if (tmp) (void)hipFree(tmp);
         return s;
     });

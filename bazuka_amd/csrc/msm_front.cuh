@@ -68,6 +68,10 @@ static constexpr uint32_t FRONT_BIN_THREADS = 512; // lanes of a bin-pass workgr
 static constexpr uint32_t FRONT_BIN_CAP = 12288;   // values a bin-pass workgroup can stage in LDS (48 KiB); fuller bins are scattered straight to memory
 static constexpr uint32_t FRONT_SCAN_BINS = 16;    // bins per workgroup of the scan pass (16 lanes x 4 bytes = one 64-byte line per tile row)
 static constexpr uint32_t FRONT_SCAN_PARTS = 16;   // tile ranges per bin in that workgroup
+// a call whose windows share ONE bucket set (a full window table: FrontPlan::shared)
+static constexpr uint32_t FRONT_GW_SHARED = 2;        // windows its scatter pass stages at a time (FRONT_TILE * FRONT_GW_SHARED 64-bit values: the same 64 KiB)
+static constexpr uint32_t FRONT_SHARED_HI_MAX = 9;    // bins <= 512 (c = 20: 2^19 keys = 512 bins of 1024 buckets)
+static constexpr uint32_t FRONT_SHARED_TAB_MAX = 4096; // entries of a tile's row of the tables: bins x window groups (c = 20: 512 x 7 = 3584)
 
 // Key k = d - 1 in [0, 2^(c-1)) = hi : lo.  A bin is a (window of the group, hi) pair, bins are window-major; the buckets of a bin are its 2^lo_bits keys.
 // Intermediate pair (32 bits, no key array): base index in idx_bits, lo above it, the sign in bit 31 - the window is the bin's.
@@ -86,6 +90,26 @@ struct FrontPlan {
     // first bucket (window-major bucket index of the call: lw * half + key) of bin b
     BZK_FRONT_HD uint32_t first_bucket(uint32_t b, uint32_t half) const { return (b >> hi_bits) * half + ((b & ((1u << hi_bits) - 1)) << lo_bits); }
     BZK_FRONT_HD size_t table_at(uint32_t tile, uint32_t bin, uint32_t nbins_) const { return (size_t)tile * nbins_ + bin; }
+
+    // ---- shared bucket set: every window of the call feeds the SAME 2^(c-1) buckets from its own level of a window table (msm_run with a full table).
+    // A bin is the key's high bits alone.  The scatter pass stages FRONT_GW_SHARED windows at a time, so a tile leaves `groups` runs per bin: the tables hold
+    // one entry per (bin, window group), bin-major - the groups of a bin are adjacent, and the scan over the entries lays every bin out contiguously.
+    // Intermediate pair (64 bits): the final gather word - table index w * table_n + i, sign in bit 31 - in the low half, lo above it.
+    bool shared = false;
+    uint32_t table_n = 0;  // points per level of the table (the set's n, not the call's)
+    uint32_t groups = 0;   // window groups of the call: ceil(windows / FRONT_GW_SHARED)
+    BZK_FRONT_HD uint32_t shared_bins() const { return 1u << hi_bits; }
+    BZK_FRONT_HD uint32_t shared_tab() const { return groups << hi_bits; }
+    BZK_FRONT_HD uint32_t shared_group(uint32_t w) const { return w / FRONT_GW_SHARED; }
+    BZK_FRONT_HD uint32_t shared_bin(uint32_t key) const { return key >> lo_bits; }
+    BZK_FRONT_HD uint32_t shared_entry(uint32_t bin, uint32_t group) const { return bin * groups + group; }
+    BZK_FRONT_HD uint64_t shared_pack(uint32_t w, uint32_t i, uint32_t key, uint32_t neg) const {
+        return (uint64_t)(w * table_n + i) | ((uint64_t)neg << 31) | ((uint64_t)lo_of(key) << 32);
+    }
+    BZK_FRONT_HD uint32_t shared_lo(uint64_t v) const { return (uint32_t)(v >> 32) & ((1u << lo_bits) - 1); }
+    // the final value of the accumulation's gather list: index | sign << 31 (clean under the mask 0x7fffffff)
+    BZK_FRONT_HD uint32_t shared_final(uint64_t v) const { return (uint32_t)v; }
+    BZK_FRONT_HD uint32_t shared_first_bucket(uint32_t b) const { return b << lo_bits; }
 };
 
 // tiles [t0, t1) of part q (of FRONT_SCAN_PARTS) in the scan pass
@@ -115,8 +139,28 @@ BZK_FRONT_HD inline uint32_t front_pop_key(uint32_t cn, uint32_t clamp) { return
 //   mode      bzk_ctx::msm_front: 0 = by the measured crossover below, 1 = always the sort, 2 = the partition wherever it can run
 // hi = min(7, c - 5), lo = c - 1 - hi: c = 16 gives 128 bins of 256 buckets per window; 9 <= c <= 17 keeps lo <= FRONT_LO_MAX and >= 16 bins per window
 // (the scan pass takes FRONT_SCAN_BINS bins per workgroup).  The packed intermediate must hold the index beside lo: n_index <= 2^(31 - lo).
-inline FrontPlan msm_front_plan(uint64_t n, uint64_t n_index, int c, int windows, bool eligible, bool alone, int mode) {
+//   table_n   0 for a plain call; the level stride of the full window table for a call whose `windows` levels share one bucket set (eligible then means:
+//             a full table, no de-duplication).  Such a call: 11 <= c <= 20, lo = min(10, c - 5), hi = c - 1 - lo in [4, 9], every window in one pass
+inline FrontPlan msm_front_plan(uint64_t n, uint64_t n_index, int c, int windows, bool eligible, bool alone, int mode, uint64_t table_n = 0) {
     FrontPlan P;
+    if (table_n) {
+        if (!eligible || mode == 1 || c < 11 || c > 20 || windows < 1 || n == 0 || n > table_n || n > ((uint64_t)1 << 24) ||
+            (uint64_t)windows * table_n >= ((uint64_t)1 << 31))
+            return P;
+        P.lo_bits = (uint32_t)(c - 5) < FRONT_LO_MAX ? (uint32_t)(c - 5) : FRONT_LO_MAX;
+        P.hi_bits = (uint32_t)(c - 1) - P.lo_bits;
+        P.idx_bits = 31;
+        P.table_n = (uint32_t)table_n;
+        P.groups = ((uint32_t)windows + FRONT_GW_SHARED - 1) / FRONT_GW_SHARED;
+        if (P.hi_bits > FRONT_SHARED_HI_MAX || P.shared_tab() > FRONT_SHARED_TAB_MAX) return P;
+        P.n_tiles = (uint32_t)((n + FRONT_TILE - 1) / FRONT_TILE);
+        P.shared = true;
+        // Measured (profiles/msm_resident_table_ab.json: 2^20 points, c = 20, one resident set with its table, one process, three alternations, medians of
+        // 25 calls): sort 3.311 - 3.314 ms, partition 3.218 - 3.243 ms; the chain before the accumulation 0.49 -> 0.39 ms (the bin pass runs unstaged: a bin
+        // holds 26 600 values), msm_accumulate 2.03 -> 2.11 ms.  So by default: the table calls of that shape that run alone; everything else keeps the sort
+        P.on = mode == 2 || (alone && c == 20 && n > ((uint64_t)1 << 19) && n <= ((uint64_t)1 << 20));
+        return P;
+    }
     if (!eligible || mode == 1 || c < 9 || c > 17 || windows < 1 || windows > 16 || n == 0 || n > ((uint64_t)1 << 24)) return P;
     P.hi_bits = (uint32_t)(c - 5) < FRONT_HI_MAX ? (uint32_t)(c - 5) : FRONT_HI_MAX;
     P.lo_bits = (uint32_t)(c - 1) - P.hi_bits;

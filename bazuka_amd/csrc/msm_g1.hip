@@ -100,11 +100,25 @@ int32_t bzk_msm_bases_info(const bzk_msm_bases* bases, uint64_t* n, int32_t* for
     if (device_bytes) *device_bytes = b->bytes;
     return BZK_OK;
 }
+int32_t bzk_msm_bases_table_info(const bzk_msm_bases* bases, uint32_t* c, uint32_t* levels, uint64_t* table_bytes) {
+    const MsmBases* b = (const MsmBases*)bases;
+    if (!b) return BZK_E_ARG;
+    if (c) *c = b->table ? (uint32_t)b->table->c : 0;
+    if (levels) *levels = b->table ? (uint32_t)b->table->levels : 0;
+    if (table_bytes) *table_bytes = b->table_bytes;
+    return BZK_OK;
+}
 
 }  // extern "C"
 
 // hooks for mg.hip / groth16.hip (not part of the C ABI)
 namespace bzk {
+int32_t msm_g1_bases_load_plain(bzk_ctx* ctx, const void* bases_dev, uint64_t n, bzk_msm_bases** out) {
+    MsmBases* b = nullptr;
+    int32_t st = msm_bases_load<G1Fast>(ctx, bases_dev, n, &b, false);
+    if (out) *out = (bzk_msm_bases*)b;
+    return st;
+}
 int32_t msm_g1_windows_dev(bzk_ctx* ctx, const bzk_msm_bases* bases, const void* bases_raw, const void* scalars, uint64_t n, uint32_t flags,
                            int w_begin, int w_end, void* d_win, int32_t info[5]) {
     return msm_windows_dev<G1Fast>(ctx, (const MsmBases*)bases, bases_raw, scalars, n, flags, w_begin, w_end, d_win, info);

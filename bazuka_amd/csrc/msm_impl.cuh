@@ -29,6 +29,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "bzk_internal.h"
 #include "host_fp64.h"
@@ -372,10 +373,12 @@ static __device__ __forceinline__ uint32_t front_block_excl_scan(const uint32_t*
     return tot;
 }
 
+// SH (FrontPlan::shared): the windows feed one bucket set; a row of the tables holds one entry per (bin, window group) instead of one per (window, bin)
+template <bool SH>
 static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_hist_kernel(const U128* __restrict__ scalars, uint64_t n, int mont, int c, int w_total, int w_begin,
                                                                               int w_cnt, FrontPlan P, uint32_t* __restrict__ tile_hist) {
-    __shared__ uint32_t h[16u << FRONT_HI_MAX];
-    const uint32_t nb = P.nbins((uint32_t)w_cnt), tile = blockIdx.x;
+    __shared__ uint32_t h[SH ? FRONT_SHARED_TAB_MAX : (16u << FRONT_HI_MAX)];
+    const uint32_t nb = SH ? P.shared_tab() : P.nbins((uint32_t)w_cnt), tile = blockIdx.x;
     for (uint32_t b = threadIdx.x; b < nb; b += FRONT_THREADS) h[b] = 0;
     __syncthreads();
 #pragma unroll 1
@@ -384,7 +387,10 @@ static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_hist_kernel(co
         if (i >= n) break;
         const Fr s = msm_load_canonical(scalars, i, mont);
         msm_signed_digits(s.l, c, w_total, [&](int w, uint32_t d, uint32_t) {
-            if (d && w >= w_begin && w < w_begin + w_cnt) atomicAdd(&h[P.bin_of((uint32_t)(w - w_begin), d - 1)], 1u);
+            if (d && w >= w_begin && w < w_begin + w_cnt) {
+                const uint32_t lw = (uint32_t)(w - w_begin);
+                atomicAdd(&h[SH ? P.shared_entry(P.shared_bin(d - 1), P.shared_group(lw)) : P.bin_of(lw, d - 1)], 1u);
+            }
         });
     }
     __syncthreads();
@@ -416,17 +422,21 @@ static __global__ void __launch_bounds__(FRONT_SCAN_BINS * FRONT_SCAN_PARTS) msm
     if (q == FRONT_SCAN_PARTS - 1) bin_total[b] = run;
 }
 
+// SH: GWV = FRONT_GW_SHARED windows at a time, every one of them into the SAME bins; the run of (tile, bin, window group) is the table entry's; 64-bit pairs
+template <bool SH>
 static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_scatter_kernel(const U128* __restrict__ scalars, uint64_t n, int mont, int c, int w_total, int w_begin,
                                                                                  int w_cnt, FrontPlan P,
                                                                                  const uint32_t* __restrict__ tile_hist, const uint32_t* __restrict__ tile_off,
                                                                                  const uint32_t* __restrict__ bin_total, uint64_t len, uint32_t* __restrict__ bin_base,
-                                                                                 uint32_t* __restrict__ inter) {
-    constexpr uint32_t PER = FRONT_TILE / FRONT_THREADS, STAGE = FRONT_TILE * FRONT_GW, GB = FRONT_GW << FRONT_HI_MAX;
-    __shared__ uint32_t stage[STAGE];
-    __shared__ uint32_t bbase[16u << FRONT_HI_MAX];
+                                                                                 typename std::conditional<SH, uint64_t, uint32_t>::type* __restrict__ inter) {
+    typedef typename std::conditional<SH, uint64_t, uint32_t>::type Pair;
+    constexpr uint32_t GWV = SH ? FRONT_GW_SHARED : FRONT_GW;
+    constexpr uint32_t PER = FRONT_TILE / FRONT_THREADS, STAGE = FRONT_TILE * GWV, GB = SH ? (1u << FRONT_SHARED_HI_MAX) : (FRONT_GW << FRONT_HI_MAX);
+    __shared__ Pair stage[STAGE];
+    __shared__ uint32_t bbase[SH ? FRONT_SHARED_TAB_MAX : (16u << FRONT_HI_MAX)];
     __shared__ uint32_t cnt_s[GB], tbs_s[GB], cur_s[GB], toff_s[GB];
     __shared__ uint32_t wave_tmp[FRONT_THREADS / 64];
-    const uint32_t nb = P.nbins((uint32_t)w_cnt), tile = blockIdx.x;
+    const uint32_t nb = SH ? P.shared_tab() : P.nbins((uint32_t)w_cnt), tile = blockIdx.x;
     for (uint32_t b = threadIdx.x; b < nb; b += FRONT_THREADS) bbase[b] = bin_total[b];
     __syncthreads();
     const uint32_t total = front_block_excl_scan<FRONT_THREADS>(bbase, bbase, nb, wave_tmp);
@@ -452,11 +462,13 @@ static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_scatter_kernel
         }
     }
 #pragma unroll 1
-    for (uint32_t g0 = 0; g0 < (uint32_t)w_cnt; g0 += FRONT_GW) {
-        const uint32_t gw = min(FRONT_GW, (uint32_t)w_cnt - g0), nbl = gw << P.hi_bits, b0 = g0 << P.hi_bits;
+    for (uint32_t g0 = 0; g0 < (uint32_t)w_cnt; g0 += GWV) {
+        const uint32_t gw = min(GWV, (uint32_t)w_cnt - g0), nbl = SH ? P.shared_bins() : gw << P.hi_bits, b0 = g0 << P.hi_bits;
+        // table entry of local bin b of this group of windows
+        auto entry = [&](uint32_t b) { return SH ? P.shared_entry(b, P.shared_group(g0)) : b0 + b; };
         for (uint32_t b = threadIdx.x; b < nbl; b += FRONT_THREADS) {
-            cnt_s[b] = tile_hist[P.table_at(tile, b0 + b, nb)];
-            toff_s[b] = tile_off[P.table_at(tile, b0 + b, nb)];
+            cnt_s[b] = tile_hist[P.table_at(tile, entry(b), nb)];
+            toff_s[b] = tile_off[P.table_at(tile, entry(b), nb)];
         }
         __syncthreads();
         front_block_excl_scan<FRONT_THREADS>(cnt_s, tbs_s, nbl, wave_tmp);
@@ -468,8 +480,11 @@ static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_scatter_kernel
             msm_signed_digits(sl[j], c, w_total, [&](int w, uint32_t d, uint32_t neg) {
                 const int lw = w - w_begin - (int)g0;  // window inside this group of FRONT_GW
                 if (d && lw >= 0 && lw < (int)gw) {
-                    const uint32_t pos = atomicAdd(&cur_s[P.bin_of((uint32_t)lw, d - 1)], 1u);
-                    if (pos < STAGE) stage[pos] = P.pack(idx[j], d - 1, neg);
+                    const uint32_t pos = atomicAdd(&cur_s[SH ? P.shared_bin(d - 1) : P.bin_of((uint32_t)lw, d - 1)], 1u);
+                    if (pos < STAGE) {
+                        if constexpr (SH) stage[pos] = P.shared_pack((uint32_t)w, idx[j], d - 1, neg);
+                        else stage[pos] = P.pack(idx[j], d - 1, neg);
+                    }
                 }
             });
         }
@@ -477,7 +492,7 @@ static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_scatter_kernel
         // 32 lanes per bin: the bin's run of this tile leaves as one contiguous store
         for (uint32_t b = threadIdx.x >> 5; b < nbl; b += FRONT_THREADS / 32) {
             const uint32_t cn = cnt_s[b], src = tbs_s[b];
-            const uint64_t dst = (uint64_t)bbase[b0 + b] + toff_s[b];
+            const uint64_t dst = (uint64_t)bbase[entry(b)] + toff_s[b];
             for (uint32_t e = threadIdx.x & 31u; e < cn; e += 32)
                 if (dst + e < len && src + e < STAGE) inter[dst + e] = stage[src + e];
         }
@@ -485,7 +500,10 @@ static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_scatter_kernel
     }
 }
 
-static __global__ void __launch_bounds__(FRONT_BIN_THREADS) msm_front_bins_kernel(const uint32_t* __restrict__ inter, const uint32_t* __restrict__ bin_base, FrontPlan P,
+// SH: bin b is the entries [b * groups, (b + 1) * groups) of the tables - contiguous -, its buckets are keys b << lo .. of the one bucket set
+template <bool SH>
+static __global__ void __launch_bounds__(FRONT_BIN_THREADS) msm_front_bins_kernel(const typename std::conditional<SH, uint64_t, uint32_t>::type* __restrict__ inter,
+                                                                                  const uint32_t* __restrict__ bin_base, FrontPlan P,
                                                                                   uint32_t half, uint64_t len, uint32_t nbk, uint32_t clamp,
                                                                                   uint32_t* __restrict__ vals_s, uint32_t* __restrict__ start,
                                                                                   uint32_t* __restrict__ count, uint32_t* __restrict__ iota,
@@ -494,12 +512,14 @@ static __global__ void __launch_bounds__(FRONT_BIN_THREADS) msm_front_bins_kerne
     __shared__ uint32_t h[1u << FRONT_LO_MAX], cur[1u << FRONT_LO_MAX];
     __shared__ uint32_t wave_tmp[FRONT_BIN_THREADS / 64];
     const uint32_t b = blockIdx.x, nbu = 1u << P.lo_bits, lw = b >> P.hi_bits;
+    auto lo_of = [&](typename std::conditional<SH, uint64_t, uint32_t>::type v) { if constexpr (SH) return P.shared_lo(v); else return P.packed_lo(v); };
     uint32_t base, cnt;
-    front_bin_range(bin_base[b], bin_base[b + 1], len, base, cnt);  // out of range (cannot happen): an empty bin, its buckets still written
-    const uint32_t g0 = P.first_bucket(b, half);
+    // out of range (cannot happen): an empty bin, its buckets still written
+    front_bin_range(bin_base[SH ? P.shared_entry(b, 0) : b], bin_base[SH ? P.shared_entry(b + 1, 0) : b + 1], len, base, cnt);
+    const uint32_t g0 = SH ? P.shared_first_bucket(b) : P.first_bucket(b, half);
     for (uint32_t k = threadIdx.x; k < nbu; k += FRONT_BIN_THREADS) h[k] = 0;
     __syncthreads();
-    for (uint32_t e = threadIdx.x; e < cnt; e += FRONT_BIN_THREADS) atomicAdd(&h[P.packed_lo(inter[base + e])], 1u);
+    for (uint32_t e = threadIdx.x; e < cnt; e += FRONT_BIN_THREADS) atomicAdd(&h[lo_of(inter[base + e])], 1u);
     __syncthreads();
     front_block_excl_scan<FRONT_BIN_THREADS>(h, cur, nbu, wave_tmp);
     for (uint32_t k = threadIdx.x; k < nbu; k += FRONT_BIN_THREADS) {
@@ -519,9 +539,11 @@ static __global__ void __launch_bounds__(FRONT_BIN_THREADS) msm_front_bins_kerne
     for (uint32_t e0 = 0; e0 < cnt; e0 += FRONT_BIN_THREADS) {
         const uint32_t e = e0 + threadIdx.x;
         if (e < cnt) {
-            const uint32_t v = inter[base + e];
-            const uint32_t pos = atomicAdd(&cur[P.packed_lo(v)], 1u);
-            const uint32_t fv = P.final_value(v, lw);
+            const auto v = inter[base + e];
+            const uint32_t pos = atomicAdd(&cur[lo_of(v)], 1u);
+            uint32_t fv;
+            if constexpr (SH) fv = P.shared_final(v);
+            else fv = P.final_value(v, lw);
             if (pos < cnt) {
                 if (staged) stage[pos] = fv;
                 else vals_s[base + pos] = fv;
@@ -1946,7 +1968,11 @@ struct MsmBases {
     uint64_t n = 0;
     int device = 0;
     int endo = 1;
-    size_t bytes = 0;  // device memory of `data` (bzk_msm_bases_info)
+    size_t bytes = 0;  // device memory of `data` and of the table (bzk_msm_bases_info)
+    // full window table (wpl == 1) over the same n points, built at load where msm_bases_table_plan says so: what an eligible stand-alone call runs from
+    // (msm_bases_entry).  Owned by the set, read-only after load like `data`
+    MsmTable* table = nullptr;
+    size_t table_bytes = 0;
 };
 // Where a call that must not finish on this host thread leaves its window sums: `d_win` receives, in DEVICE memory and in stream
 // order, the (w_end - w_begin) window sums S_w as standard-limb XYZZ points; no read-back, no Horner, no synchronisation.  The
@@ -2146,7 +2172,11 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
     // every buffer of the call, declared once; what a configuration does not take stays null
     const bool wiv = !wiv_off && !table && group <= 16 && (uint64_t)n + m_max < ((uint64_t)1 << 27);
     // partition front (section 3d) or the radix sort: decided in one place for every group of this call
-    const FrontPlan front = msm_front_plan(n, (uint64_t)n + m_max, c, group, wiv && front_eligible, front_alone, ctx->msm_front);
+    // a full table's levels share one bucket set: the shared form of the front (FrontPlan::shared), all requested levels in one pass
+    // (G1, the curve whose resident sets own such tables; a G2 table keeps the sort: neither measured nor tested in the shared form)
+    const bool front_table = table && !folded && !dedup && C::BASES_TABLE;
+    const FrontPlan front = front_table ? msm_front_plan(n, (uint64_t)levels * table->n, c, group, true, front_alone, ctx->msm_front, table->n)
+                                        : msm_front_plan(n, (uint64_t)n + m_max, c, group, wiv && front_eligible, front_alone, ctx->msm_front);
     WsLayout ws("msm_run");
     uint32_t *keys = nullptr, *vals, *keys_s = nullptr, *vals_s;
     uint32_t *f_hist = nullptr, *f_off = nullptr, *f_total = nullptr, *f_base = nullptr;
@@ -2160,7 +2190,7 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
     typename C::Fld* pref = nullptr;
     char* tmp_buf;
     if (!front.on) { ws.take(keys, len_max); ws.take(keys_s, len_max); }  // the partition front writes no key array
-    ws.take(vals, len_max); ws.take(vals_s, len_max);
+    ws.take(vals, front.shared ? 2 * len_max : len_max); ws.take(vals_s, len_max);  // the shared form's intermediate pairs are 64-bit
     ws.take(BA.start, nb_alloc); ws.take(BA.count, nb_alloc); ws.take(BA.count_s, nb_alloc); ws.take(BA.iota, nb_alloc);
     ws.take(BA.order, nb_alloc); ws.take(BA.ntask, nb_alloc); ws.take(BA.tbase, nb_alloc);
     ws.take(BA.partial, t_cap);  // per-task partial sums (multi-task buckets only)
@@ -2181,7 +2211,7 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
         ws.take(scal2, 2 * n); ws.take(pref, m_max);
     }
     if (front.on) {
-        const size_t nbins = front.nbins((uint32_t)group);
+        const size_t nbins = front.shared ? front.shared_tab() : front.nbins((uint32_t)group);
         ws.take(f_hist, (size_t)front.n_tiles * nbins); ws.take(f_off, (size_t)front.n_tiles * nbins); ws.take(f_total, nbins); ws.take(f_base, nbins + 1);
     }
     ws.take(tmp_buf, tmp);
@@ -2288,16 +2318,29 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
         const uint64_t len = (uint64_t)wc * n_eff * (folded ? (uint64_t)levels : (uint64_t)E);
         const uint32_t nb = (table && !folded) ? half : (uint32_t)wc * half;
         const int n_red_win = (table && !folded) ? 1 : wc;  // bucket sets to reduce
-        if (front.on) {
+        if (front.on && front.shared) {
+          // the same four passes over the levels of a full table: one bucket set, bins without a window in them, 64-bit intermediate pairs
+          if constexpr (C::BASES_TABLE) {
+            const uint32_t ntab = front.shared_tab();
+            BZK_LAUNCH(ctx, "msm_digits", msm_front_hist_kernel<true>, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total, wb, wc,
+                       front, f_hist);
+            BZK_LAUNCH(ctx, "msm_front_scan", msm_front_scan_kernel, dim3(ntab / FRONT_SCAN_BINS), dim3(FRONT_SCAN_BINS * FRONT_SCAN_PARTS), 0, (const uint32_t*)f_hist,
+                       front.n_tiles, ntab, front, f_off, f_total);
+            BZK_LAUNCH(ctx, "msm_front_scatter", msm_front_scatter_kernel<true>, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total,
+                       wb, wc, front, (const uint32_t*)f_hist, (const uint32_t*)f_off, (const uint32_t*)f_total, len, f_base, (uint64_t*)vals);
+            BZK_LAUNCH(ctx, "msm_front_bins", msm_front_bins_kernel<true>, dim3(front.shared_bins()), dim3(FRONT_BIN_THREADS), 0, (const uint64_t*)vals,
+                       (const uint32_t*)f_base, front, half, len, nb, msm_small_pop(len, nb) ? 255u : 65535u, vals_s, BA.start, BA.count, BA.iota, BA.ntask);
+          }
+        } else if (front.on) {
             // histogram, scan, scatter, bin pass: vals_s, start, count, iota and the population keys come out of the last one (`vals` holds the packed intermediate)
             const uint32_t nbins = front.nbins((uint32_t)wc);
-            BZK_LAUNCH(ctx, "msm_digits", msm_front_hist_kernel, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total, wb, wc,
+            BZK_LAUNCH(ctx, "msm_digits", msm_front_hist_kernel<false>, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total, wb, wc,
                        front, f_hist);
             BZK_LAUNCH(ctx, "msm_front_scan", msm_front_scan_kernel, dim3(nbins / FRONT_SCAN_BINS), dim3(FRONT_SCAN_BINS * FRONT_SCAN_PARTS), 0, (const uint32_t*)f_hist,
                        front.n_tiles, nbins, front, f_off, f_total);
-            BZK_LAUNCH(ctx, "msm_front_scatter", msm_front_scatter_kernel, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total,
+            BZK_LAUNCH(ctx, "msm_front_scatter", msm_front_scatter_kernel<false>, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total,
                        wb, wc, front, (const uint32_t*)f_hist, (const uint32_t*)f_off, (const uint32_t*)f_total, len, f_base, vals);
-            BZK_LAUNCH(ctx, "msm_front_bins", msm_front_bins_kernel, dim3(nbins), dim3(FRONT_BIN_THREADS), 0, (const uint32_t*)vals, (const uint32_t*)f_base, front,
+            BZK_LAUNCH(ctx, "msm_front_bins", msm_front_bins_kernel<false>, dim3(nbins), dim3(FRONT_BIN_THREADS), 0, (const uint32_t*)vals, (const uint32_t*)f_base, front,
                        half, len, nb, msm_small_pop(len, nb) ? 255u : 65535u, vals_s, BA.start, BA.count, BA.iota, BA.ntask);
         } else if (E > 1) {
             BZK_LAUNCH(ctx, "msm_digits_endo", (msm_digits_endo_kernel<C::ENDO>), dim3((unsigned)((n_eff + 255) / 256)), dim3(256), 0, (const U128*)scal_eff,
@@ -2672,8 +2715,30 @@ static int32_t msm_table_entry(bzk_ctx* ctx, const MsmTable* t, const void* scal
 }
 
 // ---- resident base sets (MsmBases) -------------------------------------------------------------------------------------------
+// The window table of a resident set: THE rule for whether a load builds one, and with which window.  A full table with a 20-bit window costs a stand-alone
+// 2^20-point G1 call 13 additions per point instead of 16, over one set of 2^19 buckets, and leaves the host one bucket set's terms instead of 16 sets'
+// (measured beside the per-call pipeline in every round: bench.py other_configs.msm_g1_2p20_static_table).  By default only where that was
+// measured - G1, 2^19 < n <= 2^20 -; BZK_MSM_BASES_TABLE=1 takes every G1 set whose table fits, =0 none (bzk_ctx::msm_bases_table).  Returns the table's
+// window, 0 for no table.  `free_b`: what hipMemGetInfo reports free; the table must fit beside the 8 GiB reserve the endomorphism images leave too.
 template <class C>
-static int32_t msm_bases_load(bzk_ctx* ctx, const void* bases_raw, uint64_t n, MsmBases** out) {
+static int msm_bases_table_plan(const bzk_ctx* ctx, uint64_t n, size_t free_b) {
+    if (!C::BASES_TABLE || ctx->msm_bases_table == 0) return 0;
+    if (ctx->msm_bases_table < 0 && !(n > ((uint64_t)1 << 19) && n <= ((uint64_t)1 << 20))) return 0;
+    const int c = ctx->msm_bases_table_c >= 11 && ctx->msm_bases_table_c <= 20 ? ctx->msm_bases_table_c : 20;
+    const uint64_t levels = (uint64_t)msm_windows_for(c);
+    if (levels * n >= ((uint64_t)1 << 31)) return 0;
+    if ((size_t)(levels * n) * sizeof(typename C::DevAff) + ((size_t)8 << 30) > free_b) return 0;
+    return c;
+}
+// does this call over set b run from the set's table?  Whole stand-alone MSMs only: a window range, a throughput-flagged or de-duplicated call, a context
+// with a forced window or an explicit split setting, and a lane or window-range child all keep the per-call pipeline unchanged
+template <class C>
+static bool msm_bases_table_takes(const bzk_ctx* ctx, const MsmBases* b, uint64_t n, uint32_t flags, int w_begin, int w_end) {
+    return b->table && w_begin == 0 && w_end < 0 && n > 0 && n <= b->n && !(flags & (BZK_F_THROUGHPUT | BZK_F_DEDUP)) && ctx->msm_c_override == 0 &&
+           !ctx->msm_split_env && !ctx->is_child && !ctx->split_active;
+}
+template <class C>
+static int32_t msm_bases_load(bzk_ctx* ctx, const void* bases_raw, uint64_t n, MsmBases** out, bool may_table = true) {
     if (!ctx || !out || !bases_raw || n == 0 || n >= ((uint64_t)1 << 31)) return BZK_E_ARG;
     *out = nullptr;
     (void)hipSetDevice(ctx->device);
@@ -2716,6 +2781,24 @@ static int32_t msm_bases_load(bzk_ctx* ctx, const void* bases_raw, uint64_t n, M
         return st;
     }
     b->bytes = (size_t)b->endo * n * sizeof(typename C::DevAff);
+    // the window table, where msm_bases_table_plan wants one: built from the raw points on the load's stream, complete before the load returns.  A table
+    // that does not fit or cannot be allocated is simply not there - the set works without it
+    if (may_table) {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+        const int tc = msm_bases_table_plan<C>(ctx, n, free_b);
+        if (tc) {
+            const std::string kept = ctx->last_error;
+            if (msm_table_build<C>(ctx, bases_raw, n, &b->table, 0, tc) == BZK_OK && b->table->wpl == 1) {
+                b->table_bytes = (size_t)b->table->levels * n * sizeof(typename C::DevAff);
+                b->bytes += b->table_bytes;
+            } else {
+                msm_table_free(nullptr, b->table);
+                b->table = nullptr;
+                ctx->last_error = kept;
+            }
+        }
+    }
     *out = b;
     return BZK_OK;
 }
@@ -2726,6 +2809,7 @@ static void msm_bases_free(bzk_ctx* ctx, MsmBases* b) {
         (void)hipStreamSynchronize(ctx->stream);
     }
     if (b->data) (void)hipFree(b->data);
+    msm_table_free(nullptr, b->table);  // the stream was waited for above
     delete b;
 }
 template <class C>
@@ -2736,8 +2820,14 @@ static int32_t msm_bases_entry(bzk_ctx* ctx, const MsmBases* b, const void* scal
     if (b->device != ctx->device) return BZK_E_ARG;
     (void)hipSetDevice(ctx->device);
     XyzzT<F> r;
-    const int parts = (w_begin == 0 && w_end < 0) ? msm_split_parts<C>(ctx, n, flags, b) : 1;
-    if (parts > 1) {
+    const bool from_table = msm_bases_table_takes<C>(ctx, b, n, flags, w_begin, w_end);
+    const int parts = (w_begin == 0 && w_end < 0 && !from_table) ? msm_split_parts<C>(ctx, n, flags, b) : 1;
+    if (from_table) {
+        // the set's window table (msm_bases_table_plan): the call of msm_table_entry, its stride the set's n.  The empty scope is the label by which a
+        // profile tells this path from the per-call pipeline (no launch of its own; the accumulation stays "msm_accumulate")
+        { ProfScope marker(ctx, "msm_bases_table"); }
+        BZK_TRY(msm_run<C>(ctx, nullptr, scalars, n, flags, 0, -1, r, b->table));
+    } else if (parts > 1) {
         BZK_TRY(msm_run_split<C>(ctx, scalars, n, flags, r, b, parts));
     } else {
         BZK_TRY(msm_run<C>(ctx, nullptr, scalars, n, flags, w_begin, w_end, r, nullptr, b));

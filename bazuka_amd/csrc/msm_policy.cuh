@@ -45,6 +45,8 @@ struct G1Fast {
     // prover's overlapping MSMs, where fewer buckets mean less WORK for the reduction.  A stand-alone call gains nothing: its bucket
     // reduction is as long as one lane's chain whatever the bucket count, and fuller buckets balance worse (profiles/r04_run4_5_endo_ab.txt)
     static constexpr const char* ENDO_ENV = "BZK_MSM_ENDO_G1";
+    // a resident set of this curve may own a full window table for stand-alone calls (msm_impl.cuh msm_bases_table_plan): 13 additions per point instead of 16
+    static constexpr bool BASES_TABLE = true;
     __device__ static __forceinline__ void endo_images(const DevAff& p, DevAff* out, size_t stride) { out[stride] = endo::g1_image(p); }
 #ifndef BZK_G1_PARK_REDUCE
 #define BZK_G1_PARK_REDUCE 0
@@ -134,6 +136,7 @@ struct G2Fast {
     static constexpr int ENDO = 4, ENDO_BITS = 64;
     static constexpr int ENDO_DEFAULT = 2;
     static constexpr const char* ENDO_ENV = "BZK_MSM_ENDO_G2";
+    static constexpr bool BASES_TABLE = false;  // no measurement of a G2 table behind a resident set
     __device__ static __forceinline__ void endo_images(const DevAff& p, DevAff* out, size_t stride) {
         out[stride] = endo::g2_image<1>(p);
         out[2 * stride] = endo::g2_image<2>(p);

@@ -95,6 +95,7 @@ SIGNATURES = {
     "bzk_params_free": (None, [_vp, _vp]),
     "bzk_params_slot": (_i32, [_vp, _vp, C.POINTER(_vp)]),
     "bzk_params_h_table": (_i32, [_vp, _vp, _i32]),
+    "bzk_params_resident_info": (_i32, [_vp, C.POINTER(_u32), C.POINTER(_u64), C.POINTER(_u64)]),
     "bzk_groth16_prove": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "bzk_groth16_prove_r1cs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "bzk_r1cs_stage": (_i32, [_vp, _vp, C.POINTER(_vp)]),
@@ -195,6 +196,7 @@ SIGNATURES = {
     "bzk_msm_bases_free": (None, [_vp, _vp]),
     "bzk_msm_bases_size": (_u64, [_vp]),
     "bzk_msm_bases_info": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_i32), C.POINTER(_u64)]),
+    "bzk_msm_bases_table_info": (_i32, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u64)]),
     "bzk_msm_g1_bases_run_dev": (_i32, [_vp, _vp, _vp, _u64, _u32, _vp]),
     "bzk_msm_g2_bases_run_dev": (_i32, [_vp, _vp, _vp, _u64, _u32, _vp]),
     "bzk_msm_g1_bases_windows_dev": (_i32, [_vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp]),
@@ -596,6 +598,12 @@ class Bzk:
         self._ck(self.lib.bzk_msm_bases_info(handle, C.byref(n), C.byref(forms), C.byref(nbytes)), "msm_bases_info")
         return {"n": n.value, "forms": forms.value, "device_bytes": nbytes.value}
 
+    def msm_bases_table_info(self, handle) -> dict:
+        """the window table a resident G1 set carries for stand-alone calls (include/bzk.h); all zero without one"""
+        c, levels, nbytes = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        self._ck(self.lib.bzk_msm_bases_table_info(handle, C.byref(c), C.byref(levels), C.byref(nbytes)), "msm_bases_table_info")
+        return {"c": c.value, "levels": levels.value, "table_bytes": nbytes.value}
+
     def msm_bases_free(self, handle):
         self.lib.bzk_msm_bases_free(self.h, handle)
 
@@ -775,6 +783,12 @@ class Bzk:
 
     def params_h_table(self, ph, on: bool):
         self._ck(self.lib.bzk_params_h_table(self.h, ph, int(on)), "params_h_table")
+
+    def params_resident_info(self, ph) -> dict:
+        """the resident query sets a parameter set holds once prepared (include/bzk.h)"""
+        k, nbytes, tab = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+        self._ck(self.lib.bzk_params_resident_info(ph, C.byref(k), C.byref(nbytes), C.byref(tab)), "params_resident_info")
+        return {"sets": k.value, "device_bytes": nbytes.value, "table_bytes": tab.value}
 
     def groth16_prove(self, ph, z, az, bz, cz, r: bytes, s: bytes) -> bytes:
         """z / az / bz / cz: bytes or zero-copy ctypes views (R1cs.raw) - passed by address, never copied here."""

@@ -438,6 +438,10 @@ int32_t bzk_params_slot(bzk_ctx* ctx, const bzk_params* params, bzk_params** out
  * fits; (.., 0) drops it / keeps the first proof from building it (only while this handle is the CRS's sole slot).  Environment:
  * BZK_PROVE_H_TABLE=0, BZK_PROVE_H_TABLE_MAX_LOG, BZK_PROVE_RESIDENT_BASES=0. */
 int32_t bzk_params_h_table(bzk_ctx* ctx, bzk_params* params, int32_t on);
+/* The resident query sets of a parameter set's CRS, once its first proof (or bzk_params_h_table) has prepared them: *sets = how many are held,
+ * *device_bytes = their HBM, *table_bytes = HBM of window tables among them (bzk_msm_bases_table_info) - 0: the prover's MSMs are
+ * throughput-flagged or de-duplicated and never run from such a table, so its sets are loaded without one whatever BZK_MSM_BASES_TABLE says. */
+int32_t bzk_params_resident_info(bzk_params* params, uint32_t* sets, uint64_t* device_bytes, uint64_t* table_bytes);
 /* r, s: Montgomery scalars (the prover's blinding factors; bellman draws them from the rng) */
 int32_t bzk_groth16_prove(bzk_ctx* ctx, bzk_params* params, const bzk_assignment* asg, const uint8_t r[32],
                           const uint8_t s[32], uint8_t proof_out[387]);
@@ -738,8 +742,16 @@ uint64_t bzk_msm_bases_size(const bzk_msm_bases* bases);
 /* What a load decided: *forms = 1 (the set alone) or the number of arrays held - the set plus its endomorphism images X^m P (G1: 2,
  * G2: 4), which whole-MSM calls flagged BZK_F_THROUGHPUT use (fewer bucket sets, same additions, same result).  The images are built
  * at load unless no call could use them (BZK_MSM_ENDO_G1 / _G2 = 0, BZK_MSM_NO_ENDO = 1, device groups) or they do not fit beside an
- * 8 GiB reserve; *device_bytes = HBM held by the set. */
+ * 8 GiB reserve; *device_bytes = HBM held by the set, its window table (below) included. */
 int32_t bzk_msm_bases_info(const bzk_msm_bases* bases, uint64_t* n, int32_t* forms, uint64_t* device_bytes);
+/* The window table of a resident G1 set.  A load of 2^19 < n <= 2^20 points also builds the full static table 2^(20 w) P_i (13 levels x 112 B x n: 1.5 GB
+ * at 2^20 points) when it fits beside the same 8 GiB reserve, and a whole stand-alone call over the set - bzk_msm_g1_bases_run_dev without
+ * BZK_F_THROUGHPUT / BZK_F_DEDUP, on a context with no forced window (BZK_MSM_C) and no BZK_MSM_SPLIT* setting - runs from it: 13 additions per
+ * point instead of 16, one bucket set, the same result bytes.  Every other call over the set is unchanged.  Env, read when a context is
+ * created: BZK_MSM_BASES_TABLE=0 never builds a table, =1 builds one for every G1 set it fits; BZK_MSM_BASES_TABLE_C = 11 .. 20 sets the table's window.
+ * The sets that bzk_groth16_prove and the device groups load for themselves never carry one.  *c = the table's window, *levels = its
+ * levels, *table_bytes = 112 x levels x n; all 0 for a set without a table. */
+int32_t bzk_msm_bases_table_info(const bzk_msm_bases* bases, uint32_t* c, uint32_t* levels, uint64_t* table_bytes);
 int32_t bzk_msm_g1_bases_run_dev(bzk_ctx* ctx, const bzk_msm_bases* bases, const void* scalars_dev, uint64_t n, uint32_t flags, uint8_t out[97]);
 int32_t bzk_msm_g2_bases_run_dev(bzk_ctx* ctx, const bzk_msm_bases* bases, const void* scalars_dev, uint64_t n, uint32_t flags, uint8_t out[193]);
 int32_t bzk_msm_g1_bases_windows_dev(bzk_ctx* ctx, const bzk_msm_bases* bases, const void* scalars_dev, uint64_t n, uint32_t flags,

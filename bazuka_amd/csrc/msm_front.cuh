@@ -69,9 +69,16 @@ static constexpr uint32_t FRONT_BIN_CAP = 12288;   // values a bin-pass workgrou
 static constexpr uint32_t FRONT_SCAN_BINS = 16;    // bins per workgroup of the scan pass (16 lanes x 4 bytes = one 64-byte line per tile row)
 static constexpr uint32_t FRONT_SCAN_PARTS = 16;   // tile ranges per bin in that workgroup
 // a call whose windows share ONE bucket set (a full window table: FrontPlan::shared)
-static constexpr uint32_t FRONT_GW_SHARED = 2;        // windows its scatter pass stages at a time (FRONT_TILE * FRONT_GW_SHARED 64-bit values: the same 64 KiB)
+static constexpr uint32_t FRONT_GW_SHARED = 4;        // windows its scatter pass stages at a time (FRONT_TILE * FRONT_GW_SHARED tile-local 32-bit words: the same 64 KiB)
 static constexpr uint32_t FRONT_SHARED_HI_MAX = 9;    // bins <= 512 (c = 20: 2^19 keys = 512 bins of 1024 buckets)
-static constexpr uint32_t FRONT_SHARED_TAB_MAX = 4096; // entries of a tile's row of the tables: bins x window groups (c = 20: 512 x 7 = 3584)
+static constexpr uint32_t FRONT_SHARED_TAB_MAX = 4096; // entries of a tile's row of the tables: bins x window groups (c = 20: 512 x 4 = 2048)
+static constexpr uint32_t FRONT_TABLE_LEVEL_BITS = 5;  // the level of a pair inside its call, above lo in the staged word and in the 64-bit pair
+static constexpr uint32_t FRONT_TABLE_LEVELS_MAX = 24; // levels of one call (c = 11: 24 windows)
+static constexpr uint32_t FRONT_TABLE_CELLS_MAX = 18432;  // (bucket, level) counters of a bin-pass workgroup, 72 KiB: c = 15 has 1024 buckets x 18 levels, c = 20 1024 x 13
+static constexpr uint32_t FRONT_TABLE_BIN_THREADS = 1024; // lanes of a bin-pass workgroup of a table call
+static constexpr uint32_t FRONT_TABLE_LDS_WORDS = 40944;  // that workgroup's cells and, behind them, its stage of 32-bit values: the CU's 160 KiB less the scan's 16 words
+static constexpr uint32_t FRONT_TABLE_BIN_HELD = 27;      // pairs a lane keeps in registers while its bin is ordered in the stage (27 x 1024 >= 40944 - 13312: c = 20)
+static constexpr uint32_t FRONT_TABLE_BIN_UNROLL = 4;     // strides whose loads are in flight together in the sweeps of a bin too full for the stage
 
 // Key k = d - 1 in [0, 2^(c-1)) = hi : lo.  A bin is a (window of the group, hi) pair, bins are window-major; the buckets of a bin are its 2^lo_bits keys.
 // Intermediate pair (32 bits, no key array): base index in idx_bits, lo above it, the sign in bit 31 - the window is the bin's.
@@ -94,7 +101,8 @@ struct FrontPlan {
     // ---- shared bucket set: every window of the call feeds the SAME 2^(c-1) buckets from its own level of a window table (msm_run with a full table).
     // A bin is the key's high bits alone.  The scatter pass stages FRONT_GW_SHARED windows at a time, so a tile leaves `groups` runs per bin: the tables hold
     // one entry per (bin, window group), bin-major - the groups of a bin are adjacent, and the scan over the entries lays every bin out contiguously.
-    // Intermediate pair (64 bits): the final gather word - table index w * table_n + i, sign in bit 31 - in the low half, lo above it.
+    // Intermediate pair (64 bits): the final gather word - table index w * table_n + i, sign in bit 31 - in the low half, lo above it, and above lo the level
+    // inside the call (table_widen below: what the kernels write; shared_pack is the same pair without the level).
     bool shared = false;
     uint32_t table_n = 0;  // points per level of the table (the set's n, not the call's)
     uint32_t groups = 0;   // window groups of the call: ceil(windows / FRONT_GW_SHARED)
@@ -110,7 +118,28 @@ struct FrontPlan {
     // the final value of the accumulation's gather list: index | sign << 31 (clean under the mask 0x7fffffff)
     BZK_FRONT_HD uint32_t shared_final(uint64_t v) const { return (uint32_t)v; }
     BZK_FRONT_HD uint32_t shared_first_bucket(uint32_t b) const { return b << lo_bits; }
+
+    // ---- what the kernels of a table call stage and rank by: the pair carries its level of the call (lw = w - w_begin < levels), so that the bin pass
+    // ranks over (bucket, level) cells and leaves every bucket level-major - the pair sort's order - whatever order the pairs arrive in.
+    uint32_t levels = 0;  // levels of one pass of the call: the stride of a bucket's cells
+    // the scatter pass's staged word (32 bits, tile-local): index inside the tile in 12 bits, lw, the sign, lo - 28 bits at most
+    BZK_FRONT_HD uint32_t table_stage(uint32_t t, uint32_t lw, uint32_t key, uint32_t neg) const {
+        return t | (lw << 12) | (neg << (12 + FRONT_TABLE_LEVEL_BITS)) | (lo_of(key) << (13 + FRONT_TABLE_LEVEL_BITS));
+    }
+    // widened on the way out to the 64-bit pair: shared_pack's fields (shared_lo / shared_final read it unchanged) with lw above lo, in bits 42 .. 46
+    BZK_FRONT_HD uint64_t table_widen(uint32_t s, uint32_t tile, uint32_t w_begin) const {
+        const uint32_t t = s & (FRONT_TILE - 1), lw = (s >> 12) & ((1u << FRONT_TABLE_LEVEL_BITS) - 1), neg = (s >> (12 + FRONT_TABLE_LEVEL_BITS)) & 1u;
+        const uint32_t lo = s >> (13 + FRONT_TABLE_LEVEL_BITS);
+        return (uint64_t)((w_begin + lw) * table_n + tile * FRONT_TILE + t) | ((uint64_t)neg << 31) | ((uint64_t)lo << 32) | ((uint64_t)lw << (32 + FRONT_LO_MAX));
+    }
+    BZK_FRONT_HD uint32_t table_level(uint64_t v) const { return (uint32_t)(v >> (32 + FRONT_LO_MAX)) & ((1u << FRONT_TABLE_LEVEL_BITS) - 1); }
+    // cells of a bin, bucket-major and level-minor: the exclusive scan over them gives every bucket's start and every cell's rank base
+    BZK_FRONT_HD uint32_t table_cells() const { return levels << lo_bits; }
+    BZK_FRONT_HD uint32_t table_cell(uint64_t v) const { return shared_lo(v) * levels + table_level(v); }
 };
+static_assert(FRONT_TILE == 4096 && 13 + FRONT_TABLE_LEVEL_BITS + FRONT_LO_MAX <= 32, "the staged word of a table call: 12 index bits, level, sign, lo");
+static_assert(FRONT_TABLE_LEVELS_MAX <= (1u << FRONT_TABLE_LEVEL_BITS), "a level fits its field");
+static_assert(FRONT_TABLE_CELLS_MAX < FRONT_TABLE_LDS_WORDS && 4 * (FRONT_TABLE_LDS_WORDS + FRONT_TABLE_BIN_THREADS / 64) <= 160 * 1024, "the bin pass's LDS");
 
 // tiles [t0, t1) of part q (of FRONT_SCAN_PARTS) in the scan pass
 BZK_FRONT_HD inline void front_scan_range(uint32_t n_tiles, uint32_t q, uint32_t& t0, uint32_t& t1) {
@@ -129,6 +158,12 @@ BZK_FRONT_HD inline void front_bin_range(uint32_t lo, uint32_t hi, uint64_t len,
 }
 // a bin of cnt values is ordered in LDS while it fits `cap` values (the kernel: FRONT_BIN_CAP), and stored through the running cursors otherwise
 BZK_FRONT_HD inline bool front_bin_staged(uint32_t cnt, uint32_t cap) { return cnt <= (cap < FRONT_BIN_CAP ? cap : FRONT_BIN_CAP); }
+// a table call's bin of ncell (bucket, level) cells is ordered in LDS while its values fit behind the cells and in the lanes' registers, and stored through
+// the running cursors otherwise
+BZK_FRONT_HD inline uint32_t front_table_bin_cap(uint32_t ncell) {
+    const uint32_t room = ncell < FRONT_TABLE_LDS_WORDS ? FRONT_TABLE_LDS_WORDS - ncell : 0u, held = FRONT_TABLE_BIN_HELD * FRONT_TABLE_BIN_THREADS;
+    return room < held ? room : held;
+}
 // the population key of a bucket of cn values (what msm_count_kernel writes on the sort path)
 BZK_FRONT_HD inline uint32_t front_pop_key(uint32_t cn, uint32_t clamp) { return cn < clamp ? cn : clamp; }
 
@@ -140,24 +175,32 @@ BZK_FRONT_HD inline uint32_t front_pop_key(uint32_t cn, uint32_t clamp) { return
 // hi = min(7, c - 5), lo = c - 1 - hi: c = 16 gives 128 bins of 256 buckets per window; 9 <= c <= 17 keeps lo <= FRONT_LO_MAX and >= 16 bins per window
 // (the scan pass takes FRONT_SCAN_BINS bins per workgroup).  The packed intermediate must hold the index beside lo: n_index <= 2^(31 - lo).
 //   table_n   0 for a plain call; the level stride of the full window table for a call whose `windows` levels share one bucket set (eligible then means:
-//             a full table, no de-duplication).  Such a call: 11 <= c <= 20, lo = min(10, c - 5), hi = c - 1 - lo in [4, 9], every window in one pass
+//             a full table, no de-duplication).  Such a call: 11 <= c <= 20, lo = min(10, c - 5), hi = c - 1 - lo in [4, 9], every window in one pass,
+//             at most FRONT_TABLE_LEVELS_MAX of them, and levels << lo (bucket, level) cells in the bin pass's LDS: at most FRONT_TABLE_CELLS_MAX
 inline FrontPlan msm_front_plan(uint64_t n, uint64_t n_index, int c, int windows, bool eligible, bool alone, int mode, uint64_t table_n = 0) {
     FrontPlan P;
     if (table_n) {
-        if (!eligible || mode == 1 || c < 11 || c > 20 || windows < 1 || n == 0 || n > table_n || n > ((uint64_t)1 << 24) ||
-            (uint64_t)windows * table_n >= ((uint64_t)1 << 31))
+        if (!eligible || mode == 1 || c < 11 || c > 20 || windows < 1 || (uint32_t)windows > FRONT_TABLE_LEVELS_MAX || n == 0 || n > table_n ||
+            n > ((uint64_t)1 << 24) || (uint64_t)windows * table_n >= ((uint64_t)1 << 31) || n_index > ((uint64_t)1 << 31))
             return P;
         P.lo_bits = (uint32_t)(c - 5) < FRONT_LO_MAX ? (uint32_t)(c - 5) : FRONT_LO_MAX;
         P.hi_bits = (uint32_t)(c - 1) - P.lo_bits;
         P.idx_bits = 31;
         P.table_n = (uint32_t)table_n;
         P.groups = ((uint32_t)windows + FRONT_GW_SHARED - 1) / FRONT_GW_SHARED;
-        if (P.hi_bits > FRONT_SHARED_HI_MAX || P.shared_tab() > FRONT_SHARED_TAB_MAX) return P;
+        P.levels = (uint32_t)windows;
+        // the bin pass keeps one LDS counter per (bucket, level) cell: a shape whose cells do not fit keeps the sort (none of c = 11 .. 20 does: c = 15 has
+        // the most, 1024 x 18 = FRONT_TABLE_CELLS_MAX)
+        if (P.hi_bits > FRONT_SHARED_HI_MAX || P.shared_tab() > FRONT_SHARED_TAB_MAX || P.table_cells() > FRONT_TABLE_CELLS_MAX) return P;
         P.n_tiles = (uint32_t)((n + FRONT_TILE - 1) / FRONT_TILE);
         P.shared = true;
-        // Measured (profiles/msm_resident_table_ab.json: 2^20 points, c = 20, one resident set with its table, one process, three alternations, medians of
-        // 25 calls): sort 3.311 - 3.314 ms, partition 3.218 - 3.243 ms; the chain before the accumulation 0.49 -> 0.39 ms (the bin pass runs unstaged: a bin
-        // holds 26 600 values), msm_accumulate 2.03 -> 2.11 ms.  So by default: the table calls of that shape that run alone; everything else keeps the sort
+        // Measured (profiles/msm_table_front_ab.json: 2^20 points, c = 20, one resident set with its table, one process, three alternations, medians of
+        // 25 calls): sort 3.146 - 3.153 ms, partition 2.870 - 2.889 ms (with 2 levels per scatter round and a bin pass ranking by bucket alone, a barrier per
+        // stride: 3.171 - 3.241 against 3.040 - 3.125).  The chain before the accumulation: sort 0.49 ms, partition 0.23 (histogram 0.028 + scan 0.012 +
+        // scatter 0.097 + bins 0.096; before: 0.029 + 0.012 + 0.135 + 0.217); msm_accumulate 1.94 - 1.95 ms in the sort's order, 1.95 - 1.96 in this one's
+        // (level-major too), 1.98 - 1.99 in the old group-major one.  Kernels: scatter 128 VGPRs, 90 176 B LDS, one spilled register; bin pass 82 VGPRs,
+        // 163 840 B LDS, no scratch.  Not measured: other window sizes for speed, the bin pass with a barrier per stride.
+        // So by default: the table calls of that shape that run alone; everything else keeps the sort
         P.on = mode == 2 || (alone && c == 20 && n > ((uint64_t)1 << 19) && n <= ((uint64_t)1 << 20));
         return P;
     }

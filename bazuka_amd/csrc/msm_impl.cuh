@@ -324,6 +324,8 @@ static __global__ void __launch_bounds__(256) msm_count_kernel(const uint32_t* _
 //                      bucket order (staged in LDS while the bin fits FRONT_BIN_CAP, stored through the running cursors otherwise: both sweeps walk the bin in
 //                      strides of the workgroup, so any population is served - an all-equal scalar vector puts a whole window into one bin)
 // Order inside a bucket follows the LDS atomics, not the base index: the bucket sums are the same group elements.
+// A table call (FrontPlan::shared: every level feeds ONE bucket set) runs the same chain with a bin pass of its own, msm_front_table_bins_kernel, which ranks by
+// (bucket, level) and leaves every bucket level-major.
 // This is not the round-2 partition of 3c: that one partitioned MATERIALISED pairs and scattered them with 4-byte stores; here the tile is ordered in LDS
 // before it is written and the boundaries come out of the bin pass.  Shapes and the decision sort / partition: msm_front_plan (msm_front.cuh).
 // ------------------------------------------------------------------------------------------------
@@ -422,7 +424,8 @@ static __global__ void __launch_bounds__(FRONT_SCAN_BINS * FRONT_SCAN_PARTS) msm
     if (q == FRONT_SCAN_PARTS - 1) bin_total[b] = run;
 }
 
-// SH: GWV = FRONT_GW_SHARED windows at a time, every one of them into the SAME bins; the run of (tile, bin, window group) is the table entry's; 64-bit pairs
+// SH: GWV = FRONT_GW_SHARED windows at a time, every one of them into the SAME bins; the run of (tile, bin, window group) is the table entry's.  The stage
+// holds tile-local 32-bit words (FrontPlan::table_stage: index in the tile, level, sign, lo); a run is widened to 64-bit pairs as it is stored (table_widen)
 template <bool SH>
 static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_scatter_kernel(const U128* __restrict__ scalars, uint64_t n, int mont, int c, int w_total, int w_begin,
                                                                                  int w_cnt, FrontPlan P,
@@ -432,7 +435,7 @@ static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_scatter_kernel
     typedef typename std::conditional<SH, uint64_t, uint32_t>::type Pair;
     constexpr uint32_t GWV = SH ? FRONT_GW_SHARED : FRONT_GW;
     constexpr uint32_t PER = FRONT_TILE / FRONT_THREADS, STAGE = FRONT_TILE * GWV, GB = SH ? (1u << FRONT_SHARED_HI_MAX) : (FRONT_GW << FRONT_HI_MAX);
-    __shared__ Pair stage[STAGE];
+    __shared__ uint32_t stage[STAGE];
     __shared__ uint32_t bbase[SH ? FRONT_SHARED_TAB_MAX : (16u << FRONT_HI_MAX)];
     __shared__ uint32_t cnt_s[GB], tbs_s[GB], cur_s[GB], toff_s[GB];
     __shared__ uint32_t wave_tmp[FRONT_THREADS / 64];
@@ -482,7 +485,7 @@ static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_scatter_kernel
                 if (d && lw >= 0 && lw < (int)gw) {
                     const uint32_t pos = atomicAdd(&cur_s[SH ? P.shared_bin(d - 1) : P.bin_of((uint32_t)lw, d - 1)], 1u);
                     if (pos < STAGE) {
-                        if constexpr (SH) stage[pos] = P.shared_pack((uint32_t)w, idx[j], d - 1, neg);
+                        if constexpr (SH) stage[pos] = P.table_stage(j * FRONT_THREADS + threadIdx.x, (uint32_t)(w - w_begin), d - 1, neg);
                         else stage[pos] = P.pack(idx[j], d - 1, neg);
                     }
                 }
@@ -494,15 +497,16 @@ static __global__ void __launch_bounds__(FRONT_THREADS) msm_front_scatter_kernel
             const uint32_t cn = cnt_s[b], src = tbs_s[b];
             const uint64_t dst = (uint64_t)bbase[entry(b)] + toff_s[b];
             for (uint32_t e = threadIdx.x & 31u; e < cn; e += 32)
-                if (dst + e < len && src + e < STAGE) inter[dst + e] = stage[src + e];
+                if (dst + e < len && src + e < STAGE) {
+                    if constexpr (SH) inter[dst + e] = P.table_widen(stage[src + e], tile, (uint32_t)w_begin);
+                    else inter[dst + e] = stage[src + e];
+                }
         }
         __syncthreads();
     }
 }
 
-// SH: bin b is the entries [b * groups, (b + 1) * groups) of the tables - contiguous -, its buckets are keys b << lo .. of the one bucket set
-template <bool SH>
-static __global__ void __launch_bounds__(FRONT_BIN_THREADS) msm_front_bins_kernel(const typename std::conditional<SH, uint64_t, uint32_t>::type* __restrict__ inter,
+static __global__ void __launch_bounds__(FRONT_BIN_THREADS) msm_front_bins_kernel(const uint32_t* __restrict__ inter,
                                                                                   const uint32_t* __restrict__ bin_base, FrontPlan P,
                                                                                   uint32_t half, uint64_t len, uint32_t nbk, uint32_t clamp,
                                                                                   uint32_t* __restrict__ vals_s, uint32_t* __restrict__ start,
@@ -512,11 +516,11 @@ static __global__ void __launch_bounds__(FRONT_BIN_THREADS) msm_front_bins_kerne
     __shared__ uint32_t h[1u << FRONT_LO_MAX], cur[1u << FRONT_LO_MAX];
     __shared__ uint32_t wave_tmp[FRONT_BIN_THREADS / 64];
     const uint32_t b = blockIdx.x, nbu = 1u << P.lo_bits, lw = b >> P.hi_bits;
-    auto lo_of = [&](typename std::conditional<SH, uint64_t, uint32_t>::type v) { if constexpr (SH) return P.shared_lo(v); else return P.packed_lo(v); };
+    auto lo_of = [&](uint32_t v) { return P.packed_lo(v); };
     uint32_t base, cnt;
     // out of range (cannot happen): an empty bin, its buckets still written
-    front_bin_range(bin_base[SH ? P.shared_entry(b, 0) : b], bin_base[SH ? P.shared_entry(b + 1, 0) : b + 1], len, base, cnt);
-    const uint32_t g0 = SH ? P.shared_first_bucket(b) : P.first_bucket(b, half);
+    front_bin_range(bin_base[b], bin_base[b + 1], len, base, cnt);
+    const uint32_t g0 = P.first_bucket(b, half);
     for (uint32_t k = threadIdx.x; k < nbu; k += FRONT_BIN_THREADS) h[k] = 0;
     __syncthreads();
     for (uint32_t e = threadIdx.x; e < cnt; e += FRONT_BIN_THREADS) atomicAdd(&h[lo_of(inter[base + e])], 1u);
@@ -539,11 +543,9 @@ static __global__ void __launch_bounds__(FRONT_BIN_THREADS) msm_front_bins_kerne
     for (uint32_t e0 = 0; e0 < cnt; e0 += FRONT_BIN_THREADS) {
         const uint32_t e = e0 + threadIdx.x;
         if (e < cnt) {
-            const auto v = inter[base + e];
+            const uint32_t v = inter[base + e];
             const uint32_t pos = atomicAdd(&cur[lo_of(v)], 1u);
-            uint32_t fv;
-            if constexpr (SH) fv = P.shared_final(v);
-            else fv = P.final_value(v, lw);
+            const uint32_t fv = P.final_value(v, lw);
             if (pos < cnt) {
                 if (staged) stage[pos] = fv;
                 else vals_s[base + pos] = fv;
@@ -553,6 +555,91 @@ static __global__ void __launch_bounds__(FRONT_BIN_THREADS) msm_front_bins_kerne
     }
     if (!staged) return;
     for (uint32_t e = threadIdx.x; e < cnt; e += FRONT_BIN_THREADS) vals_s[base + e] = stage[e];
+}
+
+// The bin pass of a table call (FrontPlan::shared).  Bin b is the entries [b * groups, (b + 1) * groups) of the tables - contiguous -, its buckets are keys
+// b << lo .. of the one bucket set.  One LDS counter per (bucket, level) cell, bucket-major: after the exclusive scan a bucket's start is its first cell's
+// and every value is ranked inside its cell, so every bucket comes out level-major - the pair sort's order: a wave of msm_accumulate gathers from one level of
+// the table at a time - in whatever order the lanes arrive.  Hence no barrier inside a sweep.  One workgroup owns the CU's whole LDS: the cells, and behind
+// them a stage of 32-bit values.  A bin that fits the stage (front_table_bin_cap: 27 632 values at c = 20, where a bin of uniform scalars holds ~26 600) is
+// read ONCE, FRONT_TABLE_BIN_HELD independent loads per lane that stay in registers across the scan, ordered in the stage and stored contiguously.  A fuller
+// bin takes two sweeps of FRONT_TABLE_BIN_UNROLL loads per lane and stores through the running cursors.  Any population is served: an all-equal scalar
+// vector puts n values into one cell, and a 32-bit counter holds them
+static __global__ void __launch_bounds__(FRONT_TABLE_BIN_THREADS) msm_front_table_bins_kernel(const uint64_t* __restrict__ inter, const uint32_t* __restrict__ bin_base,
+                                                                                              FrontPlan P, uint64_t len, uint32_t nbk, uint32_t clamp,
+                                                                                              uint32_t* __restrict__ vals_s, uint32_t* __restrict__ start,
+                                                                                              uint32_t* __restrict__ count, uint32_t* __restrict__ iota,
+                                                                                              uint32_t* __restrict__ ckey) {
+    constexpr uint32_t T = FRONT_TABLE_BIN_THREADS, U = FRONT_TABLE_BIN_UNROLL, H = FRONT_TABLE_BIN_HELD;
+    __shared__ uint32_t lds[FRONT_TABLE_LDS_WORDS];
+    __shared__ uint32_t wave_tmp[T / 64];
+    const uint32_t b = blockIdx.x, nbu = 1u << P.lo_bits, ncell = P.table_cells();  // <= FRONT_TABLE_CELLS_MAX (msm_front_plan)
+    uint32_t* const cell = lds;
+    uint32_t* const stage = lds + ncell;  // front_table_bin_cap(ncell) values
+    uint32_t base, cnt;
+    // out of range (cannot happen): an empty bin, its buckets still written
+    front_bin_range(bin_base[P.shared_entry(b, 0)], bin_base[P.shared_entry(b + 1, 0)], len, base, cnt);
+    const uint32_t g0 = P.shared_first_bucket(b);
+    const bool staged = cnt <= front_table_bin_cap(ncell);
+    for (uint32_t k = threadIdx.x; k < ncell; k += T) cell[k] = 0;
+    __syncthreads();
+    uint64_t held[H];
+    if (staged) {
+#pragma unroll
+        for (uint32_t u = 0; u < H; ++u) held[u] = threadIdx.x + u * T < cnt ? inter[base + threadIdx.x + u * T] : ~0ull;
+#pragma unroll
+        for (uint32_t u = 0; u < H; ++u) {
+            const uint32_t cl = P.table_cell(held[u]);
+            if (threadIdx.x + u * T < cnt && cl < ncell) atomicAdd(&cell[cl], 1u);
+        }
+    } else {
+        for (uint32_t e0 = threadIdx.x; e0 < cnt; e0 += T * U) {
+            uint32_t cl[U];
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u) cl[u] = e0 + u * T < cnt ? P.table_cell(inter[base + e0 + u * T]) : ncell;
+#pragma unroll
+            for (uint32_t u = 0; u < U; ++u)
+                if (cl[u] < ncell) atomicAdd(&cell[cl[u]], 1u);
+        }
+    }
+    __syncthreads();
+    front_block_excl_scan<T>(cell, cell, ncell, wave_tmp);
+    for (uint32_t k = threadIdx.x; k < nbu; k += T) {
+        const uint32_t g = g0 + k, at = cell[k * P.levels], cn = (k + 1 < nbu ? cell[(k + 1) * P.levels] : cnt) - at;
+        if (g < nbk) {
+            start[g] = base + at;
+            count[g] = cn;
+            iota[g] = g;
+            ckey[g] = front_pop_key(cn, clamp);
+        }
+    }
+    __syncthreads();  // the cells turn into running cursors
+    if (staged) {
+#pragma unroll
+        for (uint32_t u = 0; u < H; ++u) {
+            const uint32_t cl = P.table_cell(held[u]);
+            if (threadIdx.x + u * T < cnt && cl < ncell) {
+                const uint32_t pos = atomicAdd(&cell[cl], 1u);
+                if (pos < cnt) stage[pos] = P.shared_final(held[u]);
+            }
+        }
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < cnt; e += T) vals_s[base + e] = stage[e];
+        return;
+    }
+    for (uint32_t e0 = threadIdx.x; e0 < cnt; e0 += T * U) {
+        uint64_t v[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) v[u] = e0 + u * T < cnt ? inter[base + e0 + u * T] : ~0ull;
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            const uint32_t cl = P.table_cell(v[u]);
+            if (e0 + u * T < cnt && cl < ncell) {
+                const uint32_t pos = atomicAdd(&cell[cl], 1u);
+                if (pos < cnt) vals_s[base + pos] = P.shared_final(v[u]);
+            }
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2319,7 +2406,8 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
         const uint32_t nb = (table && !folded) ? half : (uint32_t)wc * half;
         const int n_red_win = (table && !folded) ? 1 : wc;  // bucket sets to reduce
         if (front.on && front.shared) {
-          // the same four passes over the levels of a full table: one bucket set, bins without a window in them, 64-bit intermediate pairs
+          // the same four passes over the levels of a full table: one bucket set, bins without a window in them, 64-bit intermediate pairs that carry
+          // their level: the bin pass ranks by (bucket, level) and leaves every bucket level-major
           if constexpr (C::BASES_TABLE) {
             const uint32_t ntab = front.shared_tab();
             BZK_LAUNCH(ctx, "msm_digits", msm_front_hist_kernel<true>, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total, wb, wc,
@@ -2328,8 +2416,8 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
                        front.n_tiles, ntab, front, f_off, f_total);
             BZK_LAUNCH(ctx, "msm_front_scatter", msm_front_scatter_kernel<true>, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total,
                        wb, wc, front, (const uint32_t*)f_hist, (const uint32_t*)f_off, (const uint32_t*)f_total, len, f_base, (uint64_t*)vals);
-            BZK_LAUNCH(ctx, "msm_front_bins", msm_front_bins_kernel<true>, dim3(front.shared_bins()), dim3(FRONT_BIN_THREADS), 0, (const uint64_t*)vals,
-                       (const uint32_t*)f_base, front, half, len, nb, msm_small_pop(len, nb) ? 255u : 65535u, vals_s, BA.start, BA.count, BA.iota, BA.ntask);
+            BZK_LAUNCH(ctx, "msm_front_bins", msm_front_table_bins_kernel, dim3(front.shared_bins()), dim3(FRONT_TABLE_BIN_THREADS), 0, (const uint64_t*)vals,
+                       (const uint32_t*)f_base, front, len, nb, msm_small_pop(len, nb) ? 255u : 65535u, vals_s, BA.start, BA.count, BA.iota, BA.ntask);
           }
         } else if (front.on) {
             // histogram, scan, scatter, bin pass: vals_s, start, count, iota and the population keys come out of the last one (`vals` holds the packed intermediate)
@@ -2340,7 +2428,7 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
                        front.n_tiles, nbins, front, f_off, f_total);
             BZK_LAUNCH(ctx, "msm_front_scatter", msm_front_scatter_kernel<false>, dim3(front.n_tiles), dim3(FRONT_THREADS), 0, (const U128*)scal_eff, n_eff, mont, c, w_total,
                        wb, wc, front, (const uint32_t*)f_hist, (const uint32_t*)f_off, (const uint32_t*)f_total, len, f_base, vals);
-            BZK_LAUNCH(ctx, "msm_front_bins", msm_front_bins_kernel<false>, dim3(nbins), dim3(FRONT_BIN_THREADS), 0, (const uint32_t*)vals, (const uint32_t*)f_base, front,
+            BZK_LAUNCH(ctx, "msm_front_bins", msm_front_bins_kernel, dim3(nbins), dim3(FRONT_BIN_THREADS), 0, (const uint32_t*)vals, (const uint32_t*)f_base, front,
                        half, len, nb, msm_small_pop(len, nb) ? 255u : 65535u, vals_s, BA.start, BA.count, BA.iota, BA.ntask);
         } else if (E > 1) {
             BZK_LAUNCH(ctx, "msm_digits_endo", (msm_digits_endo_kernel<C::ENDO>), dim3((unsigned)((n_eff + 255) / 256)), dim3(256), 0, (const U128*)scal_eff,

@@ -166,6 +166,10 @@ void g16v_declare(WsLayout& ws, G16vBufs& b, uint32_t n_inputs, uint64_t n, size
 int32_t g16v_enqueue(bzk_ctx* ctx, const G16vBufs& b, const hp::KeyHost& K, const hp::KeyUpload& up, const uint8_t* inputs_dev,
                      const uint8_t* proofs_dev, uint64_t n, uint8_t* ok_dev, bool sync);
 void g16v_host_run(const hp::KeyHost& K, const uint8_t* inputs, const uint8_t* proofs, uint64_t n, uint8_t* ok);
+// subgroup.hip: the first of n finite raw points (G1 96 B, G2 192 B) whose subgroup verdict is not 1: *idx (n: none) and *code.  ctx = NULL: host threads
+// on host records; on_device: the records already are in device memory.  sg_host_one: the verdict of one record on the host
+int32_t sg_first_bad(bzk_ctx* ctx, const char* who, bool g2, const uint8_t* pts, bool on_device, uint64_t n, uint64_t* idx, uint8_t* code);
+uint8_t sg_host_one(bool g2, const uint8_t* raw);
 int32_t ntt_run(bzk_ctx* ctx, void* data_dev, uint32_t log_n, int inverse, int coset);  // ntt.hip
 int32_t ntt_h_chain(bzk_ctx* ctx, void* a, void* b, void* c, uint32_t log_m);              // ntt.hip: the h polynomial's 7 transforms, fused
 // msm_g1.hip / msm_g2.hip: windows [w_begin, w_end) (w_end < 0: all) of an MSM over a resident base set (or raw bases when `bases` is

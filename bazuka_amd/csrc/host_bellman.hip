@@ -11,8 +11,9 @@
 //   flag bits of byte 0: 0x80 compressed (must be clear here), 0x40 point at infinity (all other bits zero), 0x20 sort flag
 //   (compressed form only, must be clear).
 // Parameters::read refuses the point at infinity inside h / l / a / b_g1 / b_g2, and so does this reader.  Points are checked
-// to be canonical (< p) and on the curve; the subgroup check of `read(.., checked = true)` is not repeated (a CRS is trusted
-// input: it comes from the network's ceremony, and a wrong key only yields proofs that do not verify).
+// to be canonical (< p) and on the curve, which is `read(.., checked = false)`.  The subgroup check of `checked = true` is no part
+// of decode or of bzk_params_load_bellman: bzk_bellman_params_check and bzk_params_load_bellman_checked below add it, through the
+// per-point functions of subgroup.hip (the queries on the device, the verifying key and ic on the host).
 // In memory everything is the reference's own raw form: little-endian Montgomery limbs (src/zk/groth16/mod.rs:19-38).
 #include <string.h>
 
@@ -144,6 +145,78 @@ bool parallel_points(uint64_t n, int threads, Fn&& one) {  // one(i) -> ok
     return ok.load();
 }
 
+// ---- the checked reader: where the first failure is, in file order
+const char* const ARRAY_NAME[8] = {"the verifying key", "ic", "h", "l", "a", "b_g1", "b_g2", "the array lengths"};
+struct Decoded {
+    Layout L;
+    std::vector<uint8_t> vk, ic, h, l, a, b1, b2;
+};
+struct HeadPoint { uint64_t src, dst; bool g2; };  // file offset, offset in vk870
+const HeadPoint HEAD[6] = {{0, 0, false}, {96, 97, false}, {192, 194, true}, {384, 387, true}, {576, 580, false}, {672, 677, true}};
+bool fail_at(uint64_t report[4], uint64_t array, uint64_t index, uint64_t code) {
+    report[0] = array; report[1] = index; report[2] = code; report[3] = 0;
+    return false;
+}
+// bzk_bellman_params_decode into D; when it refuses, a second, sequential pass names the record (a refusal is the rare path)
+bool decode_located(const uint8_t* bytes, uint64_t len, Decoded& D, uint64_t report[4]) {
+    Layout& L = D.L;
+    if (!layout_of(bytes, len, L)) return fail_at(report, 7, 0, 2);
+    D.vk.resize(870); D.ic.resize(97 * L.n_ic); D.h.resize(96 * L.n_h); D.l.resize(96 * L.n_l); D.a.resize(96 * L.n_a);
+    D.b1.resize(96 * L.n_b1); D.b2.resize(192 * L.n_b2);
+    if (bzk_bellman_params_decode(bytes, len, D.vk.data(), D.ic.data(), D.h.data(), D.l.data(), D.a.data(), D.b1.data(), D.b2.data(), 0) == BZK_OK)
+        return true;
+    uint8_t raw[192];
+    for (uint64_t k = 0; k < 6; ++k)
+        if (!(HEAD[k].g2 ? g2_decode(bytes + HEAD[k].src, raw) : g1_decode(bytes + HEAD[k].src, raw))) return fail_at(report, 0, k, 2);
+    for (uint64_t i = 0; i < L.n_ic; ++i)
+        if (!g1_decode(bytes + L.off_ic + 96 * i, raw)) return fail_at(report, 1, i, 2);
+    const uint64_t off[4] = {L.off_h, L.off_l, L.off_a, L.off_b1}, cnt[4] = {L.n_h, L.n_l, L.n_a, L.n_b1};
+    for (int q = 0; q < 4; ++q)
+        for (uint64_t i = 0; i < cnt[q]; ++i)
+            if (g1_decode(bytes + off[q] + 96 * i, raw) != 1) return fail_at(report, 2 + q, i, 2);  // malformed, off the curve, or the identity inside a query
+    for (uint64_t i = 0; i < L.n_b2; ++i)
+        if (g2_decode(bytes + L.off_b2 + 192 * i, raw) != 1) return fail_at(report, 6, i, 2);
+    return fail_at(report, 7, 0, 2);
+}
+// the six verifying-key points and ic on the host (a handful of points); the identity passes, as it does in the decoder
+bool head_in_subgroup(const Decoded& D, uint64_t report[4]) {
+    for (uint64_t k = 0; k < 6; ++k) {
+        const uint8_t* p = D.vk.data() + HEAD[k].dst;
+        if (p[HEAD[k].g2 ? 192 : 96]) continue;
+        const uint8_t v = sg_host_one(HEAD[k].g2, p);
+        if (v != 1) return fail_at(report, 0, k, v);
+    }
+    for (uint64_t i = 0; i < D.L.n_ic; ++i) {
+        const uint8_t* p = D.ic.data() + 97 * i;
+        if (p[96]) continue;
+        const uint8_t v = sg_host_one(false, p);
+        if (v != 1) return fail_at(report, 1, i, v);
+    }
+    return true;
+}
+// the five queries in file order: q[k] = h, l, a, b_g1, b_g2 as raw records, in host memory or (on_device) where bzk_params_load put them.
+// *pass = false and report filled at the first failure
+int32_t queries_in_subgroup(bzk_ctx* ctx, const char* who, const uint8_t* const q[5], bool on_device, const Layout& L, uint64_t report[4], bool* pass) {
+    const uint64_t cnt[5] = {L.n_h, L.n_l, L.n_a, L.n_b1, L.n_b2};
+    *pass = true;
+    for (int k = 0; k < 5; ++k) {
+        uint64_t idx = 0;
+        uint8_t code = 1;
+        const int32_t st = sg_first_bad(ctx, who, k == 4, q[k], on_device, cnt[k], &idx, &code);
+        if (st != BZK_OK) return st;
+        if (idx < cnt[k]) {
+            *pass = fail_at(report, 2 + k, idx, code);
+            return BZK_OK;
+        }
+    }
+    return BZK_OK;
+}
+std::string failure_text(const uint64_t report[4]) {
+    static const char* const WHAT[3] = {"is on the curve but outside the order-r subgroup", "", "is malformed, off the curve, or the point at infinity inside a query"};
+    if (report[0] >= 7) return "bellman parameters: truncated or malformed";
+    return std::string("bellman parameters: ") + ARRAY_NAME[report[0]] + "[" + std::to_string(report[1]) + "] " + WHAT[report[2] == 0 ? 0 : 2];
+}
+
 }  // namespace
 
 extern "C" {
@@ -239,12 +312,19 @@ int32_t bzk_bellman_params_encode(const uint8_t vk870[870], const uint8_t* ic, u
 // prover derives that from the circuit (a_aux_density, b_input_density, b_aux_density); the caller passes the density maps of
 // the circuit shape (bzk_r1cs_data views 4 and 5 of `MpnCircuit::empty`) and the counts must agree with the file.
 // vk_out (optional) receives bincode(Groth16VerifyingKey) = 870 + 8 + 97 n_in bytes, what `MpnWork::vk()` is compared with.
-int32_t bzk_params_load_bellman(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len, uint32_t n_in, uint32_t n_aux, const uint8_t* a_density,
-                                const uint8_t* b_density, bzk_params** out, uint8_t* vk_out, uint64_t vk_cap) {
+// report = NULL: the unchecked reader.  Otherwise `Parameters::read(.., checked = true)`: the verifying key and ic are checked on the host before anything is
+// uploaded, the queries on the device in the arrays bzk_params_load has just uploaded (one upload; a failure frees the handle again)
+static int32_t load_bellman(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len, uint32_t n_in, uint32_t n_aux, const uint8_t* a_density,
+                            const uint8_t* b_density, bzk_params** out, uint8_t* vk_out, uint64_t vk_cap, uint64_t* report) {
     if (!ctx || !bytes || !out || !a_density || !b_density) return BZK_E_ARG;
     *out = nullptr;
+    if (report) report[0] = report[1] = report[2] = report[3] = 0;
     Layout L;
-    if (!layout_of(bytes, len, L)) { ctx->last_error = "bellman parameters: truncated or malformed"; return BZK_E_ARG; }
+    if (!layout_of(bytes, len, L)) {
+        ctx->last_error = "bellman parameters: truncated or malformed";
+        if (report) fail_at(report, 7, 0, 2);
+        return BZK_E_ARG;
+    }
     uint64_t n_a = 0, n_b = 0;
     for (uint64_t i = 0; i < (uint64_t)n_in + n_aux; ++i) { n_a += a_density[i] != 0; n_b += b_density[i] != 0; }
     const uint64_t m = L.n_h + 1;
@@ -253,27 +333,73 @@ int32_t bzk_params_load_bellman(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len
     if (L.n_ic != n_in || L.n_l != n_aux || L.n_a != n_a || L.n_b1 != n_b || L.n_b2 != n_b || ((uint64_t)1 << log_m) != m || log_m > 28) {
         ctx->last_error = "bellman parameters: array lengths do not fit the circuit shape (ic " + std::to_string(L.n_ic) + ", h " + std::to_string(L.n_h) +
                           ", l " + std::to_string(L.n_l) + ", a " + std::to_string(L.n_a) + ", b " + std::to_string(L.n_b1) + "/" + std::to_string(L.n_b2) + ")";
+        if (report) fail_at(report, 7, 0, 2);
         return BZK_E_ARG;
     }
-    std::vector<uint8_t> vk(870), ic(97 * L.n_ic), h(96 * L.n_h), l(96 * L.n_l), a(96 * L.n_a), b1(96 * L.n_b1), b2(192 * L.n_b2);
-    if (bzk_bellman_params_decode(bytes, len, vk.data(), ic.data(), h.data(), l.data(), a.data(), b1.data(), b2.data(), 0) != BZK_OK) {
-        ctx->last_error = "bellman parameters: a point is malformed, not on the curve, or the point at infinity inside a query";
-        return BZK_E_ARG;
+    Decoded D;
+    if (report) {
+        if (!decode_located(bytes, len, D, report) || !head_in_subgroup(D, report)) {
+            ctx->last_error = failure_text(report);
+            return BZK_E_ARG;
+        }
+    } else {
+        D.vk.resize(870); D.ic.resize(97 * L.n_ic); D.h.resize(96 * L.n_h); D.l.resize(96 * L.n_l); D.a.resize(96 * L.n_a);
+        D.b1.resize(96 * L.n_b1); D.b2.resize(192 * L.n_b2);
+        if (bzk_bellman_params_decode(bytes, len, D.vk.data(), D.ic.data(), D.h.data(), D.l.data(), D.a.data(), D.b1.data(), D.b2.data(), 0) != BZK_OK) {
+            ctx->last_error = "bellman parameters: a point is malformed, not on the curve, or the point at infinity inside a query";
+            return BZK_E_ARG;
+        }
     }
     if (vk_out) {
         const uint64_t need = 870 + 8 + 97 * L.n_ic;
         if (vk_cap < need) return BZK_E_ARG;
-        memcpy(vk_out, vk.data(), 870);
+        memcpy(vk_out, D.vk.data(), 870);
         const uint64_t cnt = L.n_ic;
         memcpy(vk_out + 870, &cnt, 8);  // bincode u64 length, little-endian host
-        memcpy(vk_out + 878, ic.data(), 97 * L.n_ic);
+        memcpy(vk_out + 878, D.ic.data(), 97 * L.n_ic);
     }
     bzk_params_desc d;
     memset(&d, 0, sizeof d);
     d.n_in = n_in; d.n_aux = n_aux; d.log_m = log_m; d.n_a = (uint32_t)n_a; d.n_b = (uint32_t)n_b;
-    d.vk = vk.data(); d.h = h.data(); d.l = l.data(); d.a = a.data(); d.b_g1 = b1.data(); d.b_g2 = b2.data();
+    d.vk = D.vk.data(); d.h = D.h.data(); d.l = D.l.data(); d.a = D.a.data(); d.b_g1 = D.b1.data(); d.b_g2 = D.b2.data();
     d.a_density = a_density; d.b_density = b_density;
-    return bzk_params_load(ctx, &d, out);
+    const int32_t st = bzk_params_load(ctx, &d, out);
+    if (st != BZK_OK || !report) return st;
+    void* dev[5];
+    bzk_params_buffers_internal(*out, &dev[0], &dev[1], &dev[2], &dev[3], &dev[4]);
+    const uint8_t* q[5];
+    for (int k = 0; k < 5; ++k) q[k] = (const uint8_t*)dev[k];
+    bool pass = false;
+    const int32_t sq = queries_in_subgroup(ctx, "bzk_params_load_bellman_checked", q, true, L, report, &pass);
+    if (sq == BZK_OK && pass) return BZK_OK;
+    bzk_params_free(ctx, *out);
+    *out = nullptr;
+    if (sq != BZK_OK) return sq;
+    ctx->last_error = failure_text(report);
+    return BZK_E_ARG;
+}
+
+int32_t bzk_params_load_bellman(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len, uint32_t n_in, uint32_t n_aux, const uint8_t* a_density,
+                                const uint8_t* b_density, bzk_params** out, uint8_t* vk_out, uint64_t vk_cap) {
+    return load_bellman(ctx, bytes, len, n_in, n_aux, a_density, b_density, out, vk_out, vk_cap, nullptr);
+}
+int32_t bzk_params_load_bellman_checked(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len, uint32_t n_in, uint32_t n_aux, const uint8_t* a_density,
+                                        const uint8_t* b_density, bzk_params** out, uint8_t* vk_out, uint64_t vk_cap, uint64_t report[4]) {
+    if (!report) return BZK_E_ARG;
+    return load_bellman(ctx, bytes, len, n_in, n_aux, a_density, b_density, out, vk_out, vk_cap, report);
+}
+
+// `Parameters::read(reader, checked = true)` as a verdict: 1, or 0 with report = {array, index, verdict code, 0} of the first failure in file order
+int32_t bzk_bellman_params_check(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len, uint64_t report[4]) {
+    if (!bytes || !report) return BZK_E_ARG;
+    report[0] = report[1] = report[2] = report[3] = 0;
+    Decoded D;
+    if (!decode_located(bytes, len, D, report) || !head_in_subgroup(D, report)) return 0;
+    const uint8_t* q[5] = {D.h.data(), D.l.data(), D.a.data(), D.b1.data(), D.b2.data()};
+    bool pass = false;
+    const int32_t st = queries_in_subgroup(ctx, "bzk_bellman_params_check", q, false, D.L, report, &pass);
+    if (st != BZK_OK) return st;
+    return pass ? 1 : 0;
 }
 
 }  // extern "C"

@@ -236,6 +236,7 @@ struct KeySource {
     bzk_ctx* ctx;
     std::string dev_toxic;     // dev mode when non-empty
     std::string files[3];      // bellman Parameters files otherwise
+    bool check_params = false; // --check-params: bzk_params_load_bellman_checked
     std::map<std::vector<uint32_t>, Key> cache;
     std::mutex m;
 
@@ -276,9 +277,16 @@ struct KeySource {
             std::ifstream f(files[shape[0]], std::ios::binary);
             if (!f) throw Fail("cannot open " + files[shape[0]]);
             Bytes blob((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-            ck(bzk_params_load_bellman(ctx, blob.data(), blob.size(), (uint32_t)info[0], (uint32_t)info[1], view<uint8_t>(r.get(), 4),
-                                       view<uint8_t>(r.get(), 5), &k.params, k.vk.data(), k.vk.size()),
-               "bzk_params_load_bellman", ctx);
+            if (check_params) {  // bellman's checked read: every point of the file is tested for the order-r subgroup; the failure names the point
+                uint64_t report[4];
+                ck(bzk_params_load_bellman_checked(ctx, blob.data(), blob.size(), (uint32_t)info[0], (uint32_t)info[1], view<uint8_t>(r.get(), 4),
+                                                   view<uint8_t>(r.get(), 5), &k.params, k.vk.data(), k.vk.size(), report),
+                   "bzk_params_load_bellman_checked", ctx);
+            } else {
+                ck(bzk_params_load_bellman(ctx, blob.data(), blob.size(), (uint32_t)info[0], (uint32_t)info[1], view<uint8_t>(r.get(), 4),
+                                           view<uint8_t>(r.get(), 5), &k.params, k.vk.data(), k.vk.size()),
+                   "bzk_params_load_bellman", ctx);
+            }
             k.vk.resize(878 + 97 * info[0]);
         }
         fprintf(stderr, "[bzk-worker] proving key for kind %u (L=%u, T=%u, B=%u) ready in %.1f s\n", shape[0], shape[1], shape[2], shape[3],
@@ -326,7 +334,7 @@ struct Options {
     int slots_per_device = 1, threads = 0;
     double poll = 1.0, timeout_s = 30.0;
     long rounds = -1;
-    bool self_check = false, dry_run = false;
+    bool self_check = false, dry_run = false, check_params = false;
     bool defer = false;  // --defer: BZK_SYNTH_DEFER + bzk_groth16_prove_r1cs (the hash-dependent witness values on the device: less host CPU per work)
     bool defer_sig = false;  // --defer-sig: BZK_SYNTH_DEFER_SIG - the same and the EdDSA gadget's ladders (implies --defer)
     uint32_t flags = 0;
@@ -516,7 +524,7 @@ int usage(const char* why) {
     fprintf(stderr,
             "%s\nusage: bzk-worker --node HOST:PORT --address <64 hex> (--dev-toxic SEED | --params DEPOSIT WITHDRAW UPDATE)\n"
             "                  [--devices 0,1,..] [--slots-per-device N] [--threads N] [--poll S] [--rounds N] [--timeout S]\n"
-            "                  [--self-check] [--defer] [--defer-sig] [--sig-len-prefixed] [--dry-run]\n",
+            "                  [--self-check] [--check-params] [--defer] [--defer-sig] [--sig-len-prefixed] [--dry-run]\n",
             why);
     return 2;
 }
@@ -571,6 +579,8 @@ int main(int argc, char** argv) {
             o.defer = true;
         } else if (a == "--defer-sig") {
             o.defer = o.defer_sig = true;
+        } else if (a == "--check-params") {
+            o.check_params = true;
         } else if (a == "--self-check") {
             o.self_check = true;
         } else if (a == "--sig-len-prefixed") {
@@ -605,6 +615,7 @@ int main(int argc, char** argv) {
                         sources.back()->ctx = s.ctx;
                         sources.back()->dev_toxic = o.dev_toxic;
                         for (int x = 0; x < 3; ++x) sources.back()->files[x] = o.files[x];
+                        sources.back()->check_params = o.check_params;
                         s.first = true;
                     }
                     s.keys = sources.back().get();

@@ -107,9 +107,15 @@ SIGNATURES = {
     "bzk_bellman_params_decode": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
     "bzk_bellman_params_encode": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     "bzk_params_load_bellman": (_i32, [_vp, _vp, _u64, _u32, _u32, _vp, _vp, C.POINTER(_vp), _vp, _u64]),
+    "bzk_bellman_params_check": (_i32, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    "bzk_params_load_bellman_checked": (_i32, [_vp, _vp, _u64, _u32, _u32, _vp, _vp, C.POINTER(_vp), _vp, _u64, C.POINTER(_u64)]),
     "bzk_groth16_verify": (_i32, [_vp, _u64, _vp, _u32, _vp]),
     "bzk_groth16_verify_batch": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp]),
     "bzk_groth16_verify_batch_dev": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp]),
+    "bzk_g1_subgroup_check_batch": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "bzk_g1_subgroup_check_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "bzk_g2_subgroup_check_batch": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "bzk_g2_subgroup_check_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp]),
     "bzk_params_read": (_i32, [_vp, _vp, _i32, _vp, _u64, C.POINTER(_u64)]),
     "bzk_groth16_setup": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, C.POINTER(_vp), _vp, _u64]),
     "bzk_groth16_h_dev": (_i32, [_vp, _vp, _vp, _vp, _u32]),
@@ -260,6 +266,14 @@ class BzkError(RuntimeError):
     def __init__(self, msg, status=None):
         super().__init__(msg)
         self.status = status
+
+
+class ParamsCheckError(BzkError):
+    """a point of a proving key failed the checked reader: report = (array 0 vk head .. 6 b_g2, element index, verdict code, 0)"""
+
+    def __init__(self, msg, report):
+        super().__init__(msg, -1)
+        self.report = report
 
 
 BZK_E_UNSAT = -4
@@ -523,6 +537,15 @@ class Bzk:
         self._ck(self.lib.bzk_groth16_verify_batch_dev(self.h, _ptr(vk_bincode), len(vk_bincode), _ptr(inputs), n_inputs, _ptr(proofs), n, _ptr(ok)),
                  "groth16_verify_batch_dev")
 
+    def subgroup_check_batch(self, group: str, pts: bytes, inf: bytes = None) -> bytes:
+        """verdict byte per raw point (group "g1": 96 B, "g2": 192 B): 1 in the subgroup, 0 on the curve outside it, 2 not a curve point"""
+        return _subgroup_check_batch(self.h, group, pts, inf)
+
+    def subgroup_check_batch_dev(self, group: str, pts, inf, n: int, ok):
+        """device buffers: pts n x 96 / 192, inf n flag bytes or None; ok n verdict bytes; synchronises"""
+        fn = {"g1": self.lib.bzk_g1_subgroup_check_batch_dev, "g2": self.lib.bzk_g2_subgroup_check_batch_dev}[group]
+        self._ck(fn(self.h, _ptr(pts), _ptr(inf) if inf is not None else None, n, _ptr(ok)), "subgroup_check_batch_dev")
+
     def merkle4_root_dev(self, leaves, log4: int, nodes=None) -> bytes:
         root = C.create_string_buffer(32)
         self._ck(self.lib.bzk_merkle4_root_dev(self.h, _ptr(leaves), log4, root, _ptr(nodes)), "merkle4_root_dev")
@@ -771,6 +794,23 @@ class Bzk:
         self._ck(self.lib.bzk_params_load_bellman(self.h, _ptr(blob), len(blob), n_in, n_aux, _ptr(a_density), _ptr(b_density), C.byref(h),
                                                   vk, len(vk)), "params_load_bellman")
         return h, vk.raw
+
+    def params_load_bellman_checked(self, blob: bytes, n_in: int, n_aux: int, a_density: bytes, b_density: bytes):
+        """params_load_bellman with the subgroup check of every point (`Parameters::read(.., checked = true)`): a failed point raises
+        ParamsCheckError, whose `report` is (array, index, verdict code, 0); no handle is left"""
+        h = C.c_void_p()
+        vk = C.create_string_buffer(878 + 97 * n_in)
+        report = (C.c_uint64 * 4)()
+        st = self.lib.bzk_params_load_bellman_checked(self.h, _ptr(blob), len(blob), n_in, n_aux, _ptr(a_density), _ptr(b_density), C.byref(h),
+                                                      vk, len(vk), report)
+        if st == -1 and not h.value:
+            raise ParamsCheckError("params_load_bellman_checked: " + self.lib.bzk_last_error(self.h).decode(), tuple(report))
+        self._ck(st, "params_load_bellman_checked")
+        return h, vk.raw
+
+    def bellman_params_check(self, blob: bytes):
+        """(verdict, report): `Parameters::read(.., checked = true)` as a verdict, the queries on the device"""
+        return _bellman_params_check(self.h, blob)
 
     def params_free(self, ph):
         self.lib.bzk_params_free(self.h, ph)
@@ -1543,6 +1583,36 @@ def _groth16_verify_batch(ctx_handle, vk_bincode: bytes, inputs: bytes, n_inputs
 def host_groth16_verify_batch(vk_bincode: bytes, inputs: bytes, n_inputs: int, proofs: bytes) -> bytes:
     """Bzk.groth16_verify_batch without a device: the same per-proof functions over the host field on host threads"""
     return _groth16_verify_batch(None, vk_bincode, inputs, n_inputs, proofs)
+
+
+def _subgroup_check_batch(ctx_handle, group: str, pts: bytes, inf: bytes = None) -> bytes:
+    size = {"g1": 96, "g2": 192}[group]
+    n = len(pts) // size
+    if len(pts) != size * n or (inf is not None and len(inf) != n):
+        raise BzkError("subgroup_check_batch: pts must hold %d bytes per point and inf one flag per point" % size)
+    lib = load_library()
+    fn = {"g1": lib.bzk_g1_subgroup_check_batch, "g2": lib.bzk_g2_subgroup_check_batch}[group]
+    ok = C.create_string_buffer(max(n, 1))
+    _st(fn(ctx_handle, _ptr(pts) if n else None, _ptr(inf) if inf else None, n, ok), "subgroup_check_batch")
+    return ok.raw[:n]
+
+
+def _bellman_params_check(ctx_handle, blob: bytes):
+    report = (C.c_uint64 * 4)()
+    st = load_library().bzk_bellman_params_check(ctx_handle, _ptr(blob), len(blob), report)
+    if st < 0:
+        _st(st, "bellman_params_check")
+    return st, tuple(report)
+
+
+def host_bellman_params_check(blob: bytes):
+    """Bzk.bellman_params_check without a device: the whole check on host threads"""
+    return _bellman_params_check(None, blob)
+
+
+def host_subgroup_check_batch(group: str, pts: bytes, inf: bytes = None) -> bytes:
+    """Bzk.subgroup_check_batch without a device: the same per-point functions over the host field on host threads"""
+    return _subgroup_check_batch(None, group, pts, inf)
 
 
 def host_sha512(b: bytes) -> bytes:

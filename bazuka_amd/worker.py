@@ -178,10 +178,12 @@ class BellmanKeys:
     """Proving keys of a real network: bellman `Parameters` files (the format the reference's external prover loads,
     README.md:26-28), one per circuit kind.  The file does not carry the density maps (bellman's prover derives them from the
     circuit), so they come from the all-disabled circuit of the work's shape; bzk_params_load_bellman checks every array
-    length of the file against them.  `__call__(work)` returns the params handle like DevSetup."""
+    length of the file against them.  `__call__(work)` returns the params handle like DevSetup.  checked: every point of the file is also
+    tested for the order-r subgroup (`Parameters::read(.., checked = true)`; bzk_params_load_bellman_checked) - a key with a failing point
+    raises lib.ParamsCheckError."""
 
-    def __init__(self, bzk: L.Bzk, path_by_kind: dict[int, str]):
-        self.bzk, self.paths, self.cache = bzk, path_by_kind, {}
+    def __init__(self, bzk: L.Bzk, path_by_kind: dict[int, str], checked: bool = False):
+        self.bzk, self.paths, self.cache, self.checked = bzk, path_by_kind, {}, checked
         import threading
         self._lock = threading.Lock()
 
@@ -195,7 +197,8 @@ class BellmanKeys:
             r = DevSetup.shape_circuit(None, kind, L4, T4, B4)
             with open(self.paths[kind], "rb") as f:
                 blob = f.read()
-            self.cache[key] = self.bzk.params_load_bellman(blob, r.n_in, r.n_aux, r.view("a_density"), r.view("b_density"))
+            load = self.bzk.params_load_bellman_checked if self.checked else self.bzk.params_load_bellman
+            self.cache[key] = load(blob, r.n_in, r.n_aux, r.view("a_density"), r.view("b_density"))
             r.free()
         return self.cache[key]
 
@@ -454,6 +457,7 @@ def main(argv=None):
     ap.add_argument("--dev-toxic", help="seed of the dev-mode CRS (tau, alpha, beta, gamma, delta per circuit kind)")
     ap.add_argument("--params", nargs=3, metavar=("DEPOSIT", "WITHDRAW", "UPDATE"),
                     help="bellman `Parameters` files of the network's three circuits (instead of --dev-toxic)")
+    ap.add_argument("--check-params", action="store_true", help="with --params: test every point of the key files for the order-r subgroup while loading (bellman's checked read)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--devices", default=None, help="comma-separated GPU ordinals of this node to prove on (replicas); overrides --device")
     ap.add_argument("--slots-per-device", type=int, default=1, help="prover slots per GPU (they share the device-resident CRS)")
@@ -489,7 +493,7 @@ def main(argv=None):
     os.environ.setdefault("AMD_DIRECT_DISPATCH", "0")
 
     def key_source(bzk):
-        return BellmanKeys(bzk, dict(enumerate(a.params))) if a.params else DevSetup(bzk, {k: toxic(k) for k in range(3)})
+        return BellmanKeys(bzk, dict(enumerate(a.params)), checked=a.check_params) if a.params else DevSetup(bzk, {k: toxic(k) for k in range(3)})
 
     slots, closers = [], []
     for d in devices:

@@ -484,6 +484,31 @@ int32_t bzk_groth16_verify_batch(bzk_ctx* ctx, const uint8_t* vk, uint64_t vk_le
                                  const uint8_t* proofs, uint64_t n, uint8_t* ok);
 int32_t bzk_groth16_verify_batch_dev(bzk_ctx* ctx, const uint8_t* vk, uint64_t vk_len, const void* inputs_dev, uint32_t n_inputs,
                                      const void* proofs_dev, uint64_t n, void* ok_dev);
+/* Subgroup membership of n raw points (little-endian Montgomery limbs: G1 x | y = 96 B, G2 x.c0 | x.c1 | y.c0 | y.c1 = 192 B; what
+ * bzk_bellman_params_decode emits), one GPU lane per point: the third check of bls12_381 `from_uncompressed` after canonical range and the
+ * curve equation.  ok[i] = 1: in the order-r subgroup; 0: on the curve but outside it; 2: not a valid finite curve point (a coordinate's limbs
+ * >= p, or off the curve).  inf (n bytes, may be NULL): a record with inf[i] != 0 is the identity, its bytes are not read and ok[i] = 1.
+ * G1: [X]([X] P) == (BETA x, -y); G2: [X] P == psi(P); X = 0xd201000000010000, the ladders by complete projective formulas, so every
+ * point - of any order - runs the same steps.  Null pts / ok with n > 0: BZK_E_ARG, nothing written; n = 0: BZK_OK.  ctx = NULL runs the same
+ * per-point functions over the host field on the host's threads.  With a context the records are staged in rounds of 2^18 points (the workspace
+ * holds one round: records, flags and verdict bytes).  The _dev
+ * forms take device pointers (pts 4-byte aligned), need a context, and launch rounds of 2^18 points.  Synchronises. */
+int32_t bzk_g1_subgroup_check_batch(bzk_ctx* ctx, const uint8_t* pts, const uint8_t* inf, uint64_t n, uint8_t* ok);
+int32_t bzk_g1_subgroup_check_batch_dev(bzk_ctx* ctx, const void* pts_dev, const void* inf_dev, uint64_t n, void* ok_dev);
+int32_t bzk_g2_subgroup_check_batch(bzk_ctx* ctx, const uint8_t* pts, const uint8_t* inf, uint64_t n, uint8_t* ok);
+int32_t bzk_g2_subgroup_check_batch_dev(bzk_ctx* ctx, const void* pts_dev, const void* inf_dev, uint64_t n, void* ok_dev);
+/* bellman `Parameters::read(reader, checked = true)` as a verdict: everything bzk_bellman_params_decode checks, plus the subgroup check of the
+ * six verifying-key points, of ic and of the five queries.  Returns 1 (every point passes), 0 (one does not; report says which), negative on
+ * bad arguments (bytes or report NULL) or a device failure.  report = {array: 0 vk head (alpha_g1, beta_g1, beta_g2, gamma_g2, delta_g1,
+ * delta_g2), 1 ic, 2 h, 3 l, 4 a, 5 b_g1, 6 b_g2, 7 the array lengths do not fit the blob (or, in the loader, the circuit shape); element index;
+ * verdict code as above (2 also for the identity inside a query); 0} of the first failure in file order; zeros on success.  The identity passes
+ * inside the verifying key and ic, as it does in the decoder.  ctx = NULL: host threads; with a context the queries run on the device.
+ * bzk_params_load_bellman_checked: bzk_params_load_bellman with that check - same handle, same vk_out bytes on success; on a failed point
+ * BZK_E_ARG, report filled, bzk_last_error naming the array and index, *out NULL.  The queries are checked where bzk_params_load put them (one
+ * upload: the kernels read the loaded arrays, and a failure frees the handle again); the verifying key and ic are checked on the host first. */
+int32_t bzk_bellman_params_check(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len, uint64_t report[4]);
+int32_t bzk_params_load_bellman_checked(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len, uint32_t n_in, uint32_t n_aux, const uint8_t* a_density,
+                                        const uint8_t* b_density, bzk_params** out, uint8_t* vk_out, uint64_t vk_cap, uint64_t report[4]);
 /* reads a CRS component back (tests): which = 0 vk (870 B), 1 h, 2 l, 3 a, 4 b_g1, 5 b_g2 */
 int32_t bzk_params_read(bzk_ctx* ctx, const bzk_params* params, int32_t which, uint8_t* out, uint64_t cap, uint64_t* size_out);
 

@@ -348,6 +348,25 @@ impl Gpu {
         Ok(ok.into_iter().map(|b| b != 0).collect())
     }
 
+    /// The order-r test of `G1Affine::from_uncompressed` (bls12_381 `is_torsion_free`) for raw points (x | y, little-endian Montgomery limbs),
+    /// one device lane per point: 1 = in the subgroup, 0 = on the curve outside it, 2 = not a finite curve point.
+    pub fn subgroup_check_g1(&self, pts: &[[u8; 96]]) -> Result<Vec<u8>, GpuError> {
+        let mut ok = vec![0u8; pts.len()];
+        check(self.0, unsafe {
+            sys::bzk_g1_subgroup_check_batch(self.0, pts.as_ptr() as *const u8, ptr::null(), pts.len() as u64, ok.as_mut_ptr())
+        })?;
+        Ok(ok)
+    }
+
+    /// The same for G2 (x.c0 | x.c1 | y.c0 | y.c1).
+    pub fn subgroup_check_g2(&self, pts: &[[u8; 192]]) -> Result<Vec<u8>, GpuError> {
+        let mut ok = vec![0u8; pts.len()];
+        check(self.0, unsafe {
+            sys::bzk_g2_subgroup_check_batch(self.0, pts.as_ptr() as *const u8, ptr::null(), pts.len() as u64, ok.as_mut_ptr())
+        })?;
+        Ok(ok)
+    }
+
     /// SHA-512 per message, one device lane each
     pub fn sha512_batch(&self, msgs: &[&[u8]]) -> Result<Vec<[u8; 64]>, GpuError> {
         let mut off = Vec::with_capacity(msgs.len() + 1);
@@ -563,6 +582,37 @@ impl ProvingParams {
                                          &mut params, vk.as_mut_ptr(), vk.len() as u64)
         })?;
         Ok(ProvingParams { gpu, params, vk_bincode: vk })
+    }
+
+    /// `bellman::groth16::Parameters::<Bls12>::read(reader, checked)` shaped: the whole reader is consumed, `checked = true` also tests every
+    /// point for the order-r subgroup (the queries on the device, in the arrays the load uploads).  A failing point is
+    /// `GpuError::Status(BZK_E_ARG, ..)` whose text names the array and index; no parameters are left on the device.
+    pub fn read<R: std::io::Read>(device: i32, mut reader: R, checked: bool, n_in: u32, n_aux: u32, a_density: &[u8], b_density: &[u8]) -> Result<Self, GpuError> {
+        let mut bytes = Vec::new();
+        reader.read_to_end(&mut bytes).map_err(|e| GpuError::Status(sys::BZK_E_ARG, format!("Parameters::read: {e}")))?;
+        if !checked {
+            return Self::from_bellman(device, &bytes, n_in, n_aux, a_density, b_density);
+        }
+        let gpu = Gpu::new(device)?;
+        let mut params = ptr::null_mut();
+        let mut vk = vec![0u8; 878 + 97 * n_in as usize];
+        let mut report = [0u64; 4];
+        check(gpu.0, unsafe {
+            sys::bzk_params_load_bellman_checked(gpu.0, bytes.as_ptr(), bytes.len() as u64, n_in, n_aux, a_density.as_ptr(), b_density.as_ptr(),
+                                                 &mut params, vk.as_mut_ptr(), vk.len() as u64, report.as_mut_ptr())
+        })?;
+        Ok(ProvingParams { gpu, params, vk_bincode: vk })
+    }
+
+    /// `Parameters::read(.., checked = true)` as a verdict without loading anything: `Ok(None)` when every point passes, else
+    /// `Ok(Some([array, index, verdict code, 0]))` of the first failure in file order (array 0 = verifying key head, 1 ic, 2 h, 3 l, 4 a, 5 b_g1, 6 b_g2).
+    pub fn check_bellman(gpu: &Gpu, bytes: &[u8]) -> Result<Option<[u64; 4]>, GpuError> {
+        let mut report = [0u64; 4];
+        let st = unsafe { sys::bzk_bellman_params_check(gpu.0, bytes.as_ptr(), bytes.len() as u64, report.as_mut_ptr()) };
+        if st < 0 {
+            check(gpu.0, st)?;
+        }
+        Ok(if st == 1 { None } else { Some(report) })
     }
 }
 

@@ -93,8 +93,8 @@ struct bzk_mpn {
         for (auto& kv : a.tokens) t.set_leaf(kv.first, token_leaf(kv.second));
         return t;
     }
-    void set_with_tokens_root(uint64_t i, const MpnAccount& a, const ZkScalar& tokens_root) {
-        acct[i] = a;
+    // the account tree's side of an account write whose token root the caller already has (`acct` is the caller's to write)
+    void set_leaf_with_tokens_root(uint64_t i, const MpnAccount& a, const ZkScalar& tokens_root) {
         ZkScalar v[5] = {ZkScalar::from_u64(a.tx_nonce), ZkScalar::from_u64(a.withdraw_nonce), a.address.x, a.address.y, tokens_root};
         accounts->set_leaf(i, poseidon_hash(v, 5));
     }

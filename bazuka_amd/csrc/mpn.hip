@@ -110,92 +110,23 @@ PinnedPool& pinned_pool() {
 void* pinned_pool_take(size_t bytes) { return pinned_pool().take(bytes); }
 void pinned_pool_give(void* p, size_t bytes) { pinned_pool().give(p, bytes); }
 
-// update::update for the queued transactions (src/mpn/update.rs:8-299); mutates the world.
-static void build_transitions(bzk_mpn& w, int log4_batch, const ZkScalar& fee_token, std::vector<UpdateTransition>& out,
-                              uint64_t& fee_sum, uint64_t& rejected) {
-    const size_t cap = (size_t)1 << (2 * log4_batch);
-    fee_sum = 0;
-    rejected = 0;
-    std::vector<MpnTx> rest;
-    for (const MpnTx& tx : w.mempool) {
-        if (out.size() == cap) {
-            rest.push_back(tx);
-            continue;
-        }
-        if (tx.fee.token_id != fee_token || !tx.src_pub.is_on_curve() || !tx.dst_pub.is_on_curve()) { ++rejected; continue; }
-        long src_index = -1, dst_index = -1;
-        for (auto& kv : w.acct) {
-            if (kv.second.address == tx.src_pub && src_index < 0) src_index = (long)kv.first;
-            if (kv.second.address == tx.dst_pub && dst_index < 0) dst_index = (long)kv.first;
-        }
-        if (src_index < 0) { ++rejected; continue; }
-        if (dst_index < 0) dst_index = w.acct.empty() ? 0 : (long)(w.acct.rbegin()->first + 1);  // next free slot
-        MpnAccount src_before = w.get(src_index), dst_before0 = w.get(dst_index);
-        // (the reference passes the ACCOUNT-tree log4 size here, SURVEY App. E; harmless, kept)
-        long sti = src_before.find_token_index(w.L, tx.amount.token_id, false);
-        long dti = dst_before0.find_token_index(w.L, tx.amount.token_id, true);
-        long sfi = src_before.find_token_index(w.L, tx.fee.token_id, false);
-        if (sti < 0 || dti < 0 || sfi < 0) { ++rejected; continue; }
-        Money src_token = src_before.tokens[sti];
-        const bool dst_has = dst_before0.tokens.count(dti) != 0;
-        if (tx.nonce != src_before.tx_nonce + 1 || !(src_before.address == tx.src_pub) ||
-            (dst_before0.address.is_on_curve() && !(dst_before0.address == tx.dst_pub)) ||
-            (dst_has && src_token.token_id != dst_before0.tokens[dti].token_id) || src_token.token_id != tx.amount.token_id ||
-            src_token.amount < tx.amount.amount) {
-            ++rejected;
-            continue;
-        }
-        // All rejection tests of update.rs that depend only on account DATA are decided before the state is
-        // touched (the reference works on an isolated mirror and discards it on reject; the effect is the same).
-        MpnAccount src_after = src_before;
-        src_after.tx_nonce += 1;
-        src_after.tokens[sti].amount -= tx.amount.amount;
-        if (!src_after.tokens.count(sfi)) { ++rejected; continue; }
-        const Money src_fee_token = src_after.tokens[sfi];
-        if (src_fee_token.token_id != tx.fee.token_id || src_fee_token.amount < tx.fee.amount) { ++rejected; continue; }
-
-        UpdateTransition t;
-        t.enabled = true;
-        t.tx = tx;
-        t.src_index = src_index; t.dst_index = dst_index;
-        t.src_token_index = sti; t.dst_token_index = dti; t.src_fee_token_index = sfi;
-        t.src_before = src_before;
-        t.src_before_balance = src_token;
-        // token tree of the sender, updated in place step by step (one root path per update, as set_data does)
-        SparseTree4 stree = w.tokens_tree(src_before);
-        t.src_before_balances_hash = stree.root();
-        t.src_proof = w.accounts->prove(src_index);
-        t.src_balance_proof = stree.prove(sti);
-        stree.set_leaf(sti, token_leaf(src_after.tokens[sti]));
-        t.src_before_fee_balance = src_fee_token;
-        t.src_fee_balance_proof = stree.prove(sfi);
-        src_after.tokens[sfi].amount -= tx.fee.amount;
-        stree.set_leaf(sfi, token_leaf(src_after.tokens[sfi]));
-        w.set_with_tokens_root(src_index, src_after, stree.root());
-        t.dst_proof = w.accounts->prove(dst_index);
-        MpnAccount dst_before = w.get(dst_index);  // read AFTER the sender update (matters when src == dst)
-        SparseTree4 dtree = w.tokens_tree(dst_before);
-        t.dst_balance_proof = dtree.prove(dti);
-        t.dst_before = dst_before;
-        t.dst_before_balances_hash = dtree.root();
-        t.dst_before_balance = dst_before.tokens.count(dti) ? dst_before.tokens[dti] : Money();
-        MpnAccount dst_after = dst_before;
-        dst_after.address = tx.dst_pub;
-        if (!dst_after.tokens.count(dti)) dst_after.tokens[dti] = Money{tx.amount.token_id, 0};
-        dst_after.tokens[dti].amount += tx.amount.amount;
-        dtree.set_leaf(dti, token_leaf(dst_after.tokens[dti]));
-        w.set_with_tokens_root(dst_index, dst_after, dtree.root());
-        fee_sum += tx.fee.amount;
-        t.state_after = w.accounts->root();
-        out.push_back(std::move(t));
-    }
-    w.mempool.swap(rest);
-}
-
 // ------------------------------------------------------------------------------------------------
-// Device path of the witness builders ("replacing the per-tx KV walk in prepare_works", src/mpn/mod.rs:353-414).
+// The witness builders: update::update (src/mpn/update.rs:8-299), deposit::deposit (src/mpn/deposit.rs:11-233) and withdraw::withdraw
+// (src/mpn/withdraw.rs:10-259) for the queued transactions; they mutate the world.  Each kind is ONE acceptance walk (walk_updates,
+// walk_deposits, walk_withdraws): the queue cut at the batch capacity, the account lookup, every rejection rule, the account arithmetic and
+// the transition's fields.  A walk decides on account DATA only and hands the Merkle side - roots before and after, sibling triples, the
+// update of the account tree - to a "trees" back end through five calls:
+//   touch(index, account as it stands)               the first use of an account in this batch
+//   token_write(index, slot, money) -> token event   one leaf write in that account's token tree
+//   account_write(index, account after, last token event) -> account event
+//   run() -> status                                  after the walk; a failure leaves the account tree as it was before the batch
+//   tokens_root_before / token_proof (token event), account_proof / state_after (account event), once run() has succeeded
+// There are two back ends, and they share no code: HostTrees walks the sparse trees event by event, DevBatch plans the same hashes level
+// by level for the device.  Both compute the same proofs; the comparison of their works' bytes (tests/test_gpu_mpn_devtree.py,
+// tests/test_gpu_mpn_builder.py) is what checks one against the other.
 //
-// The host builders above walk the account tree once per transaction: prove -> set -> prove -> set, ~50 sequential Poseidon hashes per
+// Device path ("replacing the per-tx KV walk in prepare_works", src/mpn/mod.rs:353-414).
+// The host back end walks the account tree once per transaction: prove -> set -> prove -> set, ~50 sequential Poseidon hashes per
 // update transaction (1.06 ms on a host core at L = 15, T = 3: 0.27 s of a 256-tx batch).  Inside a batch every proof is taken against
 // the state the previous transition left, so the transactions cannot simply be hashed side by side - but the hashes can be grouped BY
 // LEVEL: every transaction's ACCEPTANCE depends on account data only (balances, nonces, keys), so a first pass decides the batch and
@@ -398,21 +329,64 @@ struct DevBatch {
             for (int k = 0; k < 3; ++k) p[lv][k] = P.value(e.sib[lv][k]);
         return p;
     }
+    ZkScalar tokens_root_before(size_t tok_ev) const { return P.value(tok[tok_ev].root_before); }
+    Proof4 token_proof(size_t tok_ev) const { return proof(tok[tok_ev]); }
+    Proof4 account_proof(size_t acc_ev) const { return proof(acc[acc_ev]); }
+    ZkScalar state_after(size_t acc_ev) const { return P.value(acc[acc_ev].root_after); }
+};
+
+// The host back end: the immediate walk of the sparse trees, which stores per event what the walk asks for afterwards.  Nothing of the
+// planner above is used here (see the head of this section).  An account's token tree is built on its first touch and then kept up to
+// date write by write for the length of the batch: the same values as rebuilding it per transaction, and fewer hashes.
+struct HostTrees {
+    bzk_mpn& w;
+    std::map<uint64_t, SparseTree4> tokens;
+    struct TokenEvent { ZkScalar root_before; Proof4 proof; };
+    struct AccountEvent { Proof4 proof; ZkScalar state_after; };
+    std::vector<TokenEvent> tok;
+    std::vector<AccountEvent> acc;
+    explicit HostTrees(bzk_mpn& world) : w(world) {}
+    void touch(uint64_t index, const MpnAccount& as_it_stands) {
+        if (!tokens.count(index)) tokens.emplace(index, w.tokens_tree(as_it_stands));
+    }
+    // one root path per write, as set_data does
+    size_t token_write(uint64_t index, uint64_t slot, const Money& m) {
+        SparseTree4& t = tokens.at(index);
+        tok.push_back({t.root(), t.prove(slot)});
+        t.set_leaf(slot, token_leaf(m));
+        return tok.size() - 1;
+    }
+    size_t account_write(uint64_t index, const MpnAccount& a, size_t) {
+        // the siblings of the account's leaf (independent of the leaf itself), against the tree as the previous event left it
+        acc.push_back({w.accounts->prove(index), ZkScalar()});
+        w.set_leaf_with_tokens_root(index, a, tokens.at(index).root());
+        acc.back().state_after = w.accounts->root();
+        return acc.size() - 1;
+    }
+    int32_t run() { return BZK_OK; }  // everything was hashed on the way
+    const ZkScalar& tokens_root_before(size_t tok_ev) const { return tok[tok_ev].root_before; }
+    const Proof4& token_proof(size_t tok_ev) const { return tok[tok_ev].proof; }
+    const Proof4& account_proof(size_t acc_ev) const { return acc[acc_ev].proof; }
+    const ZkScalar& state_after(size_t acc_ev) const { return acc[acc_ev].state_after; }
 };
 }  // namespace
 
-// The device builders decide a batch on account data first (balances, nonces, queue) and hash afterwards in one batched step.  If that
-// step fails (allocation, HIP error) the decision must not stay behind - the Merkle tree was not advanced, so every later root, proof
-// or work of this handle would silently disagree with its accounts.  First-touch copies of the accounts; the caller keeps
-// the old queue in `rest` after the swap.
+// A walk changes the world's accounts as it decides (the next transaction of the batch sees them).  If the back end's run() fails
+// (allocation, HIP error) the decision must not stay behind - the Merkle tree was not advanced, so every later root, proof or work of
+// this handle would silently disagree with its accounts.  First-touch copies of the accounts; write() is the one place an
+// account event changes `w.acct`.  The host back end cannot fail, so there the copies are never used.
 struct AcctUndo {
     bzk_mpn& w;
     std::map<uint64_t, std::pair<bool, MpnAccount>> before;  // slot -> (existed, contents)
     explicit AcctUndo(bzk_mpn& w_) : w(w_) {}
-    void note(uint64_t i) {
-        if (before.count(i)) return;
-        auto it = w.acct.find(i);
-        before[i] = {it != w.acct.end(), it != w.acct.end() ? it->second : MpnAccount()};
+    template <class Trees>
+    size_t write(Trees& B, uint64_t i, const MpnAccount& after, size_t tok_ev) {
+        if (!before.count(i)) {
+            auto it = w.acct.find(i);
+            before[i] = {it != w.acct.end(), it != w.acct.end() ? it->second : MpnAccount()};
+        }
+        w.acct[i] = after;
+        return B.account_write(i, after, tok_ev);
     }
     void rollback() {
         for (auto& kv : before) {
@@ -421,14 +395,28 @@ struct AcctUndo {
         }
     }
 };
+// the end of every walk: `rest` holds the queue's tail and is swapped in; the last `n` transitions of `out` are this batch's.  A failed
+// run() leaves nothing of the batch behind: accounts, queue and (untouched) tree agree again
+template <class Trees, class Tx, class Tr>
+static int32_t run_or_roll_back(Trees& B, AcctUndo& undo, std::vector<Tx>& queue, std::vector<Tx>& rest, std::vector<Tr>& out, size_t n) {
+    queue.swap(rest);
+    if (n == 0) return BZK_OK;
+    const int32_t st = B.run();
+    if (st != BZK_OK) {
+        undo.rollback();
+        queue.swap(rest);
+        out.resize(out.size() - n);
+    }
+    return st;
+}
 
-// update::update (src/mpn/update.rs:8-299) with the Merkle work batched on the device; same acceptance rules, same transitions
-static int32_t build_transitions_dev(bzk_mpn& w, int log4_batch, const ZkScalar& fee_token, std::vector<UpdateTransition>& out,
-                                     uint64_t& fee_sum, uint64_t& rejected) {
+// update::update (src/mpn/update.rs:8-299)
+template <class Trees>
+static int32_t walk_updates(bzk_mpn& w, Trees& B, int log4_batch, const ZkScalar& fee_token, std::vector<UpdateTransition>& out,
+                            uint64_t& fee_sum, uint64_t& rejected) {
     const size_t cap = (size_t)1 << (2 * log4_batch);
     fee_sum = 0;
     rejected = 0;
-    DevBatch B(w);
     AcctUndo undo(w);
     struct Rec { size_t ev_sti, ev_sfi, ev_dti, leaf_src, leaf_dst; };
     std::vector<Rec> recs;
@@ -445,8 +433,9 @@ static int32_t build_transitions_dev(bzk_mpn& w, int log4_batch, const ZkScalar&
             if (kv.second.address == tx.dst_pub && dst_index < 0) dst_index = (long)kv.first;
         }
         if (src_index < 0) { ++rejected; continue; }
-        if (dst_index < 0) dst_index = w.acct.empty() ? 0 : (long)(w.acct.rbegin()->first + 1);
+        if (dst_index < 0) dst_index = w.acct.empty() ? 0 : (long)(w.acct.rbegin()->first + 1);  // next free slot
         MpnAccount src_before = w.get(src_index), dst_before0 = w.get(dst_index);
+        // (the reference passes the ACCOUNT-tree log4 size here, SURVEY App. E; harmless, kept)
         long sti = src_before.find_token_index(w.L, tx.amount.token_id, false);
         long dti = dst_before0.find_token_index(w.L, tx.amount.token_id, true);
         long sfi = src_before.find_token_index(w.L, tx.fee.token_id, false);
@@ -460,6 +449,8 @@ static int32_t build_transitions_dev(bzk_mpn& w, int log4_batch, const ZkScalar&
             ++rejected;
             continue;
         }
+        // All rejection tests of update.rs that depend only on account DATA are decided before the state is
+        // touched (the reference works on an isolated mirror and discards it on reject; the effect is the same).
         MpnAccount src_after = src_before;
         src_after.tx_nonce += 1;
         src_after.tokens[sti].amount -= tx.amount.amount;
@@ -476,14 +467,13 @@ static int32_t build_transitions_dev(bzk_mpn& w, int log4_batch, const ZkScalar&
         t.src_before_balance = src_token;
         t.src_before_fee_balance = src_fee_token;
         Rec r;
+        // token tree of the sender, updated step by step: the amount's slot, then the fee's slot of the tree the first write left
         B.touch(src_index, src_before);
         r.ev_sti = B.token_write(src_index, sti, src_after.tokens[sti]);
         src_after.tokens[sfi].amount -= tx.fee.amount;
         r.ev_sfi = B.token_write(src_index, sfi, src_after.tokens[sfi]);
-        undo.note(src_index);
-        w.acct[src_index] = src_after;
-        r.leaf_src = B.account_write(src_index, src_after, r.ev_sfi);
-        MpnAccount dst_before = w.get(dst_index);  // read AFTER the sender update (matters when src == dst)
+        r.leaf_src = undo.write(B, src_index, src_after, r.ev_sfi);
+        MpnAccount dst_before = w.get(dst_index);  // read AFTER the sender update (matters when src == dst: its token tree has that write too)
         t.dst_before = dst_before;
         t.dst_before_balance = dst_before.tokens.count(dti) ? dst_before.tokens[dti] : Money();
         MpnAccount dst_after = dst_before;
@@ -492,36 +482,38 @@ static int32_t build_transitions_dev(bzk_mpn& w, int log4_batch, const ZkScalar&
         dst_after.tokens[dti].amount += tx.amount.amount;
         B.touch(dst_index, dst_before);
         r.ev_dti = B.token_write(dst_index, dti, dst_after.tokens[dti]);
-        undo.note(dst_index);
-        w.acct[dst_index] = dst_after;
-        r.leaf_dst = B.account_write(dst_index, dst_after, r.ev_dti);
+        r.leaf_dst = undo.write(B, dst_index, dst_after, r.ev_dti);  // its proof: against the tree the sender's leaf write left
         fee_sum += tx.fee.amount;
         out.push_back(std::move(t));
         recs.push_back(r);
     }
-    w.mempool.swap(rest);
-    if (recs.empty()) return BZK_OK;
-    if (const int32_t st = B.run(); st != BZK_OK) {  // nothing of the batch stays: accounts, queue and (untouched) tree agree again
-        undo.rollback();
-        w.mempool.swap(rest);
-        out.resize(out.size() - recs.size());
-        return st;
-    }
+    if (const int32_t st = run_or_roll_back(B, undo, w.mempool, rest, out, recs.size()); st != BZK_OK) return st;
     const size_t first = out.size() - recs.size();
     for (size_t k = 0; k < recs.size(); ++k) {
         UpdateTransition& t = out[first + k];
         const Rec& r = recs[k];
-        t.src_before_balances_hash = B.P.value(B.tok[r.ev_sti].root_before);
-        t.src_balance_proof = B.proof(B.tok[r.ev_sti]);
-        t.src_fee_balance_proof = B.proof(B.tok[r.ev_sfi]);
-        t.dst_before_balances_hash = B.P.value(B.tok[r.ev_dti].root_before);
-        t.dst_balance_proof = B.proof(B.tok[r.ev_dti]);
-        t.src_proof = B.proof(B.acc[r.leaf_src]);
-        t.dst_proof = B.proof(B.acc[r.leaf_dst]);
-        t.state_after = B.P.value(B.acc[r.leaf_dst].root_after);
+        t.src_before_balances_hash = B.tokens_root_before(r.ev_sti);
+        t.src_balance_proof = B.token_proof(r.ev_sti);
+        t.src_fee_balance_proof = B.token_proof(r.ev_sfi);
+        t.dst_before_balances_hash = B.tokens_root_before(r.ev_dti);
+        t.dst_balance_proof = B.token_proof(r.ev_dti);
+        t.src_proof = B.account_proof(r.leaf_src);
+        t.dst_proof = B.account_proof(r.leaf_dst);
+        t.state_after = B.state_after(r.leaf_dst);
     }
     return BZK_OK;
 }
+// the back end is the world's choice (bzk_mpn_set_device)
+static int32_t build_updates(bzk_mpn& w, int log4_batch, const ZkScalar& fee_token, std::vector<UpdateTransition>& out, uint64_t& fee_sum,
+                             uint64_t& rejected) {
+    if (w.dev) {
+        DevBatch B(w);
+        return walk_updates(w, B, log4_batch, fee_token, out, fee_sum, rejected);
+    }
+    HostTrees B(w);
+    return walk_updates(w, B, log4_batch, fee_token, out, fee_sum, rejected);
+}
+
 
 struct LcModeGuard {
     bool prev;
@@ -974,54 +966,12 @@ static ZkScalar native_batch_root(const std::vector<std::vector<ZkScalar>>& item
 // ------------------------------------------------------------------------------------------------
 // deposit::deposit (src/mpn/deposit.rs:11-233) and DepositCircuit (src/mpn/circuits/deposit_circuit.rs:47-293)
 // ------------------------------------------------------------------------------------------------
-static void build_deposits(bzk_mpn& w, int log4_batch, std::vector<DepositTransition>& out, uint64_t& rejected) {
+template <class Trees>
+static int32_t walk_deposits(bzk_mpn& w, Trees& B, int log4_batch, std::vector<DepositTransition>& out, uint64_t& rejected) {
     const size_t cap = (size_t)1 << (2 * log4_batch);
     rejected = 0;
-    std::vector<DepositTx> rest;
-    for (const DepositTx& tx : w.deposit_queue) {
-        if (out.size() == cap) { rest.push_back(tx); continue; }
-        long index = -1;
-        for (auto& kv : w.acct)
-            if (kv.second.address == tx.mpn_address) { index = (long)kv.first; break; }
-        if (index < 0) index = w.acct.empty() ? 0 : (long)(w.acct.rbegin()->first + 1);
-        MpnAccount acc = w.get(index);
-        long ti = acc.find_token_index(w.L, tx.amount.token_id, true);
-        if (ti < 0) { ++rejected; continue; }
-        const bool has = acc.tokens.count(ti) != 0;
-        if ((!(acc.address == PointAffine()) && !(tx.mpn_address == acc.address)) || (has && acc.tokens[ti].token_id != tx.amount.token_id)) {
-            ++rejected;
-            continue;
-        }
-        DepositTransition t;
-        t.enabled = true;
-        t.tx = tx;
-        t.account_index = index;
-        t.token_index = ti;
-        t.before = acc;
-        SparseTree4 tree = w.tokens_tree(acc);
-        t.before_balances_hash = tree.root();
-        t.before_balance = has ? acc.tokens[ti] : Money();
-        t.balance_proof = tree.prove(ti);
-        t.proof = w.accounts->prove(index);
-        MpnAccount upd = acc;
-        upd.address = tx.mpn_address;
-        if (!has) upd.tokens[ti] = Money{tx.amount.token_id, 0};
-        upd.tokens[ti].amount += tx.amount.amount;
-        tree.set_leaf(ti, token_leaf(upd.tokens[ti]));
-        w.set_with_tokens_root(index, upd, tree.root());
-        t.state_after = w.accounts->root();
-        out.push_back(std::move(t));
-    }
-    w.deposit_queue.swap(rest);
-}
-
-// deposit::deposit (src/mpn/deposit.rs:11-233) with the Merkle work batched on the device (see DevBatch)
-static int32_t build_deposits_dev(bzk_mpn& w, int log4_batch, std::vector<DepositTransition>& out, uint64_t& rejected) {
-    const size_t cap = (size_t)1 << (2 * log4_batch);
-    rejected = 0;
-    DevBatch B(w);
     AcctUndo undo(w);
-    struct Rec { size_t ev_tok, leaf; bool had_tokens; };
+    struct Rec { size_t ev_tok, leaf; };
     std::vector<Rec> recs;
     std::vector<DepositTx> rest;
     for (const DepositTx& tx : w.deposit_queue) {
@@ -1052,30 +1002,30 @@ static int32_t build_deposits_dev(bzk_mpn& w, int log4_batch, std::vector<Deposi
         Rec r;
         B.touch(index, acc);
         r.ev_tok = B.token_write(index, ti, upd.tokens[ti]);
-        undo.note(index);
-        w.acct[index] = upd;
-        r.leaf = B.account_write(index, upd, r.ev_tok);
+        r.leaf = undo.write(B, index, upd, r.ev_tok);
         out.push_back(std::move(t));
         recs.push_back(r);
     }
-    w.deposit_queue.swap(rest);
-    if (recs.empty()) return BZK_OK;
-    if (const int32_t st = B.run(); st != BZK_OK) {  // see AcctUndo: nothing of the batch stays behind
-        undo.rollback();
-        w.deposit_queue.swap(rest);
-        out.resize(out.size() - recs.size());
-        return st;
-    }
+    if (const int32_t st = run_or_roll_back(B, undo, w.deposit_queue, rest, out, recs.size()); st != BZK_OK) return st;
     const size_t first = out.size() - recs.size();
     for (size_t k = 0; k < recs.size(); ++k) {
         DepositTransition& t = out[first + k];
-        t.before_balances_hash = B.P.value(B.tok[recs[k].ev_tok].root_before);
-        t.balance_proof = B.proof(B.tok[recs[k].ev_tok]);
-        t.proof = B.proof(B.acc[recs[k].leaf]);
-        t.state_after = B.P.value(B.acc[recs[k].leaf].root_after);
+        t.before_balances_hash = B.tokens_root_before(recs[k].ev_tok);
+        t.balance_proof = B.token_proof(recs[k].ev_tok);
+        t.proof = B.account_proof(recs[k].leaf);
+        t.state_after = B.state_after(recs[k].leaf);
     }
     return BZK_OK;
 }
+static int32_t build_deposits(bzk_mpn& w, int log4_batch, std::vector<DepositTransition>& out, uint64_t& rejected) {
+    if (w.dev) {
+        DevBatch B(w);
+        return walk_deposits(w, B, log4_batch, out, rejected);
+    }
+    HostTrees B(w);
+    return walk_deposits(w, B, log4_batch, out, rejected);
+}
+
 
 static ZkScalar deposit_aux(const std::vector<DepositTransition>& trs, int log4_batch) {
     std::vector<std::vector<ZkScalar>> items;
@@ -1162,54 +1112,6 @@ static void synthesize_deposit(ConstraintSystem& cs, int L, int T, const ZkScala
 // ------------------------------------------------------------------------------------------------
 // withdraw::withdraw (src/mpn/withdraw.rs:10-259) and WithdrawCircuit (src/mpn/circuits/withdraw_circuit.rs:50-413)
 // ------------------------------------------------------------------------------------------------
-static void build_withdraws(bzk_mpn& w, int log4_batch, std::vector<WithdrawTransition>& out, uint64_t& rejected) {
-    const size_t cap = (size_t)1 << (2 * log4_batch);
-    rejected = 0;
-    std::vector<WithdrawTx> rest;
-    for (const WithdrawTx& tx : w.withdraw_queue) {
-        if (out.size() == cap) { rest.push_back(tx); continue; }
-        long index = -1;
-        for (auto& kv : w.acct)
-            if (kv.second.address == tx.mpn_address) { index = (long)kv.first; break; }
-        if (index < 0) { ++rejected; continue; }
-        MpnAccount acc = w.get(index);
-        long ti = acc.find_token_index(w.L, tx.amount.token_id, false), fi = acc.find_token_index(w.L, tx.fee.token_id, false);
-        if (ti < 0 || fi < 0 || !acc.tokens.count(ti)) { ++rejected; continue; }
-        const Money acc_token = acc.tokens[ti];
-        if ((!(acc.address == PointAffine()) && !(tx.mpn_address == acc.address)) ||
-            !jubjub_verify(tx.mpn_address, tx.sign_message(), tx.sig) || tx.nonce != acc.withdraw_nonce + 1 ||
-            tx.amount.token_id != acc_token.token_id || tx.amount.amount > acc_token.amount) {
-            ++rejected;
-            continue;
-        }
-        MpnAccount upd = acc;
-        upd.address = tx.mpn_address;
-        upd.withdraw_nonce += 1;
-        upd.tokens[ti].amount -= tx.amount.amount;
-        if (!upd.tokens.count(fi)) { ++rejected; continue; }
-        const Money acc_fee = upd.tokens[fi];
-        if (tx.fee.token_id != acc_fee.token_id || tx.fee.amount > acc_fee.amount) { ++rejected; continue; }
-        WithdrawTransition t;
-        t.enabled = true;
-        t.tx = tx;
-        t.account_index = index; t.token_index = ti; t.fee_token_index = fi;
-        t.before = acc;
-        t.before_token_balance = acc_token;
-        t.before_fee_balance = acc_fee;
-        SparseTree4 tree = w.tokens_tree(acc);
-        t.before_token_hash = tree.root();
-        t.token_balance_proof = tree.prove(ti);
-        tree.set_leaf(ti, token_leaf(upd.tokens[ti]));
-        t.fee_balance_proof = tree.prove(fi);
-        upd.tokens[fi].amount -= tx.fee.amount;
-        tree.set_leaf(fi, token_leaf(upd.tokens[fi]));
-        t.proof = w.accounts->prove(index);  // siblings of the account leaf (independent of the leaf itself)
-        w.set_with_tokens_root(index, upd, tree.root());
-        t.state_after = w.accounts->root();
-        out.push_back(std::move(t));
-    }
-    w.withdraw_queue.swap(rest);
-}
 
 // The signature checks of a withdraw queue on the device: the sign messages H2(fingerprint, nonce) of the whole queue in one Poseidon batch (on first
 // use), the signatures in chunks of the batch capacity (bzk_jubjub_verify_batch, launch label "jubjub_verify"), each chunk when the builder's loop first asks for a verdict in it.
@@ -1254,16 +1156,24 @@ struct SigBatch {
     }
 };
 
-// withdraw::withdraw (src/mpn/withdraw.rs:10-259) with the Merkle work batched on the device (see DevBatch); the signatures likewise (SigBatch)
-static int32_t build_withdraws_dev(bzk_mpn& w, int log4_batch, std::vector<WithdrawTransition>& out, uint64_t& rejected) {
+// the same verdicts one at a time on the host; cannot fail
+struct HostSigs {
+    const std::vector<WithdrawTx>& queue;
+    int32_t verdict(size_t i, bool& out) {
+        out = jubjub_verify(queue[i].mpn_address, queue[i].sign_message(), queue[i].sig);
+        return BZK_OK;
+    }
+};
+
+// `sigs`: who says whether the signature of queue entry i holds (SigBatch / HostSigs)
+template <class Trees, class Sigs>
+static int32_t walk_withdraws(bzk_mpn& w, Trees& B, Sigs& sigs, int log4_batch, std::vector<WithdrawTransition>& out, uint64_t& rejected) {
     const size_t cap = (size_t)1 << (2 * log4_batch);
     rejected = 0;
-    DevBatch B(w);
     AcctUndo undo(w);
     struct Rec { size_t ev_ti, ev_fi, leaf; };
     std::vector<Rec> recs;
     std::vector<WithdrawTx> rest;
-    SigBatch sigs(w.dev, w.withdraw_queue, cap);
     size_t qi = 0;
     for (const WithdrawTx& tx : w.withdraw_queue) {
         const size_t q = qi++;
@@ -1277,7 +1187,7 @@ static int32_t build_withdraws_dev(bzk_mpn& w, int log4_batch, std::vector<Withd
         if (ti < 0 || fi < 0 || !acc.tokens.count(ti)) { ++rejected; continue; }
         const Money acc_token = acc.tokens[ti];
         bool sig_ok = false;
-        if (const int32_t st = sigs.verdict(q, sig_ok); st != BZK_OK) {  // as when B.run fails below: nothing of the batch stays behind
+        if (const int32_t st = sigs.verdict(q, sig_ok); st != BZK_OK) {  // as when run() fails: nothing of the batch stays behind (the queue was not cut yet)
             undo.rollback();
             out.resize(out.size() - recs.size());
             return st;
@@ -1307,31 +1217,33 @@ static int32_t build_withdraws_dev(bzk_mpn& w, int log4_batch, std::vector<Withd
         r.ev_ti = B.token_write(index, ti, upd.tokens[ti]);
         upd.tokens[fi].amount -= tx.fee.amount;
         r.ev_fi = B.token_write(index, fi, upd.tokens[fi]);
-        undo.note(index);
-        w.acct[index] = upd;
-        r.leaf = B.account_write(index, upd, r.ev_fi);
+        r.leaf = undo.write(B, index, upd, r.ev_fi);
         out.push_back(std::move(t));
         recs.push_back(r);
     }
-    w.withdraw_queue.swap(rest);
-    if (recs.empty()) return BZK_OK;
-    if (const int32_t st = B.run(); st != BZK_OK) {  // see AcctUndo: nothing of the batch stays behind
-        undo.rollback();
-        w.withdraw_queue.swap(rest);
-        out.resize(out.size() - recs.size());
-        return st;
-    }
+    if (const int32_t st = run_or_roll_back(B, undo, w.withdraw_queue, rest, out, recs.size()); st != BZK_OK) return st;
     const size_t first = out.size() - recs.size();
     for (size_t k = 0; k < recs.size(); ++k) {
         WithdrawTransition& t = out[first + k];
-        t.before_token_hash = B.P.value(B.tok[recs[k].ev_ti].root_before);
-        t.token_balance_proof = B.proof(B.tok[recs[k].ev_ti]);
-        t.fee_balance_proof = B.proof(B.tok[recs[k].ev_fi]);
-        t.proof = B.proof(B.acc[recs[k].leaf]);
-        t.state_after = B.P.value(B.acc[recs[k].leaf].root_after);
+        t.before_token_hash = B.tokens_root_before(recs[k].ev_ti);
+        t.token_balance_proof = B.token_proof(recs[k].ev_ti);
+        t.fee_balance_proof = B.token_proof(recs[k].ev_fi);
+        t.proof = B.account_proof(recs[k].leaf);
+        t.state_after = B.state_after(recs[k].leaf);
     }
     return BZK_OK;
 }
+static int32_t build_withdraws(bzk_mpn& w, int log4_batch, std::vector<WithdrawTransition>& out, uint64_t& rejected) {
+    if (w.dev) {
+        DevBatch B(w);
+        SigBatch sigs(w.dev, w.withdraw_queue, (size_t)1 << (2 * log4_batch));
+        return walk_withdraws(w, B, sigs, log4_batch, out, rejected);
+    }
+    HostTrees B(w);
+    HostSigs sigs{w.withdraw_queue};
+    return walk_withdraws(w, B, sigs, log4_batch, out, rejected);
+}
+
 
 static ZkScalar withdraw_aux(const std::vector<WithdrawTransition>& trs, int log4_batch) {
     std::vector<std::vector<ZkScalar>> items;
@@ -1474,6 +1386,41 @@ static void finish_r1cs(bzk_r1cs* r) {
     }
 }
 
+// What an instance is made for.  Matrices: the KeypairAssembly role (matrices + densities, LCs re-evaluated against the supplied values as a
+// self-check).  The others: the pure ProvingAssignment role (values only: no linear-combination bookkeeping at all) - all of them on the
+// host, or with the hash-dependent values left to a DeferProgram, or with the signature gadget's ladders left to it as well.
+enum class Synth { Witness, Matrices, Defer, DeferSig };
+static Synth world_synth(const bzk_mpn& w, bool record_matrices) {
+    return record_matrices ? Synth::Matrices : !w.defer ? Synth::Witness : w.defer_sig ? Synth::DeferSig : Synth::Defer;
+}
+// One circuit instance.  fill(r, dd) runs the synthesize_* of its kind on r.cs (dd: where to note deferred values, or nullptr), sets
+// r.accepted / r.rejected, and returns a status other than BZK_OK to give up (a failed device step of a builder).  what: receives an
+// exception's text.
+template <class Fill>
+static int32_t make_instance(Synth mode, bzk_r1cs** out, Fill&& fill, std::string* what = nullptr) {
+    try {
+        const bool rec = mode == Synth::Matrices;
+        std::unique_ptr<bzk_r1cs> r(new bzk_r1cs(rec));
+        LcModeGuard guard(rec);
+        r->cs.self_check = rec;
+        if (mode == Synth::Defer || mode == Synth::DeferSig) {
+            r->defer.reset(new DeferData());
+            r->defer->sig = mode == Synth::DeferSig;
+        }
+        if (const int32_t st = fill(*r, r->defer.get()); st != BZK_OK) return st;
+        if (r->defer && !r->defer->prog) r->defer.reset();  // no program came out: nothing is deferred
+        if (r->cs.check_failed_at >= 0) return BZK_E_INTERNAL;  // a gadget supplied a value that is not <LC, z>
+        finish_r1cs(r.get());
+        *out = r.release();
+        return BZK_OK;
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    } catch (const std::exception& e) {
+        if (what) *what = e.what();
+        return BZK_E_INTERNAL;
+    }
+}
+
 // groth16.hip (bzk_groth16_prove_r1cs): the instance's arrays as an assignment, and what is deferred in them (nullptr: nothing, or already filled in)
 void r1cs_assignment(const bzk_r1cs* r, bzk_assignment* a, const DeferData** dd, uint64_t* n_in) {
     const ConstraintSystem& cs = r->cs;
@@ -1576,43 +1523,26 @@ int32_t bzk_mpn_update_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_t
                                   int32_t record_matrices, bzk_r1cs** out) {
     if (!w || !commitment || !fee_token || !out || log4_batch > 6) return BZK_E_ARG;
     *out = nullptr;
-    try {
-        const bool dbg = getenv("BZK_DEBUG") != nullptr;
-        auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        double t0 = now();
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double t0 = now(), t1 = t0, t2 = t0;
+    const int32_t st = make_instance(world_synth(*w, record_matrices != 0), out, [&](bzk_r1cs& r, DeferData* dd) -> int32_t {
         const ZkScalar ft = ZkScalar::from_bytes(fee_token);
         const ZkScalar state = w->accounts->root();
         std::vector<UpdateTransition> trs;
-        uint64_t fee_sum = 0, rejected = 0;
-        if (w->dev) { const int32_t ds = build_transitions_dev(*w, (int)log4_batch, ft, trs, fee_sum, rejected); if (ds != BZK_OK) return ds; }
-        else build_transitions(*w, (int)log4_batch, ft, trs, fee_sum, rejected);
-        double t1 = now();
-        const uint64_t accepted = trs.size();
+        uint64_t fee_sum = 0;
+        if (const int32_t ds = build_updates(*w, (int)log4_batch, ft, trs, fee_sum, r.rejected); ds != BZK_OK) return ds;
+        t1 = now();
+        r.accepted = trs.size();
         while (trs.size() < ((size_t)1 << (2 * log4_batch))) trs.push_back(UpdateTransition::null(w->L, w->T));
         ZkScalar auxin[2] = {ft, ZkScalar::from_u64(fee_sum)};
         const ZkScalar aux = poseidon_hash(auxin, 2);
-        const ZkScalar next_state = w->accounts->root();
-        std::unique_ptr<bzk_r1cs> r(new bzk_r1cs(record_matrices != 0));
-        // KeypairAssembly role (matrices + densities, LCs re-evaluated against the supplied values as a self-check)
-        // or pure ProvingAssignment role (values only: no linear-combination bookkeeping at all)
-        LcModeGuard guard(record_matrices != 0);
-        r->cs.self_check = record_matrices != 0;
-        if (w->defer && !record_matrices) { r->defer.reset(new DeferData()); r->defer->sig = w->defer_sig; }
-        synthesize_update(r->cs, w->L, w->T, ZkScalar::from_bytes(commitment), w->height, state, aux, next_state, ft, trs, w->threads, r->defer.get());
-        if (r->defer && !r->defer->prog) r->defer.reset();
-        if (r->cs.check_failed_at >= 0) return BZK_E_INTERNAL;  // a gadget supplied a value that is not <LC, z>
-        double t2 = now();
-        r->accepted = accepted;
-        r->rejected = rejected;
-        finish_r1cs(r.get());
-        if (dbg) fprintf(stderr, "[bzk] update_synthesize: transitions %.3f s, circuit %.3f s, finish %.3f s\n", t1 - t0, t2 - t1, now() - t2);
-        *out = r.release();
+        synthesize_update(r.cs, w->L, w->T, ZkScalar::from_bytes(commitment), w->height, state, aux, w->accounts->root(), ft, trs, w->threads, dd);
+        t2 = now();
         return BZK_OK;
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    } catch (const std::exception&) {
-        return BZK_E_INTERNAL;
-    }
+    });
+    if (st == BZK_OK && getenv("BZK_DEBUG"))
+        fprintf(stderr, "[bzk] update_synthesize: transitions %.3f s, circuit %.3f s, finish %.3f s\n", t1 - t0, t2 - t1, now() - t2);
+    return st;
 }
 
 // The all-disabled instance `MpnCircuit::empty(L, T, B)` with explicit public inputs - the circuit the
@@ -1625,22 +1555,13 @@ int32_t bzk_mpn_update_empty(uint32_t log4_tree, uint32_t log4_token_tree, uint3
         log4_tree > 30 || log4_token_tree == 0 || log4_token_tree > 8)
         return BZK_E_ARG;
     *out = nullptr;
-    try {
+    return make_instance(record_matrices ? Synth::Matrices : Synth::Witness, out, [&](bzk_r1cs& r, DeferData*) -> int32_t {
         std::vector<UpdateTransition> trs((size_t)1 << (2 * log4_batch), UpdateTransition::null((int)log4_tree, (int)log4_token_tree));
-        std::unique_ptr<bzk_r1cs> r(new bzk_r1cs(record_matrices != 0));
-        LcModeGuard guard(record_matrices != 0);
-        r->cs.self_check = record_matrices != 0;
-        synthesize_update(r->cs, (int)log4_tree, (int)log4_token_tree, ZkScalar::from_bytes(commitment), height,
+        synthesize_update(r.cs, (int)log4_tree, (int)log4_token_tree, ZkScalar::from_bytes(commitment), height,
                           ZkScalar::from_bytes(state), ZkScalar::from_bytes(aux_data), ZkScalar::from_bytes(next_state),
                           ZkScalar::from_bytes(fee_token), trs, 1);
-        finish_r1cs(r.get());
-        *out = r.release();
         return BZK_OK;
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    } catch (const std::exception&) {
-        return BZK_E_INTERNAL;
-    }
+    });
 }
 
 // ---- deposits and withdrawals: the other two MpnWorkData variants (src/mpn/mod.rs:243-248)
@@ -1700,64 +1621,32 @@ int32_t bzk_mpn_deposit_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_
                                    bzk_r1cs** out) {
     if (!w || !commitment || !out || log4_batch > 6) return BZK_E_ARG;
     *out = nullptr;
-    try {
+    return make_instance(world_synth(*w, record_matrices != 0), out, [&](bzk_r1cs& r, DeferData* dd) -> int32_t {
         const ZkScalar state = w->accounts->root();
         std::vector<DepositTransition> trs;
-        uint64_t rejected = 0;
-        if (w->dev) { const int32_t ds = build_deposits_dev(*w, (int)log4_batch, trs, rejected); if (ds != BZK_OK) return ds; }
-        else build_deposits(*w, (int)log4_batch, trs, rejected);
-        const uint64_t accepted = trs.size();
+        if (const int32_t ds = build_deposits(*w, (int)log4_batch, trs, r.rejected); ds != BZK_OK) return ds;
+        r.accepted = trs.size();
         const ZkScalar aux = deposit_aux(trs, (int)log4_batch);
         while (trs.size() < ((size_t)1 << (2 * log4_batch))) trs.push_back(DepositTransition::null(w->L, w->T));
-        std::unique_ptr<bzk_r1cs> r(new bzk_r1cs(record_matrices != 0));
-        LcModeGuard guard(record_matrices != 0);
-        r->cs.self_check = record_matrices != 0;
-        if (w->defer && !record_matrices) { r->defer.reset(new DeferData()); r->defer->sig = w->defer_sig; }
-        synthesize_deposit(r->cs, w->L, w->T, ZkScalar::from_bytes(commitment), w->height, state, aux, w->accounts->root(), trs, w->threads, r->defer.get());
-        if (r->defer && !r->defer->prog) r->defer.reset();
-        if (r->cs.check_failed_at >= 0) return BZK_E_INTERNAL;
-        r->accepted = accepted;
-        r->rejected = rejected;
-        finish_r1cs(r.get());
-        *out = r.release();
+        synthesize_deposit(r.cs, w->L, w->T, ZkScalar::from_bytes(commitment), w->height, state, aux, w->accounts->root(), trs, w->threads, dd);
         return BZK_OK;
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    } catch (const std::exception&) {
-        return BZK_E_INTERNAL;
-    }
+    });
 }
 
 int32_t bzk_mpn_withdraw_synthesize(bzk_mpn* w, uint32_t log4_batch, const uint8_t commitment[32], int32_t record_matrices,
                                     bzk_r1cs** out) {
     if (!w || !commitment || !out || log4_batch > 6) return BZK_E_ARG;
     *out = nullptr;
-    try {
+    return make_instance(world_synth(*w, record_matrices != 0), out, [&](bzk_r1cs& r, DeferData* dd) -> int32_t {
         const ZkScalar state = w->accounts->root();
         std::vector<WithdrawTransition> trs;
-        uint64_t rejected = 0;
-        if (w->dev) { const int32_t ds = build_withdraws_dev(*w, (int)log4_batch, trs, rejected); if (ds != BZK_OK) return ds; }
-        else build_withdraws(*w, (int)log4_batch, trs, rejected);
-        const uint64_t accepted = trs.size();
+        if (const int32_t ds = build_withdraws(*w, (int)log4_batch, trs, r.rejected); ds != BZK_OK) return ds;
+        r.accepted = trs.size();
         const ZkScalar aux = withdraw_aux(trs, (int)log4_batch);
         while (trs.size() < ((size_t)1 << (2 * log4_batch))) trs.push_back(WithdrawTransition::null(w->L, w->T));
-        std::unique_ptr<bzk_r1cs> r(new bzk_r1cs(record_matrices != 0));
-        LcModeGuard guard(record_matrices != 0);
-        r->cs.self_check = record_matrices != 0;
-        if (w->defer && !record_matrices) { r->defer.reset(new DeferData()); r->defer->sig = w->defer_sig; }
-        synthesize_withdraw(r->cs, w->L, w->T, ZkScalar::from_bytes(commitment), w->height, state, aux, w->accounts->root(), trs, w->threads, r->defer.get());
-        if (r->defer && !r->defer->prog) r->defer.reset();
-        if (r->cs.check_failed_at >= 0) return BZK_E_INTERNAL;
-        r->accepted = accepted;
-        r->rejected = rejected;
-        finish_r1cs(r.get());
-        *out = r.release();
+        synthesize_withdraw(r.cs, w->L, w->T, ZkScalar::from_bytes(commitment), w->height, state, aux, w->accounts->root(), trs, w->threads, dd);
         return BZK_OK;
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    } catch (const std::exception&) {
-        return BZK_E_INTERNAL;
-    }
+    });
 }
 
 // `MpnCircuit::empty` for the other two circuits (src/mpn/circuits/test.rs:151-229): kind 0 = deposit, 1 = withdraw
@@ -1768,29 +1657,19 @@ int32_t bzk_mpn_circuit_empty(int32_t kind, uint32_t log4_tree, uint32_t log4_to
         log4_token_tree == 0 || log4_token_tree > 8 || kind < 0 || kind > 1)
         return BZK_E_ARG;
     *out = nullptr;
-    try {
-        std::unique_ptr<bzk_r1cs> r(new bzk_r1cs(record_matrices != 0));
-        LcModeGuard guard(record_matrices != 0);
-        r->cs.self_check = record_matrices != 0;
+    return make_instance(record_matrices ? Synth::Matrices : Synth::Witness, out, [&](bzk_r1cs& r, DeferData*) -> int32_t {
         const size_t n = (size_t)1 << (2 * log4_batch);
         if (kind == 0) {
             std::vector<DepositTransition> trs(n, DepositTransition::null((int)log4_tree, (int)log4_token_tree));
-            synthesize_deposit(r->cs, (int)log4_tree, (int)log4_token_tree, ZkScalar::from_bytes(commitment), height,
+            synthesize_deposit(r.cs, (int)log4_tree, (int)log4_token_tree, ZkScalar::from_bytes(commitment), height,
                                ZkScalar::from_bytes(state), ZkScalar::from_bytes(aux_data), ZkScalar::from_bytes(next_state), trs);
         } else {
             std::vector<WithdrawTransition> trs(n, WithdrawTransition::null((int)log4_tree, (int)log4_token_tree));
-            synthesize_withdraw(r->cs, (int)log4_tree, (int)log4_token_tree, ZkScalar::from_bytes(commitment), height,
+            synthesize_withdraw(r.cs, (int)log4_tree, (int)log4_token_tree, ZkScalar::from_bytes(commitment), height,
                                 ZkScalar::from_bytes(state), ZkScalar::from_bytes(aux_data), ZkScalar::from_bytes(next_state), trs);
         }
-        if (r->cs.check_failed_at >= 0) return BZK_E_INTERNAL;
-        finish_r1cs(r.get());
-        *out = r.release();
         return BZK_OK;
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    } catch (const std::exception&) {
-        return BZK_E_INTERNAL;
-    }
+    });
 }
 
 // info[0..8) = n_in, n_aux, n_constraints, nnz(A), nnz(B), nnz(C), first unsatisfied constraint + 1 (0 = ok),
@@ -2135,47 +2014,31 @@ int32_t bzk_mpn_work_synthesize(const bzk_mpn_work* h, const uint8_t prover_pub[
     // 0 witness only, 1 with the CSR matrices, BZK_SYNTH_DEFER witness only with deferred values, BZK_SYNTH_DEFER_SIG the same with the signature
     // gadget deferred as well: anything else is a caller's mistake, not "non-zero = matrices"
     if (record_matrices != 0 && record_matrices != 1 && record_matrices != (int32_t)BZK_SYNTH_DEFER && record_matrices != (int32_t)BZK_SYNTH_DEFER_SIG) return BZK_E_ARG;
-    try {
+    const Synth mode = record_matrices == 1 ? Synth::Matrices : record_matrices == (int32_t)BZK_SYNTH_DEFER_SIG ? Synth::DeferSig :
+                       record_matrices == (int32_t)BZK_SYNTH_DEFER ? Synth::Defer : Synth::Witness;
+    return make_instance(mode, out, [&](bzk_r1cs& r, DeferData* dd) -> int32_t {
         const MpnWork& w = h->w;
         const int L = w.config.log4_tree, T = w.config.log4_token_tree, B = w.log4_batch();
         const size_t cap = (size_t)1 << (2 * B);
         const int nt = threads > 0 ? threads : host_default_threads();
         const ZkScalar commitment = mpn_work_commitment(prover_pub, w.reward);
-        const bool rec = record_matrices == 1, sig = record_matrices == BZK_SYNTH_DEFER_SIG, defer = record_matrices == BZK_SYNTH_DEFER || sig;  // 0: witness only
-        std::unique_ptr<bzk_r1cs> r(new bzk_r1cs(rec));
-        LcModeGuard guard(rec);
-        r->cs.self_check = rec;
         if (w.kind == 2) {
             std::vector<UpdateTransition> trs = w.updates;
             while (trs.size() < cap) trs.push_back(UpdateTransition::null(L, T));
             const ZkScalar ft = fee_token ? ZkScalar::from_bytes(fee_token) : ZkScalar::one();
-            if (defer) { r->defer.reset(new DeferData()); r->defer->sig = sig; }
-            synthesize_update(r->cs, L, T, commitment, w.height, w.state, w.aux_data, w.next_state, ft, trs, nt, r->defer.get());
-            if (r->defer && !r->defer->prog) r->defer.reset();
+            synthesize_update(r.cs, L, T, commitment, w.height, w.state, w.aux_data, w.next_state, ft, trs, nt, dd);
         } else if (w.kind == 0) {
             std::vector<DepositTransition> trs = w.deposits;
             while (trs.size() < cap) trs.push_back(DepositTransition::null(L, T));
-            if (defer) { r->defer.reset(new DeferData()); r->defer->sig = sig; }
-            synthesize_deposit(r->cs, L, T, commitment, w.height, w.state, w.aux_data, w.next_state, trs, nt, r->defer.get());
-            if (r->defer && !r->defer->prog) r->defer.reset();
+            synthesize_deposit(r.cs, L, T, commitment, w.height, w.state, w.aux_data, w.next_state, trs, nt, dd);
         } else {
             std::vector<WithdrawTransition> trs = w.withdraws;
             while (trs.size() < cap) trs.push_back(WithdrawTransition::null(L, T));
-            if (defer) { r->defer.reset(new DeferData()); r->defer->sig = sig; }
-            synthesize_withdraw(r->cs, L, T, commitment, w.height, w.state, w.aux_data, w.next_state, trs, nt, r->defer.get());
-            if (r->defer && !r->defer->prog) r->defer.reset();
+            synthesize_withdraw(r.cs, L, T, commitment, w.height, w.state, w.aux_data, w.next_state, trs, nt, dd);
         }
-        if (r->cs.check_failed_at >= 0) return BZK_E_INTERNAL;
-        r->accepted = w.n_transitions();
-        finish_r1cs(r.get());
-        *out = r.release();
+        r.accepted = w.n_transitions();
         return BZK_OK;
-    } catch (const std::bad_alloc&) {
-        return BZK_E_ALLOC;
-    } catch (const std::exception& e) {
-        g_work_error = e.what();
-        return BZK_E_INTERNAL;
-    }
+    }, &g_work_error);
 }
 
 // Validator side: one work of `prepare_works` (src/mpn/mod.rs:352-414) from the transactions queued in the world: runs the
@@ -2211,18 +2074,15 @@ int32_t bzk_mpn_make_work(bzk_mpn* w, int32_t kind, const bzk_mpn_work_config* c
         uint64_t rejected = 0;
         if (kind == 2) {
             uint64_t fee_sum = 0;
-            if (w->dev) { const int32_t ds = build_transitions_dev(*w, c.log4_update_batch, ZkScalar::one(), o.updates, fee_sum, rejected); if (ds != BZK_OK) return ds; }
-            else build_transitions(*w, c.log4_update_batch, ZkScalar::one(), o.updates, fee_sum, rejected);
+            if (const int32_t ds = build_updates(*w, c.log4_update_batch, ZkScalar::one(), o.updates, fee_sum, rejected); ds != BZK_OK) return ds;
             o.aux_data = h2(ZkScalar::one(), ZkScalar::from_u64(fee_sum));
         } else if (kind == 0) {
-            if (w->dev) { const int32_t ds = build_deposits_dev(*w, c.log4_deposit_batch, o.deposits, rejected); if (ds != BZK_OK) return ds; }
-            else build_deposits(*w, c.log4_deposit_batch, o.deposits, rejected);
+            if (const int32_t ds = build_deposits(*w, c.log4_deposit_batch, o.deposits, rejected); ds != BZK_OK) return ds;
             o.aux_data = deposit_aux(o.deposits, c.log4_deposit_batch);
         } else {
             for (auto& tx : w->withdraw_queue)
                 if (tx.payment.empty()) return BZK_E_ARG;  // queued with an opaque fingerprint: no wire form
-            if (w->dev) { const int32_t ds = build_withdraws_dev(*w, c.log4_withdraw_batch, o.withdraws, rejected); if (ds != BZK_OK) return ds; }
-            else build_withdraws(*w, c.log4_withdraw_batch, o.withdraws, rejected);
+            if (const int32_t ds = build_withdraws(*w, c.log4_withdraw_batch, o.withdraws, rejected); ds != BZK_OK) return ds;
             o.aux_data = withdraw_aux(o.withdraws, c.log4_withdraw_batch);
         }
         o.next_state = w->accounts->root();

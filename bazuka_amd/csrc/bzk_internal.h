@@ -79,6 +79,8 @@ struct bzk_ctx {
     // is_child: a lane or a window-range child - its calls never take a set's table; msm_split_env: some BZK_MSM_SPLIT* variable was set when the context was created
     int msm_bases_table = -1, msm_bases_table_c = 0;
     bool is_child = false, msm_split_env = false;
+    // env BZK_MSM_BITSUM_PLAIN=0: a table call's one bucket set leaves its terms in the paired layout of every other caller (msm_impl.cuh msm_bitsum_quad_kernel; A/B runs, tests)
+    bool msm_bitsum_plain = true;
     void* split_terms = nullptr;
     size_t split_terms_bytes = 0;
     void* split_conv = nullptr;  // internal form of the raw bases of a split call (msm_entry_dev), grow-only; released by bzk_ctx_trim

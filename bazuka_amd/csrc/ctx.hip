@@ -288,6 +288,7 @@ int32_t bzk_ctx_create(int32_t device_id, void* stream, bzk_ctx** out) {
         if (v >= 11 && v <= 20) ctx->msm_bases_table_c = v;
         else fprintf(stderr, "[bzk] BZK_MSM_BASES_TABLE_C=%s is outside 11 .. 20: the table keeps its 20-bit window\n", e);
     }
+    if (const char* e = getenv("BZK_MSM_BITSUM_PLAIN")) ctx->msm_bitsum_plain = atoi(e) != 0;
     ctx->msm_split_env = getenv("BZK_MSM_SPLIT") || getenv("BZK_MSM_SPLIT_MIN_LOG") || getenv("BZK_MSM_SPLIT_PRIO") || getenv("BZK_MSM_SPLIT_CUTS");
     if (const char* e = getenv("BZK_MSM_SPLIT")) ctx->msm_split = atoi(e);
     if (const char* e = getenv("BZK_MSM_SPLIT_MIN_LOG")) ctx->msm_split_min_log = atoi(e);

@@ -1516,22 +1516,30 @@ __global__ void __launch_bounds__(THREADS, 2) msm_rowcol_quad_kernel(const G1X28
     if (valid && slot % seg == 0) (col_pass ? cols : rows)[(size_t)set * (col_pass ? L : H) + out_idx] = sh[slot];
 }
 // Terms of a set.  Bit k of the bucket index contributes S_k = (k < lbits: the column sums with bit k of l set; else: the row sums with bit k - lbits of h
-// set); two ADJACENT bits share a workgroup of 2 x THREADS lanes (THREADS = 128: the two trees' 2 x 128 points are the 56 KiB of LDS a workgroup may declare) - each half runs the tree of one bit, then one quad forms D_j = S_2j + 2 S_(2j+1) (a
-// doubling and an addition: ~12 us) - so the host's Horner adds half as many points (an XYZZ addition costs a host core 0.5 us: 272 of them were 0.14 of
-// the step's 3.5 ms).  Terms of a set, standard-limb XYZZ at terms[set * n_terms + t]:  t < n_pairs: D_t (bit position 2 t);  t = n_pairs: the plain sum
-// of the set (every row sum; position 0).  n_pairs = ceil((c - 1) / 2).
+// set).  Two layouts of the terms a set leaves (standard-limb XYZZ at terms[set * n_terms + t]), one kernel templated on them:
+//   PAIRED  n_terms = n_pairs + 1, n_pairs = ceil((c - 1) / 2).  Two ADJACENT bits share a workgroup of 2 x THREADS lanes (THREADS = 128: the two trees' 2 x 128
+//           points are the 56 KiB of LDS a workgroup may declare) - each half runs the tree of one bit, then one quad forms D_j = S_2j + 2 S_(2j+1) (a doubling and
+//           an addition: ~12 us) - so the host's Horner adds half as many points (an XYZZ addition costs a host core 0.5 us: 272 of them were 0.14 of the step's
+//           3.5 ms with 16 sets).  t < n_pairs: D_t (bit position 2 t);  t = n_pairs: the plain sum of the set (every row sum; position 0).  What every caller that
+//           reduces several sets, exchanges its terms or stores them takes.
+//   PLAIN   n_terms = n_bits + 1 = c.  One bit per workgroup, ONE tree of 2 x THREADS lanes over the same LDS, no doubling and no pair addition.  t < n_bits: S_t
+//           (bit position t);  t = n_bits: the plain sum (position 0).  For a call that reduces exactly ONE set and hands its terms straight to this host's Horner
+//           (a full window table, msm_run): there the pairing saves the host c / 2 additions (~5 us) and costs the device its pair stage and, at c = 20, two of
+//           the three serial lone-lane additions a 128-lane tree needs in front of 512 leaves (a 256-lane tree needs one).
 __host__ __device__ inline uint32_t msm_bitsum_pairs(const RowColPlan& P) { return (P.lbits + P.hbits + 1u) / 2u; }
-template <int THREADS>
+__host__ __device__ inline uint32_t msm_bitsum_terms(int c, bool plain) { return plain ? (uint32_t)c : (uint32_t)c / 2u + 1u; }  // per bucket set
+template <int THREADS, bool PLAIN>
 __global__ void __launch_bounds__(2 * THREADS) msm_bitsum_quad_kernel(const G1X28* __restrict__ rows, const G1X28* __restrict__ cols, RowColPlan P,
                                                                       XyzzT<FpOps>* __restrict__ terms) {
 #if defined(__HIP_DEVICE_COMPILE__)
     __shared__ G1X28 sh[2 * THREADS];
-    const uint32_t n_bits = P.lbits + P.hbits, n_pairs = msm_bitsum_pairs(P), n_terms = n_pairs + 1u;
+    constexpr uint32_t TREE = PLAIN ? 2u * THREADS : (uint32_t)THREADS;  // lanes, and LDS slots, of one tree
+    const uint32_t n_bits = P.lbits + P.hbits, n_digit = PLAIN ? n_bits : msm_bitsum_pairs(P), n_terms = n_digit + 1u;
     const uint32_t set = blockIdx.x / n_terms, t = blockIdx.x % n_terms;
-    const uint32_t half = threadIdx.x / THREADS, tid = threadIdx.x % THREADS;  // half 0: bit 2 t (or the plain sum), half 1: bit 2 t + 1
-    const bool total = t == n_pairs;
-    const uint32_t k = 2u * t + half;
-    const bool have = total ? half == 0 : k < n_bits;  // an odd bit count leaves the last pair's upper half empty
+    const uint32_t half = threadIdx.x / TREE, tid = threadIdx.x % TREE;  // PAIRED: half 0: bit 2 t (or the plain sum), half 1: bit 2 t + 1;  PLAIN: one half, bit t
+    const bool total = t == n_digit;
+    const uint32_t k = PLAIN ? t : 2u * t + half;
+    const bool have = total ? half == 0 : k < n_bits;  // PAIRED: an odd bit count leaves the last pair's upper half empty
     const bool from_cols = !total && k < P.lbits;
     const uint32_t n_src = 1u << (from_cols ? P.lbits : P.hbits), bit = total ? 0u : (from_cols ? k : k - P.lbits);
     const G1X28* src = (from_cols ? cols : rows) + (size_t)set * n_src;
@@ -1540,19 +1548,20 @@ __global__ void __launch_bounds__(2 * THREADS) msm_bitsum_quad_kernel(const G1X2
     G1X28 acc = g1x28::identity();
     if (tid < n_leaves) {
         acc = src[leaf_index(tid)];
-        for (uint32_t j = tid + THREADS; j < n_leaves; j += THREADS) {
+        for (uint32_t j = tid + TREE; j < n_leaves; j += TREE) {
             const G1X28 q = src[leaf_index(j)];
             g1x28::add_full(acc, q);
         }
     }
-    G1X28* const my = sh + half * THREADS;
+    G1X28* const my = sh + half * TREE;
     my[tid] = acc;
     __syncthreads();
-    // both halves walk the same number of levels (the barriers are the workgroup's); a half whose tree is narrower idles through the wide levels
-    const uint32_t widest = 1u << (P.lbits > P.hbits ? P.lbits : P.hbits);
+    // PAIRED: both halves walk the same number of levels (the barriers are the workgroup's); a half whose tree is narrower idles through the wide levels.
+    // PLAIN: the workgroup's one tree starts at its own leaf count
+    const uint32_t widest = PLAIN ? n_leaves : 1u << (P.lbits > P.hbits ? P.lbits : P.hbits);
     int levels_from = 1;
-    while (levels_from < THREADS && (uint32_t)levels_from < widest) levels_from <<= 1;
-    const int quad = (int)(tid >> 2), n_quads = THREADS / 4;
+    while (levels_from < (int)TREE && (uint32_t)levels_from < widest) levels_from <<= 1;
+    const int quad = (int)(tid >> 2), n_quads = (int)TREE / 4;
     for (int s = levels_from / 2; s > 0; s >>= 1) {  // (slots beyond a half's leaves hold identities: their additions return at once)
         for (int p = quad; p < s; p += n_quads) {
             const G1X28 r = g1_add_quad(my[p], my[p + s]);
@@ -1560,9 +1569,11 @@ __global__ void __launch_bounds__(2 * THREADS) msm_bitsum_quad_kernel(const G1X2
         }
         __syncthreads();
     }
-    if (threadIdx.x < 4) {  // one quad: D = S_lo + 2 S_hi
+    if (threadIdx.x < 4) {
         G1X28 r = sh[0];
-        if (!total && 2u * t + 1u < n_bits) r = g1_add_quad(r, g1_dbl_quad(sh[THREADS]));
+        if constexpr (!PLAIN) {  // one quad: D = S_lo + 2 S_hi
+            if (!total && 2u * t + 1u < n_bits) r = g1_add_quad(r, g1_dbl_quad(sh[THREADS]));
+        }
         if (threadIdx.x == 0) terms[(size_t)set * n_terms + t] = g1x28::to_std(r);
     }
 #endif
@@ -2079,7 +2090,7 @@ static bool msm_bitsum_applies(int c) {
     return on && !C::PARK_REDUCE && c >= 11 && c <= 21;
 }
 template <class C>
-static int msm_terms_per_set(int c) { return msm_bitsum_applies<C>(c) ? c / 2 + 1 : 0; }
+static int msm_terms_per_set(int c) { return msm_bitsum_applies<C>(c) ? (int)msm_bitsum_terms(c, false) : 0; }  // what a caller RECEIVES: always the paired layout
 
 // Horner over window sums on the host: result = sum_k 2^(c (w0 + k)) S[k].  c * (count + w0) doublings that nothing can overlap
 // with - they run on the 6 x 64-bit host field of host_fp64.h (round 3: 0.63 -> 0.45 us per doubling, same values).
@@ -2095,22 +2106,26 @@ static XyzzT<F> msm_horner_host(const XyzzT<F>* S, int count, int c, int w0) {
     return from_host_fast<F>(acc);
 }
 
-// Horner over the TERMS of the multiplication-free reduction (section 6b): bucket set k (k < count) contributes its n_pairs digit terms D_j = S_2j + 2 S_(2j+1)
-// at bit positions c (w0 + k) + 2 j and its last term - the plain sum of the set - at position c (w0 + k).  The same c (count + w0) doublings as
-// msm_horner_host, count * (n_pairs + 1) additions.
+// Horner over the TERMS of the multiplication-free reduction (section 6b), in either layout of msm_bitsum_quad_kernel.  Paired: bucket set k (k < count)
+// contributes its n_pairs digit terms D_j = S_2j + 2 S_(2j+1) at bit positions c (w0 + k) + 2 j;  plain: its c - 1 bit sums S_j at positions c (w0 + k) + j.
+// Either way the set's last term - its plain sum - joins at position c (w0 + k).  The same c (count + w0) doublings as msm_horner_host, count * n_terms additions.
+// One set's share of it: c doublings of acc with the terms t[] added at their positions
 template <class F>
-static XyzzT<F> msm_horner_terms_host(const XyzzT<F>* T, int count, int c, int w0) {
+static void msm_horner_terms_set(XyzzT<typename HostFast<F>::Ops>& acc, const XyzzT<F>* t, int c, bool plain) {
     typedef typename HostFast<F>::Ops H;
-    const int n_pairs = c / 2, n_terms = n_pairs + 1;  // ceil((c - 1) / 2)
-    XyzzT<H> acc = xyzz_identity<H>();
-    for (int k = count - 1; k >= 0; --k) {
-        const XyzzT<F>* t = T + (size_t)k * n_terms;
-        for (int bit = c - 1; bit >= 0; --bit) {
-            acc = xyzz_dbl<H>(acc);
-            if ((bit & 1) == 0 && bit / 2 < n_pairs) xyzz_add<H>(acc, to_host_fast<F>(t[bit / 2]));
-            if (bit == 0) xyzz_add<H>(acc, to_host_fast<F>(t[n_pairs]));
-        }
+    const int n_digit = plain ? c - 1 : c / 2, step = plain ? 1 : 2;  // paired: ceil((c - 1) / 2) terms, at the even positions
+    for (int bit = c - 1; bit >= 0; --bit) {
+        acc = xyzz_dbl<H>(acc);
+        if (bit % step == 0 && bit / step < n_digit) xyzz_add<H>(acc, to_host_fast<F>(t[bit / step]));
+        if (bit == 0) xyzz_add<H>(acc, to_host_fast<F>(t[n_digit]));
     }
+}
+template <class F>
+static XyzzT<F> msm_horner_terms_host(const XyzzT<F>* T, int count, int c, int w0, bool plain = false) {
+    typedef typename HostFast<F>::Ops H;
+    const size_t n_terms = msm_bitsum_terms(c, plain);
+    XyzzT<H> acc = xyzz_identity<H>();
+    for (int k = count - 1; k >= 0; --k) msm_horner_terms_set<F>(acc, T + (size_t)k * n_terms, c, plain);
     for (int d = 0; d < c * w0; ++d) acc = xyzz_dbl<H>(acc);
     return from_host_fast<F>(acc);
 }
@@ -2192,7 +2207,11 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
     const bool bitsum = msm_bitsum_applies<C>(c) && !folded;
     const RowColPlan rc_plan = msm_rowcol_plan(c - 1, 256);
     const size_t rc_per_set = ((size_t)1 << rc_plan.lbits) + ((size_t)1 << rc_plan.hbits);
-    if (wout) { wout->c = c; wout->w_total = w_total; wout->w_begin = w_begin; wout->w_end = w_end; wout->single = table && !folded; wout->terms_per_set = bitsum ? c / 2 + 1 : 0; }
+    // the layout of a set's terms (msm_bitsum_quad_kernel): plain where the call reduces exactly one set - a full table's - and its terms go straight to this
+    // host's Horner; every caller that receives terms (wout: ranks, window ranges) or reduces several sets keeps the paired one.  env BZK_MSM_BITSUM_PLAIN=0, read
+    // when the context is created: paired here too (A/B)
+    const bool plain_terms = bitsum && table && !folded && !wout && ctx->msm_bitsum_plain;
+    if (wout) { wout->c = c; wout->w_total = w_total; wout->w_begin = w_begin; wout->w_end = w_end; wout->single = table && !folded; wout->terms_per_set = bitsum ? (int)msm_bitsum_terms(c, false) : 0; }
 
     // windows are processed in groups so that one group's pair list stays below 2^30 entries
     int group = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)(w_end - w_begin), ((uint64_t)1 << 30) / n));
@@ -2255,7 +2274,7 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
                                               dedup ? (uint64_t)m_max + n / seg_dd + 1 : 0);
     const size_t wide_cap = (size_t)t_cap / 32 + 2 * MSM_FOLD_WIDE_POS + 2;  // slot(i) + chunks(i) <= t / 64 + i + t / 64 + 1 (msm_fold_wide_slot)
     const size_t n_sets_max = (table && !folded) ? 1 : (size_t)group;
-    const size_t n_terms = (size_t)c / 2 + 1;  // per bucket set: ceil((c - 1) / 2) digit terms + the plain sum (msm_bitsum_quad_kernel)
+    const size_t n_terms = msm_bitsum_terms(c, plain_terms);  // per bucket set: its digit terms (paired: ceil((c - 1) / 2), plain: c - 1) + the plain sum
     // every buffer of the call, declared once; what a configuration does not take stays null
     const bool wiv = !wiv_off && !table && group <= 16 && (uint64_t)n + m_max < ((uint64_t)1 << 27);
     // partition front (section 3d) or the radix sort: decided in one place for every group of this call
@@ -2458,8 +2477,13 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
                 // halves of 128 lanes: with 256-lane halves (112 KiB of static LDS - the runtime takes it) a workgroup saves a tree level and loses more to its
                 // eight waves sharing a CU: 0.166 - 0.170 against 0.150 - 0.153 ms, same box, alternating (profiles/r06_run11_bitsum_wide_negative.txt)
                 StdPt* const terms_dst = wout ? (StdPt*)wout->d_win + ((table && !folded) ? 0 : (size_t)(wb - w_begin) * n_terms) : terms_out;
-                BZK_LAUNCH(ctx, "msm_bitsum", (msm_bitsum_quad_kernel<128>), dim3((unsigned)n_red_win * (unsigned)n_terms), dim3(256), 0, (const G1X28*)rows,
-                           (const G1X28*)cols, rc_plan, (XyzzT<FpOps>*)terms_dst);
+                if (plain_terms) {  // one set, one bit per workgroup, one 256-lane tree
+                    BZK_LAUNCH(ctx, "msm_bitsum", (msm_bitsum_quad_kernel<128, true>), dim3((unsigned)n_red_win * (unsigned)n_terms), dim3(256), 0, (const G1X28*)rows,
+                               (const G1X28*)cols, rc_plan, (XyzzT<FpOps>*)terms_dst);
+                } else {
+                    BZK_LAUNCH(ctx, "msm_bitsum", (msm_bitsum_quad_kernel<128, false>), dim3((unsigned)n_red_win * (unsigned)n_terms), dim3(256), 0, (const G1X28*)rows,
+                               (const G1X28*)cols, rc_plan, (XyzzT<FpOps>*)terms_dst);
+                }
                 if (wout) {  // the terms stay on the device, in stream order; the caller reads them back (or exchanges them) and combines
                     if (table && !folded) return BZK_OK;
                     continue;
@@ -2467,7 +2491,7 @@ static int32_t msm_run(bzk_ctx* ctx, const void* bases_raw, const void* scalars,
                 BZK_HIP(ctx, hipMemcpyAsync(ctx->pinned, terms_out, (size_t)n_red_win * n_terms * sizeof(StdPt), hipMemcpyDeviceToHost, ctx->stream));
                 BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 if (table && !folded) {  // one bucket set fed by every level of the table: its c terms are the whole result
-                    result = msm_horner_terms_host<F>((const StdPt*)ctx->pinned, 1, c, 0);
+                    result = msm_horner_terms_host<F>((const StdPt*)ctx->pinned, 1, c, 0, plain_terms);
                     return BZK_OK;
                 }
                 memcpy(&wsum[(size_t)(wb - w_begin) * n_terms], ctx->pinned, (size_t)wc * n_terms * sizeof(StdPt));
@@ -2603,17 +2627,9 @@ static int msm_split_parts(const bzk_ctx* ctx, uint64_t n, uint32_t flags, const
 }
 // continues a Horner over terms (msm_horner_terms_host without its trailing doublings): acc <- acc 2^(c count) + sum_k 2^(c k) (terms of set k)
 template <class F>
-static void msm_horner_terms_continue(XyzzT<typename HostFast<F>::Ops>& acc, const XyzzT<F>* T, int count, int c) {
-    typedef typename HostFast<F>::Ops H;
-    const int n_pairs = c / 2, n_terms = n_pairs + 1;
-    for (int k = count - 1; k >= 0; --k) {
-        const XyzzT<F>* t = T + (size_t)k * n_terms;
-        for (int bit = c - 1; bit >= 0; --bit) {
-            acc = xyzz_dbl<H>(acc);
-            if ((bit & 1) == 0 && bit / 2 < n_pairs) xyzz_add<H>(acc, to_host_fast<F>(t[bit / 2]));
-            if (bit == 0) xyzz_add<H>(acc, to_host_fast<F>(t[n_pairs]));
-        }
-    }
+static void msm_horner_terms_continue(XyzzT<typename HostFast<F>::Ops>& acc, const XyzzT<F>* T, int count, int c, bool plain = false) {
+    const size_t n_terms = msm_bitsum_terms(c, plain);
+    for (int k = count - 1; k >= 0; --k) msm_horner_terms_set<F>(acc, T + (size_t)k * n_terms, c, plain);
 }
 template <class C>
 static int32_t msm_run_split(bzk_ctx* ctx, const void* scalars, uint64_t n, uint32_t flags, XyzzT<typename C::HostF>& result, const MsmBases* prep, int parts) {

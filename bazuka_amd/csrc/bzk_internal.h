@@ -168,6 +168,39 @@ void g16v_declare(WsLayout& ws, G16vBufs& b, uint32_t n_inputs, uint64_t n, size
 int32_t g16v_enqueue(bzk_ctx* ctx, const G16vBufs& b, const hp::KeyHost& K, const hp::KeyUpload& up, const uint8_t* inputs_dev,
                      const uint8_t* proofs_dev, uint64_t n, uint8_t* ok_dev, bool sync);
 void g16v_host_run(const hp::KeyHost& K, const uint8_t* inputs, const uint8_t* proofs, uint64_t n, uint8_t* ok);
+// verify_keys.hip: the same verifier over GROUPS of proofs, a key per group, in one set of launches per round of 2^16 lanes (every group padded to
+// whole blocks of 64).  A group on the device path has a valid prepared key of at most 16 inputs and count > 0; K, up and count are what
+// g16k_declare reads, the three pointers are set before g16k_enqueue: device pointers to the group's rows - or, `staged`, HOST pointers to its
+// inputs and proofs, which go up round by round through staging buffers the declaration adds (ok stays a device pointer).  g16k_declare cuts the
+// rounds and adds the verifier's buffers, the keys' uploads, the segment records and the block table to the CALLER's layout; after the caller's
+// commit g16k_enqueue runs on it in stream order (`up`, the groups and `b` must outlive the work; sync: wait for it).  g16k_host_run: the same
+// per-proof functions on host threads, all groups' rows in one task loop (host pointers; every verdict of an invalid key 0; `up` is not read).
+struct G16kGroup {
+    const hp::KeyHost* K = nullptr;
+    const hp::KeyUpload* up = nullptr;
+    uint64_t count = 0;
+    const uint8_t *inputs = nullptr, *proofs = nullptr;
+    uint8_t* ok = nullptr;
+};
+struct G16kSeg {   // the rows [first, first + rows) of a group: its part of one round, from block `block0` of the round on
+    uint32_t group, rows;
+    uint64_t first;
+    uint32_t block0;
+    size_t in_at;  // staged: where its inputs lie in the round's staging buffer
+};
+struct G16kBufs {
+    uint32_t *slab = nullptr, *flags = nullptr, *sc = nullptr;
+    uint8_t *dkeys = nullptr, *dsegs = nullptr, *dblocks = nullptr, *din = nullptr, *dpr = nullptr;
+    uint32_t stride = 0;                          // lanes of the largest round
+    uint64_t n_blocks = 0;
+    std::vector<size_t> key_at;                   // per group: its key's upload in dkeys
+    std::vector<G16kSeg> segs;                    // in lane order
+    std::vector<uint32_t> round_at, round_blocks; // round r: segments [round_at[r], round_at[r + 1]), round_blocks[r] blocks
+    std::vector<uint8_t> hsegs, hblocks;          // the host images of dsegs and dblocks (g16k_enqueue)
+};
+void g16k_declare(WsLayout& ws, G16kBufs& b, const std::vector<G16kGroup>& groups, bool staged);
+int32_t g16k_enqueue(bzk_ctx* ctx, G16kBufs& b, const std::vector<G16kGroup>& groups, bool staged, bool sync);
+void g16k_host_run(const std::vector<G16kGroup>& groups);
 // subgroup.hip: the first of n finite raw points (G1 96 B, G2 192 B) whose subgroup verdict is not 1: *idx (n: none) and *code.  ctx = NULL: host threads
 // on host records; on_device: the records already are in device memory.  sg_host_one: the verdict of one record on the host
 int32_t sg_first_bad(bzk_ctx* ctx, const char* who, bool g2, const uint8_t* pts, bool on_device, uint64_t n, uint64_t* idx, uint8_t* code);

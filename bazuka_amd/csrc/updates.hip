@@ -11,7 +11,7 @@
 //   upd_tree_level     one launch per level over ALL updates of the round; only parents with a populated child are computed
 //   upd_inputs         one lane per update    commitment, aux (root / default / H2 of a FunctionCall), SIGS and ROUTE bits, the five inputs and the
 //                                             proof into the update's key group
-// Stage 2, per key group, one after another: verify.hip's three kernels over the group's inputs and proofs, in rounds of 2^16 proofs.
+// Stage 2, all key groups side by side: verify_keys.hip's three kernels over the groups' inputs and proofs, one set of launches per round of 2^16 lanes.
 // Stage 3: upd_verdict scatters the group verdicts back to update order and ORs in the bits.
 // Aux values, commitments, bits and the groups' arrays of all n updates stay on the device between rounds; everything is one WsLayout.
 #include <memory>
@@ -216,16 +216,13 @@ void make_plan(const bzk_contract_desc& c, UpdParsed& P, const uint64_t* count, 
         }
     }
 }
-void prepare_keys(Plan& plan, bool device, size_t& key_bytes) {
-    key_bytes = 0;
-    for (Group& g : plan.groups) {
-        if (!g.count) continue;
+void prepare_keys(Plan& plan, bool device) {   // the groups' keys side by side on the host threads
+    host_for_each(plan.groups.size(), host_default_threads(), [&](uint64_t i) {
+        Group& g = plan.groups[i];
+        if (!g.count) return;
         hp::key_prepare(g.fn->vk, g.fn->vk_len, 5, g.key);   // check_proof's five inputs; a key of another shape verifies nothing
-        if (g.key.valid && device) {
-            g.up.reset(new hp::KeyUpload(g.key));
-            key_bytes = std::max(key_bytes, g.up->bytes.size());
-        }
-    }
+        if (g.key.valid && device) g.up.reset(new hp::KeyUpload(g.key));
+    });
 }
 
 // ---- the same plan on host threads
@@ -270,10 +267,12 @@ int32_t run_host(int threads, const UpdParsed& P, const Plan& plan, const uint8_
                                           : (uint8_t)((upd::sigs_all(u, sig.data() + (u.pay0 - pay_base)) ? BZK_UPD_SIGS : 0) | (u.route ? BZK_UPD_ROUTE : 0));
         });
     }
+    std::vector<G16kGroup> vg;   // every group's rows in one task loop
     for (const Group& g : plan.groups)
         if (g.count)
-            g16v_host_run(g.key, (const uint8_t*)(inputs.data() + 5 * g.first), proofs.data() + upd::PROOF_BYTES * g.first, g.count,
-                          verdict.data() + g.first);
+            vg.push_back({&g.key, nullptr, g.count, (const uint8_t*)(inputs.data() + 5 * g.first), proofs.data() + upd::PROOF_BYTES * g.first,
+                          verdict.data() + g.first});
+    g16k_host_run(vg);
     for (uint64_t i = 0; i < n; ++i) ok[i] = (uint8_t)(bits[i] | ((plan.slot[i] != upd::NO_SLOT && verdict[plan.slot[i]]) ? BZK_UPD_PROOF : 0));
     if (aux_out) memcpy(aux_out, aux.data(), n * 32);
     if (commit_out) memcpy(commit_out, commit.data(), n * 32);
@@ -281,11 +280,10 @@ int32_t run_host(int threads, const UpdParsed& P, const Plan& plan, const uint8_
 }
 
 // ---- and on the device
-int32_t run_device(bzk_ctx* ctx, const UpdParsed& P, const Plan& plan, size_t key_bytes, const uint8_t state0[32], uint8_t* ok, uint8_t* aux_out,
-                   uint8_t* commit_out) {
+int32_t run_device(bzk_ctx* ctx, const UpdParsed& P, const Plan& plan, const uint8_t state0[32], uint8_t* ok, uint8_t* aux_out, uint8_t* commit_out) {
     (void)hipSetDevice(ctx->device);
     const uint64_t n = P.rec.size();
-    uint64_t cap_u = 1, cap_p = 1, cap_bytes = 1, cap_rows = 1, cap_nodes = 1, max_group = 0;
+    uint64_t cap_u = 1, cap_p = 1, cap_bytes = 1, cap_rows = 1, cap_nodes = 1;
     for (const Round& R : plan.rounds) {
         cap_u = std::max<uint64_t>(cap_u, R.mu());
         cap_p = std::max<uint64_t>(cap_p, R.row(0)[R.mu()]);
@@ -293,21 +291,31 @@ int32_t run_device(bzk_ctx* ctx, const UpdParsed& P, const Plan& plan, size_t ke
         cap_rows = std::max<uint64_t>(cap_rows, R.rows.size());
         cap_nodes = std::max<uint64_t>(cap_nodes, R.n_nodes);
     }
+    std::vector<G16kGroup> vg;   // the groups the verifier runs: a group whose key is refused keeps verdict 0
     for (const Group& g : plan.groups)
-        if (g.key.valid) max_group = std::max(max_group, g.count);
+        if (g.count && g.key.valid) vg.push_back({&g.key, g.up.get(), g.count, nullptr, nullptr, nullptr});
     WsLayout ws("bzk_contract_updates_check");
     uint8_t *dbytes, *dsig, *dprev, *dbits, *dproofs, *dverdict, *dok;
     UpdRec* drec;
     PayRec* dpay;
     uint32_t *drows, *dslot;
     Fr *dnodes, *daux, *dcommit, *dinputs, *ddflt;
-    G16vBufs vb;
+    G16kBufs vb;
     ws.take(dbytes, cap_bytes + 8); ws.take(drec, cap_u); ws.take(dpay, cap_p); ws.take(drows, cap_rows); ws.take(dnodes, cap_nodes);
     ws.take(dsig, cap_p); ws.take(dprev, (size_t)32 * plan.rounds.size()); ws.take(ddflt, plan.dflt.size());
     ws.take(daux, n); ws.take(dcommit, n); ws.take(dbits, n); ws.take(dslot, n); ws.take(dok, n);
     ws.take(dinputs, (size_t)5 * plan.n_slots + 1); ws.take(dproofs, (size_t)upd::PROOF_BYTES * plan.n_slots + 1); ws.take(dverdict, plan.n_slots + 1);
-    if (max_group) g16v_declare(ws, vb, 5, max_group, key_bytes);
+    if (!vg.empty()) g16k_declare(ws, vb, vg, false);
     BZK_TRY(ws.commit(ctx));
+    {
+        size_t v = 0;
+        for (const Group& g : plan.groups)
+            if (g.count && g.key.valid) {
+                vg[v].inputs = (const uint8_t*)(dinputs + 5 * g.first);
+                vg[v].proofs = dproofs + upd::PROOF_BYTES * g.first;
+                vg[v++].ok = dverdict + g.first;
+            }
+    }
     upd::Consts c;
     const void* pc;
     BZK_TRY(poseidon_consts_dev_shared(ctx, 3, &pc, &c.rf3, &c.rp3));
@@ -360,10 +368,7 @@ int32_t run_device(bzk_ctx* ctx, const UpdParsed& P, const Plan& plan, size_t ke
                    (const uint8_t*)dbytes, base, (const UpdRec*)drec, upd0, mu, (const uint8_t*)prev, (const Fr*)dnodes, (const uint8_t*)dsig, pay_base, c,
                    daux, dcommit, dbits, dinputs, dproofs);
     }
-    for (const Group& g : plan.groups)  // one after another: the verifier's slab is shared
-        if (g.count && g.key.valid)
-            BZK_TRY(g16v_enqueue(ctx, vb, g.key, *g.up, (const uint8_t*)(dinputs + 5 * g.first), dproofs + upd::PROOF_BYTES * g.first, g.count,
-                                 dverdict + g.first, false));
+    BZK_TRY(g16k_enqueue(ctx, vb, vg, false, false));  // all live groups side by side: one set of launches per round
     BZK_LAUNCH(ctx, "upd_verdict", upd_verdict_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint32_t*)dslot, (const uint8_t*)dverdict,
                (const uint8_t*)dbits, n, dok);
     BZK_HIP(ctx, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
@@ -379,9 +384,8 @@ int32_t contract_updates_run(bzk_ctx* ctx, const bzk_contract_desc& c, UpdParsed
                              const uint8_t state0[32], uint8_t* ok, uint8_t* aux_out, uint8_t* commit_out) {
     Plan plan;
     make_plan(c, P, count, m, height0, plan);
-    size_t key_bytes = 0;
-    prepare_keys(plan, ctx != nullptr, key_bytes);
-    if (ctx) return run_device(ctx, P, plan, key_bytes, state0, ok, aux_out, commit_out);
+    prepare_keys(plan, ctx != nullptr);
+    if (ctx) return run_device(ctx, P, plan, state0, ok, aux_out, commit_out);
     return run_host(host_default_threads(), P, plan, state0, ok, aux_out, commit_out);
 }
 

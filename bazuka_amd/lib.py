@@ -1,6 +1,7 @@
 """ctypes binding of libbzk.so - mirrors include/bzk.h one to one."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -112,6 +113,8 @@ SIGNATURES = {
     "bzk_groth16_verify": (_i32, [_vp, _u64, _vp, _u32, _vp]),
     "bzk_groth16_verify_batch": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp]),
     "bzk_groth16_verify_batch_dev": (_i32, [_vp, _vp, _u64, _vp, _u32, _vp, _u64, _vp]),
+    "bzk_groth16_verify_batch_keys": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_groth16_verify_groups_dev": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bzk_g1_subgroup_check_batch": (_i32, [_vp, _vp, _vp, _u64, _vp]),
     "bzk_g1_subgroup_check_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp]),
     "bzk_g2_subgroup_check_batch": (_i32, [_vp, _vp, _vp, _u64, _vp]),
@@ -450,6 +453,11 @@ class Bzk:
         """`groth16_verify` for len(proofs) / 387 proofs of one key, one device lane per proof: inputs n x n_inputs x 32 B Montgomery; verdict bytes"""
         return _groth16_verify_batch(self.h, vk_bincode, inputs, n_inputs, proofs)
 
+    def groth16_verify_batch_keys(self, keys, key_of, inputs: bytes, proofs: bytes) -> bytes:
+        """`groth16_verify` for len(proofs) / 387 proofs of SEVERAL keys in one set of launches: keys = [(vk_bincode, n_inputs)], proof i of key
+        key_of[i], inputs packed in proof order (32 n_inputs[key_of[i]] bytes each); verdict bytes in the caller's order"""
+        return _groth16_verify_batch_keys(self.h, keys, key_of, inputs, proofs)
+
     def mpn_deposit_verify_batch(self, txs: bytes, n: int, want_address: bool = True):
         """n consecutive bincode(MpnDeposit): (verdict bytes: bit 0 the payment's Ed25519 signature, bit 1 the address decompresses; addresses
         n x 64 or None); a malformed record raises"""
@@ -536,6 +544,14 @@ class Bzk:
         """device buffers: inputs n x n_inputs x 32, proofs n x 387; ok n verdict bytes (the key is host bytes); synchronises"""
         self._ck(self.lib.bzk_groth16_verify_batch_dev(self.h, _ptr(vk_bincode), len(vk_bincode), _ptr(inputs), n_inputs, _ptr(proofs), n, _ptr(ok)),
                  "groth16_verify_batch_dev")
+
+    def groth16_verify_groups_dev(self, keys, counts, inputs, proofs, ok):
+        """device buffers, group after group: keys = [(vk_bincode, n_inputs)] (host bytes), group g is counts[g] proofs of keys[g]; inputs, proofs
+        (387 each) and the verdict bytes ok each contiguous in group order; synchronises"""
+        vks, vk_off, n_inputs = _pack_keys(keys)
+        cnt = (C.c_uint64 * max(len(keys), 1))(*counts)
+        self._ck(self.lib.bzk_groth16_verify_groups_dev(self.h, len(keys), _ptr(vks) if vks else None, vk_off, n_inputs, cnt, _ptr(inputs), _ptr(proofs),
+                                                        _ptr(ok)), "groth16_verify_groups_dev")
 
     def subgroup_check_batch(self, group: str, pts: bytes, inf: bytes = None) -> bytes:
         """verdict byte per raw point (group "g1": 96 B, "g2": 192 B): 1 in the subgroup, 0 on the curve outside it, 2 not a curve point"""
@@ -1583,6 +1599,35 @@ def _groth16_verify_batch(ctx_handle, vk_bincode: bytes, inputs: bytes, n_inputs
 def host_groth16_verify_batch(vk_bincode: bytes, inputs: bytes, n_inputs: int, proofs: bytes) -> bytes:
     """Bzk.groth16_verify_batch without a device: the same per-proof functions over the host field on host threads"""
     return _groth16_verify_batch(None, vk_bincode, inputs, n_inputs, proofs)
+
+
+def _pack_keys(keys):
+    """[(vk_bincode, n_inputs)] as the several-key entries take them: (the keys' bytes back to back, vk_off of len + 1, n_inputs)"""
+    off = [0]
+    for vk, _ in keys:
+        off.append(off[-1] + len(vk))
+    return (b"".join(vk for vk, _ in keys), (C.c_uint64 * len(off))(*off), (C.c_uint32 * max(len(keys), 1))(*[k for _, k in keys]))
+
+
+def _groth16_verify_batch_keys(ctx_handle, keys, key_of, inputs: bytes, proofs: bytes) -> bytes:
+    n = len(proofs) // 387
+    if len(proofs) != 387 * n or len(key_of) != n:
+        raise BzkError("groth16_verify_batch_keys: proofs must hold 387 bytes and key_of one index per proof")
+    per_key = collections.Counter(key_of)   # key_of: a sequence of ints, or a ctypes array of c_uint32 (passed as it is)
+    if all(0 <= k < len(keys) for k in per_key) and len(inputs) != sum(32 * keys[k][1] * c for k, c in per_key.items()):
+        raise BzkError("groth16_verify_batch_keys: inputs must hold 32 n_inputs[key_of[i]] bytes per proof")
+    vks, vk_off, n_inputs = _pack_keys(keys)
+    ok = C.create_string_buffer(max(n, 1))
+    _st(load_library().bzk_groth16_verify_batch_keys(ctx_handle, len(keys), _ptr(vks) if vks else None, vk_off, n_inputs,
+                                                     key_of if isinstance(key_of, C.Array) else (C.c_uint32 * max(n, 1))(*key_of),
+                                                     _ptr(inputs) if inputs else None,
+                                                     _ptr(proofs) if n else None, n, ok), "groth16_verify_batch_keys")
+    return ok.raw[:n]
+
+
+def host_groth16_verify_batch_keys(keys, key_of, inputs: bytes, proofs: bytes) -> bytes:
+    """Bzk.groth16_verify_batch_keys without a device: the same per-proof functions over the host field, all proofs in one task loop"""
+    return _groth16_verify_batch_keys(None, keys, key_of, inputs, proofs)
 
 
 def _subgroup_check_batch(ctx_handle, group: str, pts: bytes, inf: bytes = None) -> bytes:

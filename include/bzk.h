@@ -484,6 +484,23 @@ int32_t bzk_groth16_verify_batch(bzk_ctx* ctx, const uint8_t* vk, uint64_t vk_le
                                  const uint8_t* proofs, uint64_t n, uint8_t* ok);
 int32_t bzk_groth16_verify_batch_dev(bzk_ctx* ctx, const uint8_t* vk, uint64_t vk_len, const void* inputs_dev, uint32_t n_inputs,
                                      const void* proofs_dev, uint64_t n, void* ok_dev);
+/* The same check for proofs of SEVERAL keys in one call (a block's Deposit, Withdraw and Update proofs have three): every verdict is what
+ * bzk_groth16_verify_batch says about that proof under its key, but the device runs ONE set of launches per round of 2^16 lanes instead of one
+ * per key - the lanes of all keys side by side, every key's proofs padded to whole blocks of 64 - so a call of a few thousand proofs costs one
+ * lane's chain of dependent products, not one per key.  Key k is the bytes vks[vk_off[k] .. vk_off[k + 1]) (vk_off: n_keys + 1 ascending
+ * offsets) with n_inputs[k] inputs.
+ * bzk_groth16_verify_batch_keys: n proofs in any order, proof i of key key_of[i]; inputs are packed in proof order (proof i holds
+ * 32 n_inputs[key_of[i]] bytes), proofs = n x 387 bytes; the host groups the rows by key (a stable counting sort), stages them round by round
+ * and returns ok[i] in the caller's order.  ctx = NULL runs the per-proof functions on the host's threads, all proofs in one task loop.
+ * bzk_groth16_verify_groups_dev: the rows already grouped in device memory - group g is counts[g] proofs of key g, the groups' inputs, proofs
+ * and verdict bytes each contiguous, group after group (two groups may name the same key bytes; a count of 0 is legal anywhere); needs a context.
+ * A key the single call refuses gives 0 for ITS proofs only; a key of more than 16 inputs takes the host-thread route (on copies in the device
+ * form) while the other keys' proofs run on the device.  BZK_E_ARG, nothing written: key_of[i] >= n_keys, vk_off not ascending, a key shorter
+ * than 878 bytes, n_keys = 0 with n > 0, a null pointer with n > 0.  n = 0 (all counts 0): BZK_OK, nothing touched. */
+int32_t bzk_groth16_verify_batch_keys(bzk_ctx* ctx, uint32_t n_keys, const uint8_t* vks, const uint64_t* vk_off, const uint32_t* n_inputs,
+                                      const uint32_t* key_of, const uint8_t* inputs, const uint8_t* proofs, uint64_t n, uint8_t* ok);
+int32_t bzk_groth16_verify_groups_dev(bzk_ctx* ctx, uint32_t n_groups, const uint8_t* vks, const uint64_t* vk_off, const uint32_t* n_inputs,
+                                      const uint64_t* counts, const void* inputs_dev, const void* proofs_dev, void* ok_dev);
 /* Subgroup membership of n raw points (little-endian Montgomery limbs: G1 x | y = 96 B, G2 x.c0 | x.c1 | y.c0 | y.c1 = 192 B; what
  * bzk_bellman_params_decode emits), one GPU lane per point: the third check of bls12_381 `from_uncompressed` after canonical range and the
  * curve equation.  ok[i] = 1: in the order-r subgroup; 0: on the curve but outside it; 2: not a valid finite curve point (a coordinate's limbs

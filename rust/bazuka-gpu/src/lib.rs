@@ -25,6 +25,7 @@
 //!   * `contract_update_spans`  - where the `ContractUpdate`s of one contract lie in serialized transactions (host only)
 //!   * `groth16_prove`          - beside `groth16_verify` (src/zk/groth16/mod.rs:67-75), same argument order
 //!   * `groth16_verify_batch`   - `groth16_verify` for n proofs of one key: update_contract/mod.rs:100 and `MpnWork::verify` (src/mpn/mod.rs:281-295)
+//!   * `Gpu::groth16_verify_batch_keys` - the same for proofs of several keys (a block's Deposit, Withdraw and Update proofs) in one set of launches
 //!   * `compress`               - `ZkStateModel::compress::<H>(&data)` (src/zk/mod.rs:392-399)
 //!   * `DeviceStateManager`     - `KvStoreStateManager::{update_contract, root, get_data, prove}` (src/zk/state/mod.rs:218-438) for one
 //!                                contract with the values resident on the GPU
@@ -344,6 +345,36 @@ impl Gpu {
         let mut ok = vec![0u8; n];
         check(self.0, unsafe {
             sys::bzk_groth16_verify_batch(self.0, vk.as_ptr(), vk.len() as u64, inputs.as_ptr(), n_inputs as u32, proofs.as_ptr(), n as u64, ok.as_mut_ptr())
+        })?;
+        Ok(ok.into_iter().map(|b| b != 0).collect())
+    }
+
+    /// The same for proofs of SEVERAL keys in one call - a block's Deposit, Withdraw and Update proofs, or the mix `MpnWork::verify` meets: the
+    /// device runs one set of launches for all keys instead of one per key.  `keys` = bincode(Groth16VerifyingKey) each; every item = (the index
+    /// of its key, its public inputs, the proof), in any order; an item's number of inputs is its key's.  Verdicts come back in item order.
+    pub fn groth16_verify_batch_keys(&self, keys: &[&[u8]], items: &[(usize, &[[u8; 32]], &[u8; 387])]) -> Result<Vec<bool>, GpuError> {
+        let n = items.len();
+        let mut n_inputs: Vec<Option<u32>> = vec![None; keys.len()];
+        let (mut vks, mut vk_off) = (Vec::new(), vec![0u64]);
+        for k in keys {
+            vks.extend_from_slice(k);
+            vk_off.push(vks.len() as u64);
+        }
+        let (mut key_of, mut inputs, mut proofs) = (Vec::with_capacity(n), Vec::new(), Vec::with_capacity(387 * n));
+        for (k, x, p) in items {
+            if *k >= keys.len() || *n_inputs[*k].get_or_insert(x.len() as u32) != x.len() as u32 {
+                return Err(GpuError::Status(sys::BZK_E_ARG, "groth16_verify_batch_keys: a key index out of range, or two proofs of one key with different numbers of inputs".into()));
+            }
+            key_of.push(*k as u32);
+            for s in x.iter() {
+                inputs.extend_from_slice(&s[..]);
+            }
+            proofs.extend_from_slice(&p[..]);
+        }
+        let n_inputs: Vec<u32> = n_inputs.into_iter().map(|c| c.unwrap_or(0)).collect();
+        let mut ok = vec![0u8; n];
+        check(self.0, unsafe {
+            sys::bzk_groth16_verify_batch_keys(self.0, keys.len() as u32, vks.as_ptr(), vk_off.as_ptr(), n_inputs.as_ptr(), key_of.as_ptr(), inputs.as_ptr(), proofs.as_ptr(), n as u64, ok.as_mut_ptr())
         })?;
         Ok(ok.into_iter().map(|b| b != 0).collect())
     }

@@ -935,6 +935,8 @@ struct UpdSpans {
     const uint8_t* cid;
     uint64_t tx = 0;
     std::vector<uint64_t> out;
+    // bzk_l1_tx_deltas: per UpdateContract of cid (transaction, offset of the ZkDeltaPairs body, length, source: 0 `delta`, 1 `state_delta`, 2 none)
+    std::vector<uint64_t> deltas;
 };
 // an Option in the middle of the record that the signature leaves out: [cut_a, cut_b) where it is Some, empty otherwise
 template <class Skip>
@@ -949,6 +951,8 @@ inline void rd_cut_option(BinReader& r, size_t p0, l1::L1Rec& o, const char* wha
 }
 inline void rd_l1_tx(BinReader& r, uint32_t flags, bool and_delta, l1::L1Rec& o, UpdSpans* spans = nullptr) {
     const size_t p0 = r.pos;
+    bool upd_listed = false;  // an UpdateContract of spans->cid: where its delta lies
+    uint64_t d_off = 0, d_len = 0, d_src = 2;
     o = l1::L1Rec();
     if (rd_option_tag(r, "Option<src> tag")) {
         if (r.u64("ed25519 public key length") != 32) r.fail("ed25519 public key length");
@@ -994,7 +998,10 @@ inline void rd_l1_tx(BinReader& r, uint32_t flags, bool and_delta, l1::L1Rec& o,
             skip_contract_update(r, flags);
             if (listed && r.ok) spans->out.insert(spans->out.end(), {spans->tx, (uint64_t)a, (uint64_t)(r.pos - a)});
         }
+        const size_t at = r.pos;
         rd_cut_option(r, p0, o, "Option<ZkDeltaPairs> tag", skip_delta_pairs);
+        upd_listed = listed;
+        if (r.ok && r.pos > at + 1) d_off = at + 1, d_len = r.pos - at - 1, d_src = 0;
         break;
     }
     default:
@@ -1012,7 +1019,14 @@ inline void rd_l1_tx(BinReader& r, uint32_t flags, bool and_delta, l1::L1Rec& o,
         r.bytes(64, "ed25519 signature");
         o.flags |= l1::SIGNED;
     }
-    if (and_delta && rd_option_tag(r, "Option<state_delta> tag")) skip_delta_pairs(r);
+    if (and_delta) {
+        const size_t at = r.pos;
+        if (rd_option_tag(r, "Option<state_delta> tag")) {
+            skip_delta_pairs(r);
+            if (r.ok && d_src == 2) d_off = at + 1, d_len = r.pos - at - 1, d_src = 1;
+        }
+    }
+    if (upd_listed && r.ok) spans->deltas.insert(spans->deltas.end(), {spans->tx, d_off, d_len, d_src});
     if (r.ok && r.pos - p0 > l1::RECORD_MAX) r.fail("record longer than 1048576 bytes");
 }
 struct L1Parsed {

@@ -21,10 +21,13 @@
 #include <unordered_map>
 
 #include "bzk_internal.h"
+#include "bzk_poseidon29_coop.cuh"
+#include "bzk_state_chain.h"
 #include "host_zk.h"
 
 namespace bzk {
 int32_t poseidon_launch(bzk_ctx* ctx, const void* in_dev, uint32_t arity, uint64_t n, void* out_dev);  // poseidon.hip
+int32_t poseidon_consts_dev_shared(bzk_ctx* ctx, int t, const void** out, int* rf, int* rp);               // poseidon.hip
 }
 
 namespace {
@@ -338,24 +341,70 @@ int32_t compress_core(bzk_ctx* ctx, const Model& M, const uint64_t* loc_off, con
 //   key of an inner node of a list's tree  = locator of the list ++ {AUX | depth, index at that depth}   (0 < depth < log4_size)
 // Nodes that return to their default stay in the index (the reference removes them): same values either way.
 // ------------------------------------------------------------------------------------------------------------------------------
-constexpr uint64_t AUX = (uint64_t)1 << 63;  // no list index reaches it: 4^31 items at most
-typedef std::vector<uint64_t> Key;
-struct KeyHash {
-    size_t operator()(const Key& k) const {
-        uint64_t h = 0x9e3779b97f4a7c15ull ^ k.size();
-        for (uint64_t x : k) {
-            h ^= x + 0x9e3779b97f4a7c15ull + (h << 6) + (h >> 2);
-            h *= 0xff51afd7ed558ccdull;
-            h ^= h >> 33;
-        }
-        return (size_t)h;
-    }
-};
+using sc::AUX;
+using sc::Key;
+using sc::KeyHash;
 
 __global__ void __launch_bounds__(256) state_scatter_kernel(const Fr* __restrict__ in, const uint32_t* __restrict__ dst, uint64_t count,
                                                             Fr* __restrict__ vals) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) vals[dst[i]] = in[i];
+}
+
+// ---- the chain's kernels (bzk_state_update_chain): a level of every (node, time) pair of a round in ONE launch - the inputs fetched through source
+// indices (bzk_state_chain.h: top bit = the round's arena, else the value store), the hash written to the node's arena position.  The store and the
+// arena are two buffers and the output IS the arena: no __restrict__ between them.  What makes a launch safe is the plan - a group only reads versions
+// of lower levels.  Widths 2 .. 8 (poseidon29_hash / poseidon29_coop_val); wider structs run as gather, poseidon_launch.
+__device__ __forceinline__ Fr chain_load(const Fr* vals, const Fr* arena, uint32_t s) {
+    return (s & sc::SRC_ARENA) ? arena[s & ~sc::SRC_ARENA] : vals[s];
+}
+// one lane per node
+template <int T>
+__global__ void __launch_bounds__(128) state_chain_hash_kernel(const Fr* vals, Fr* arena, const uint32_t* __restrict__ src, uint64_t n, uint64_t first,
+                                                               const Fr29* __restrict__ consts, int rf, int rp) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Fr in[T - 1];
+#pragma unroll
+    for (int k = 0; k < T - 1; ++k) in[k] = chain_load(vals, arena, src[i * (T - 1) + k]);
+    arena[first + i] = poseidon29_hash<T>(in, consts, rf, rp);
+}
+// eight lanes per node (lane j of a group fetches input j - 1), for groups too small to fill the machine: poseidon_launch's reasoning and its bound
+template <int T>
+__global__ void __launch_bounds__(64) state_chain_hash_coop_kernel(const Fr* vals, Fr* arena, const uint32_t* __restrict__ src, uint64_t n, uint64_t first,
+                                                                   const Fr29* __restrict__ consts, int rf, int rp) {
+    const uint64_t node = (uint64_t)blockIdx.x * 8 + (threadIdx.x >> 3);
+    const uint64_t p = node < n ? node : n - 1;  // whole groups stay convergent for the shuffles
+    const int j = threadIdx.x & 7, jj = j < T ? j : T - 1;
+    const Fr mine = chain_load(vals, arena, src[p * (T - 1) + (jj >= 1 ? jj - 1 : 0)]);
+    const Fr h = poseidon29_coop_val<T>(mine, consts, rf, rp);
+    if (node < n && j == 1) arena[first + p] = h;
+}
+typedef void (*chain_hash_fn)(const Fr*, Fr*, const uint32_t*, uint64_t, uint64_t, const Fr29*, int, int);
+chain_hash_fn chain_hash_table(int t, bool coop) {
+    switch (t) {
+        case 2: return coop ? state_chain_hash_coop_kernel<2> : state_chain_hash_kernel<2>;
+        case 3: return coop ? state_chain_hash_coop_kernel<3> : state_chain_hash_kernel<3>;
+        case 4: return coop ? state_chain_hash_coop_kernel<4> : state_chain_hash_kernel<4>;
+        case 5: return coop ? state_chain_hash_coop_kernel<5> : state_chain_hash_kernel<5>;
+        case 6: return coop ? state_chain_hash_coop_kernel<6> : state_chain_hash_kernel<6>;
+        case 7: return coop ? state_chain_hash_coop_kernel<7> : state_chain_hash_kernel<7>;
+        case 8: return coop ? state_chain_hash_coop_kernel<8> : state_chain_hash_kernel<8>;
+        default: return nullptr;
+    }
+}
+constexpr uint64_t CHAIN_COOP_MAX_NODES = 8192;  // poseidon.hip COOP_MAX_NODES
+// the inputs of a wide group, side by side for poseidon_launch
+__global__ void __launch_bounds__(256) state_chain_gather_kernel(const Fr* vals, const Fr* arena, const uint32_t* __restrict__ src, uint64_t count,
+                                                                 Fr* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) out[i] = chain_load(vals, arena, src[i]);
+}
+// the commit of a prefix: the host has de-duplicated `dst`, no two lanes write one slot
+__global__ void __launch_bounds__(256) state_chain_commit_kernel(const Fr* __restrict__ arena, const uint32_t* __restrict__ from, const uint32_t* __restrict__ dst,
+                                                                 uint64_t count, Fr* __restrict__ vals) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) vals[dst[i]] = arena[from[i]];
 }
 
 }  // namespace
@@ -375,6 +424,10 @@ struct bzk_state {
     uint8_t root_hash[32];
     bool poisoned = false;  // a device error in the middle of an update: the slots no longer describe one state
     std::mutex m;
+    const uint32_t* find_slot(const Key& k) const {  // what sc::Updater reads the index through
+        auto it = slot_of.find(k);
+        return it != slot_of.end() ? &it->second : nullptr;
+    }
     // every call that used the store has synchronised its stream before returning, and the context is not touched here: a host that
     // tears its handles down in arbitrary order (a garbage collector) may already have destroyed it
     ~bzk_state() {
@@ -452,136 +505,9 @@ int32_t state_read_slots(bzk_state* S, const std::vector<uint32_t>& idx, uint8_t
     return BZK_OK;
 }
 
-// the plan of one update_contract
-struct UpPlan {
-    struct Node { uint32_t dst, first_in, arity, level; };
-    std::vector<Node> nodes;
-    std::vector<uint32_t> inputs;                    // slots
-    std::vector<std::pair<Key, uint32_t>> new_keys;  // index entries to add once the update has run
-    std::vector<uint32_t> scalar_dst;                // per pair: its slot
-    uint32_t next_slot = 0;
-    std::string err;
-    int32_t code = 0;  // BZK_REFUSE_* of `err`
-};
-struct Updater {
-    bzk_state& S;
-    UpPlan& P;
-    const uint64_t* loc_off;
-    const uint64_t* loc;
-    const std::vector<uint64_t>& order;
-    Key prefix;
-    struct Val { uint32_t slot, level; };
-    uint64_t at(uint64_t pos, uint64_t d) const { return loc[loc_off[order[pos]] + d]; }
-    uint64_t len(uint64_t pos) const { return loc_off[order[pos] + 1] - loc_off[order[pos]]; }
-    uint32_t slot_for(const Key& k) {  // the slot of a key that is being written: its own, or a fresh one
-        auto it = S.slot_of.find(k);
-        if (it != S.slot_of.end()) return it->second;
-        if (P.next_slot >= 0x7ffffff0u) { P.err = "too many nodes"; P.code = BZK_REFUSE_OTHER; return 0; }
-        P.new_keys.push_back({k, P.next_slot});
-        return P.next_slot++;
-    }
-    uint32_t read_slot(const Key& k, uint32_t dflt) const {  // an untouched sibling: its slot, or the default of its kind
-        auto it = S.slot_of.find(k);
-        return it != S.slot_of.end() ? it->second : dflt;
-    }
-    Val hashed(const Key& dst_key, const std::vector<uint32_t>& in, uint32_t level) {
-        const uint32_t dst = slot_for(dst_key);
-        P.nodes.push_back({dst, (uint32_t)P.inputs.size(), (uint32_t)in.size(), level});
-        P.inputs.insert(P.inputs.end(), in.begin(), in.end());
-        return {dst, level};
-    }
-    // the value at `prefix` (of model type m, prefix.size() == d) given the sorted pairs [lo, hi) below it (non-empty)
-    Val build(int m, uint64_t d, uint64_t lo, uint64_t hi) {
-        const ModelNode& n = S.M.nodes[m];
-        if (!P.err.empty()) return {0, 0};
-        if (n.kind == 0) {
-            if (hi - lo != 1) { P.err = "duplicate locator"; P.code = BZK_REFUSE_DUPLICATE_LOCATOR; return {0, 0}; }
-            if (len(lo) != d) { P.err = "locator points below a scalar (ZkLocatorError::InvalidLocator)"; P.code = BZK_REFUSE_INVALID_LOCATOR; return {0, 0}; }
-            const uint32_t s = slot_for(prefix);
-            P.scalar_dst[order[lo]] = s;
-            return {s, 0};
-        }
-        for (uint64_t i = lo; i < hi; ++i)
-            if (len(i) <= d) { P.err = "locator does not reach a scalar (StateManagerError::NonScalarLocatorError)"; P.code = BZK_REFUSE_NON_SCALAR_LOCATOR; return {0, 0}; }
-        if (n.kind == 1) {
-            std::vector<uint32_t> in(n.fields.size());
-            uint32_t lv = 0;
-            uint64_t i = lo;
-            for (size_t f = 0; f < n.fields.size(); ++f) {
-                uint64_t j = i;
-                while (j < hi && at(j, d) == f) ++j;
-                prefix.push_back(f);
-                if (j > i) {
-                    const Val v = build(n.fields[f], d + 1, i, j);
-                    in[f] = v.slot;
-                    lv = std::max(lv, v.level);
-                } else {
-                    in[f] = read_slot(prefix, S.dflt_slot[n.fields[f]]);
-                }
-                prefix.pop_back();
-                i = j;
-            }
-            if (i != hi) { P.err = "struct field index out of range (the reference indexes field_types out of bounds)"; P.code = BZK_REFUSE_INVALID_LOCATOR; return {0, 0}; }
-            if (!P.err.empty()) return {0, 0};
-            return hashed(prefix, in, lv + 1);
-        }
-        const uint64_t size = n.log4 >= 32 ? ~0ull : ((uint64_t)1 << (2 * n.log4));
-        struct Cur { uint64_t idx; Val v; };
-        std::vector<Cur> cur;
-        for (uint64_t i = lo; i < hi;) {
-            const uint64_t idx = at(i, d);
-            if (idx >= size) { P.err = "list index out of range (ZkLocatorError::InvalidLocator)"; P.code = BZK_REFUSE_INVALID_LOCATOR; return {0, 0}; }
-            uint64_t j = i;
-            while (j < hi && at(j, d) == idx) ++j;
-            prefix.push_back(idx);
-            cur.push_back({idx, build(n.item, d + 1, i, j)});
-            prefix.pop_back();
-            if (!P.err.empty()) return {0, 0};
-            i = j;
-        }
-        if (n.log4 == 0) {
-            // `set_data`'s level loop does not run: the list's value IS its only item; both locators name one slot
-            // (this prefix is visited once per plan, so the index alone says whether the alias exists)
-            if (S.slot_of.find(prefix) == S.slot_of.end()) P.new_keys.push_back({prefix, cur[0].v.slot});
-            return cur[0].v;
-        }
-        for (int k = n.log4; k > 0; --k) {  // children at depth k -> parents at depth k - 1
-            std::vector<Cur> up;
-            for (size_t i = 0; i < cur.size();) {
-                const uint64_t parent = cur[i].idx >> 2;
-                std::vector<uint32_t> in(4);
-                uint32_t lv = 0;
-                for (uint64_t j = 0; j < 4; ++j) {
-                    const uint64_t child = 4 * parent + j;
-                    if (i < cur.size() && cur[i].idx == child) {
-                        in[j] = cur[i].v.slot;
-                        lv = std::max(lv, cur[i].v.level);
-                        ++i;
-                    } else {
-                        if (k == n.log4) {
-                            prefix.push_back(child);
-                        } else {
-                            prefix.push_back(AUX | (uint64_t)k);
-                            prefix.push_back(child);
-                        }
-                        in[j] = read_slot(prefix, S.depth_slot[m][k]);
-                        prefix.resize(d);
-                    }
-                }
-                if (k > 1) {
-                    prefix.push_back(AUX | (uint64_t)(k - 1));
-                    prefix.push_back(parent);
-                }
-                const Val v = hashed(prefix, in, lv + 1);
-                prefix.resize(d);
-                if (!P.err.empty()) return {0, 0};
-                up.push_back({parent, v});
-            }
-            cur.swap(up);
-        }
-        return cur[0].v;
-    }
-};
+// the plan of one update_contract and the walk that makes it: bzk_state_chain.h (shared with the chain planner)
+using sc::UpPlan;
+typedef sc::Updater<bzk_state> Updater;
 
 int32_t state_update_impl(bzk_state* S, const uint64_t* loc_off, const uint64_t* loc, const uint8_t* values, uint64_t n, uint64_t target_height,
                           uint8_t* prev_values_out) {
@@ -716,6 +642,183 @@ int32_t state_update_impl(bzk_state* S, const uint64_t* loc_off, const uint64_t*
         was = now ? 1 : 0;
     }
     S->height = target_height;
+    return BZK_OK;
+}
+
+// ---- bzk_state_update_chain: m deltas through the tree together (bzk_state_chain.h).  m_out >= m verdicts are written; tail_refusal (or NULL): delta m
+// exists but did not decode - it is refused for that reason if the deltas before it all apply
+int32_t state_chain_impl(bzk_state* S, uint64_t m, uint64_t m_out, const char* tail_refusal, const uint64_t* delta_off, const uint64_t* loc_off,
+                         const uint64_t* loc, const uint8_t* values, const uint64_t* heights, const uint8_t* claims, uint64_t round_versions,
+                         uint8_t* states_out, uint8_t* verdict, uint64_t* applied, uint8_t* prev_out) {
+    bzk_ctx* ctx = S->ctx;
+    if (S->poisoned) { ctx->last_error = "state: an earlier update failed on the device; this state is unusable"; return BZK_E_DEVICE; }
+    for (uint64_t j = 0; j < m; ++j)
+        if (delta_off[j] > delta_off[j + 1]) return BZK_E_ARG;
+    const uint64_t pairs = m ? delta_off[m] : 0;
+    for (uint64_t i = m ? delta_off[0] : 0; i < pairs; ++i)
+        if (loc_off[i] > loc_off[i + 1]) return BZK_E_ARG;
+    memset(states_out, 0, (size_t)m_out * 40);
+    memset(verdict, BZK_CHAIN_NOT_REACHED, (size_t)m_out);
+    *applied = 0;
+    if (prev_out && pairs) memset(prev_out, 0, (size_t)pairs * 32);
+    sc::ChainPlanner<bzk_state> PL(*S);
+    PL.plan(m, delta_off, loc_off, loc, values, [](const uint8_t* v) {
+        Fr f;
+        memcpy(f.l, v, 32);
+        Fr g = f;
+        fe_reduce_once<FrParams>(g);
+        return g.equals(f);
+    });
+    const uint64_t mp = PL.deltas.size();
+    (void)hipSetDevice(ctx->device);
+    // the rollbacks that only the store knows: scalars the call's first writer of a slot finds there.  Read before anything is committed
+    std::vector<uint8_t> resident;
+    std::vector<uint64_t> resident_at(PL.prev_of.size(), 0);
+    if (prev_out) {
+        std::vector<uint32_t> idx;
+        uint64_t q = 0;
+        for (uint64_t j = 0; j < mp; ++j)
+            for (uint64_t i = 0; i < PL.deltas[j].n; ++i, ++q)
+                if (PL.prev_of[q] == sc::PREV_RESIDENT) {
+                    resident_at[q] = idx.size();
+                    idx.push_back(PL.deltas[j].P.scalar_dst[i]);
+                }
+        resident.resize(idx.size() * 32);
+        BZK_TRY(state_read_slots(S, idx, resident.data()));
+    }
+    const std::vector<uint64_t> cuts = PL.rounds(round_versions);
+    std::vector<sc::ChainRound> R(cuts.size() - 1);
+    uint64_t cap_v = 0, cap_src = 0, cap_in = 0, cap_d = 0, cap_w = 0;
+    for (size_t r = 0; r < R.size(); ++r) {
+        R[r].resolve(PL.deltas, cuts[r], cuts[r + 1]);
+        cap_v = std::max(cap_v, R[r].n_versions);
+        cap_src = std::max<uint64_t>(cap_src, R[r].src.size());
+        cap_in = std::max(cap_in, R[r].widest_in);
+        cap_d = std::max(cap_d, R[r].d1 - R[r].d0);
+        cap_w = std::max<uint64_t>(cap_w, R[r].writes.size());
+    }
+    WsLayout ws("state_chain_impl");
+    Fr *d_arena, *d_in, *d_roots;
+    uint32_t *d_src, *d_rix, *d_from, *d_dst;
+    ws.take(d_arena, cap_v); ws.take(d_src, cap_src); ws.take(d_in, cap_in); ws.take(d_rix, cap_d); ws.take(d_roots, cap_d);
+    ws.take(d_from, cap_w); ws.take(d_dst, cap_w);
+    if (mp) BZK_TRY(ws.commit(ctx));
+    uint64_t done = 0;  // deltas that are part of the state now
+    bool stopped = false;
+    std::vector<uint32_t> rix, from, dst;
+    std::vector<uint8_t> roots;
+    for (size_t r = 0; r < R.size() && !stopped; ++r) {
+        const sc::ChainRound& C = R[r];
+        // every index a lane will follow, checked here: a plain source is a slot of the store as it stands, an arena source a version of this round
+        for (uint32_t s : C.src)
+            if ((s & sc::SRC_ARENA) ? (s & ~sc::SRC_ARENA) >= C.n_versions : s >= S->used) { ctx->last_error = "state_update_chain: a source index out of range"; return BZK_E_INTERNAL; }
+        rix.clear();
+        for (uint32_t x : C.root_ix)
+            if (x != sc::NO_ROOT) {
+                if (x >= C.n_versions) { ctx->last_error = "state_update_chain: a root index out of range"; return BZK_E_INTERNAL; }
+                rix.push_back(x);
+            }
+        roots.assign(rix.size() * 32, 0);
+        // pageable sources (the caller's values, this frame's vectors): whatever was queued finishes before an error returns
+        auto run = [&]() -> int32_t {
+            if (C.n_up) BZK_HIP(ctx, hipMemcpyAsync(d_arena, values + 32 * C.pair0, (size_t)C.n_up * 32, hipMemcpyHostToDevice, ctx->stream));
+            if (!C.src.empty()) BZK_HIP(ctx, hipMemcpyAsync(d_src, C.src.data(), C.src.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+            for (const sc::ChainRound::Group& g : C.groups) {
+                const int t = (int)g.arity + 1;
+                if (t <= 8) {
+                    const void* consts;
+                    int rf, rp;
+                    BZK_TRY(poseidon_consts_dev_shared(ctx, t, &consts, &rf, &rp));
+                    if (g.count <= CHAIN_COOP_MAX_NODES && !ctx->no_coop) {
+                        BZK_LAUNCH(ctx, "state_chain_hash_coop", chain_hash_table(t, true), dim3((unsigned)((g.count + 7) / 8)), dim3(64), 0, (const Fr*)S->d_vals,
+                                   d_arena, (const uint32_t*)(d_src + g.src_off), g.count, g.first, (const Fr29*)consts, rf, rp);
+                    } else {
+                        const uint64_t blocks = (g.count + 127) / 128;
+                        if (blocks > 0x7fffffffull) return BZK_E_ARG;
+                        BZK_LAUNCH(ctx, "state_chain_hash", chain_hash_table(t, false), dim3((unsigned)blocks), dim3(128), 0, (const Fr*)S->d_vals, d_arena,
+                                   (const uint32_t*)(d_src + g.src_off), g.count, g.first, (const Fr29*)consts, rf, rp);
+                    }
+                } else {
+                    const uint64_t cnt = g.count * g.arity;
+                    BZK_LAUNCH(ctx, "state_chain_gather", state_chain_gather_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, (const Fr*)S->d_vals,
+                               (const Fr*)d_arena, (const uint32_t*)(d_src + g.src_off), cnt, d_in);
+                    BZK_TRY(poseidon_launch(ctx, d_in, g.arity, g.count, d_arena + g.first));
+                }
+            }
+            if (!rix.empty()) {
+                BZK_HIP(ctx, hipMemcpyAsync(d_rix, rix.data(), rix.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+                BZK_LAUNCH(ctx, "state_gather", state_gather_kernel, dim3((unsigned)((rix.size() + 255) / 256)), dim3(256), 0, (const Fr*)d_arena,
+                           (const uint32_t*)d_rix, (uint64_t)rix.size(), d_roots);
+                BZK_HIP(ctx, hipMemcpyAsync(roots.data(), d_roots, rix.size() * 32, hipMemcpyDeviceToHost, ctx->stream));
+            }
+            BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            return BZK_OK;
+        };
+        if (const int32_t st = run(); st != BZK_OK) {
+            (void)hipStreamSynchronize(ctx->stream);
+            if (st == BZK_E_DEVICE) S->poisoned = true;
+            return st;
+        }
+        // the states of the round and the prefix of it that holds
+        std::vector<uint8_t> states((size_t)(C.d1 - C.d0) * 40);
+        uint8_t cur[32];
+        memcpy(cur, S->root_hash, 32);
+        uint64_t upto = C.d1, q = 0;
+        for (uint64_t j = C.d0; j < C.d1; ++j) {
+            if (C.root_ix[j - C.d0] != sc::NO_ROOT) memcpy(cur, roots.data() + 32 * q++, 32);
+            uint8_t* s40 = states.data() + 40 * (j - C.d0);
+            memcpy(s40, cur, 32);
+            memcpy(s40 + 32, &PL.deltas[j].size_after, 8);
+            if (upto == C.d1 && claims && memcmp(s40, claims + 40 * j, 40) != 0) upto = j;
+        }
+        if (upto > C.d0) {
+            BZK_TRY(state_grow(S, PL.deltas[upto - 1].used_after));
+            C.commit_lists(upto, from, dst);
+            auto commit = [&]() -> int32_t {
+                if (dst.empty()) return BZK_OK;
+                BZK_HIP(ctx, hipMemcpyAsync(d_from, from.data(), from.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+                BZK_HIP(ctx, hipMemcpyAsync(d_dst, dst.data(), dst.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+                BZK_LAUNCH(ctx, "state_chain_commit", state_chain_commit_kernel, dim3((unsigned)((dst.size() + 255) / 256)), dim3(256), 0, (const Fr*)d_arena,
+                           (const uint32_t*)d_from, (const uint32_t*)d_dst, (uint64_t)dst.size(), S->d_vals);
+                BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                return BZK_OK;
+            };
+            for (size_t i = 0; i < dst.size(); ++i)
+                if (dst[i] >= S->cap || from[i] >= C.n_versions) { ctx->last_error = "state_update_chain: a commit index out of range"; return BZK_E_INTERNAL; }
+            if (const int32_t st = commit(); st != BZK_OK) {
+                (void)hipStreamSynchronize(ctx->stream);
+                S->poisoned = true;  // the slots may be half-written
+                return st;
+            }
+            sc::commit_index(*S, PL.deltas, C.d0, upto, values);
+            memcpy(S->root_hash, states.data() + 40 * (upto - 1 - C.d0), 32);
+            S->height = heights[upto - 1];
+            done = upto;
+        }
+        const uint64_t shown = upto < C.d1 ? upto + 1 : upto;  // a mismatching delta shows the state it gives
+        memcpy(states_out + 40 * C.d0, states.data(), (size_t)(shown - C.d0) * 40);
+        memset(verdict + C.d0, BZK_CHAIN_APPLIED, (size_t)(upto - C.d0));
+        if (upto < C.d1) {
+            verdict[upto] = BZK_CHAIN_MISMATCH;
+            stopped = true;
+        }
+    }
+    *applied = done;
+    if (!stopped && (PL.refused || (tail_refusal && mp == m))) {
+        verdict[mp] = BZK_CHAIN_REFUSED;
+        ctx->last_error = "state_update_chain: delta " + std::to_string(mp) + ": " + (PL.refused ? PL.refuse_err : std::string(tail_refusal));
+        ctx->last_refusal = PL.refused ? PL.refuse_code : BZK_REFUSE_OTHER;
+    }
+    if (prev_out) {
+        uint64_t q = 0;
+        for (uint64_t j = 0; j < mp; ++j)
+            for (uint64_t i = 0; i < PL.deltas[j].n; ++i, ++q) {
+                if (j >= done) continue;
+                const int64_t from_pair = PL.prev_of[q];
+                if (from_pair >= 0) memcpy(prev_out + 32 * (PL.deltas[j].pair0 + i), values + 32 * from_pair, 32);
+                else if (from_pair == sc::PREV_RESIDENT) memcpy(prev_out + 32 * (PL.deltas[j].pair0 + i), resident.data() + 32 * resident_at[q], 32);
+            }
+    }
     return BZK_OK;
 }
 
@@ -881,31 +984,98 @@ static int32_t state_entry_update(bzk_state* st, const uint64_t* loc_off, const 
 
 // delta = bincode(ZkDeltaPairs) = HashMap<ZkDataLocator, Option<ZkScalar>> (src/zk/mod.rs:473-474): u64 count; per entry Vec<u64>,
 // the Option's u8 tag, the four Montgomery limbs when Some.  None writes zero, as `update_contract` does (`v.unwrap_or_default()`).
-static int32_t state_entry_update_bincode(bzk_state* st, const uint8_t* delta, uint64_t delta_len, uint64_t target_height, uint8_t compressed_out[40]) {
-    if (!st || !delta || !compressed_out) return BZK_E_ARG;
+// One decoder for bzk_state_update_bincode and for every blob of bzk_state_update_chain_bincode.
+// appends the pairs of one blob: their locators to (off, loc), their values (zeros for None) to vals; false when the bytes are not one ZkDeltaPairs
+static bool delta_decode_append(const uint8_t* delta, uint64_t delta_len, std::vector<uint64_t>& off, std::vector<uint64_t>& loc, std::vector<uint8_t>& vals,
+                                uint64_t* n_out) {
     Rd r{delta, delta_len};
     const uint64_t n = r.u(8);
-    if (!r.ok || n > delta_len / 9) return BZK_E_ARG;
-    std::vector<uint64_t> off(1, 0), loc;
-    std::vector<uint8_t> vals((size_t)n * 32, 0);
+    if (!r.ok || n > delta_len / 9) return false;
+    const size_t v0 = vals.size();
+    vals.resize(v0 + (size_t)n * 32, 0);
     for (uint64_t i = 0; i < n; ++i) {
         const uint64_t k = r.u(8);
-        if (!r.ok || k > 64) return BZK_E_ARG;
+        if (!r.ok || k > 64) return false;
         for (uint64_t j = 0; j < k; ++j) loc.push_back(r.u(8));
         off.push_back(loc.size());
         const uint64_t tag = r.u(1);
-        if (!r.ok || tag > 1) return BZK_E_ARG;
+        if (!r.ok || tag > 1) return false;
         if (tag) {
-            if (r.off + 32 > delta_len) return BZK_E_ARG;
-            memcpy(vals.data() + 32 * i, delta + r.off, 32);
+            if (r.off + 32 > delta_len) return false;
+            memcpy(vals.data() + v0 + 32 * i, delta + r.off, 32);
             r.off += 32;
         }
     }
-    if (!r.ok || r.off != delta_len) return BZK_E_ARG;
+    if (!r.ok || r.off != delta_len) return false;
+    *n_out = n;
+    return true;
+}
+static int32_t state_entry_update_bincode(bzk_state* st, const uint8_t* delta, uint64_t delta_len, uint64_t target_height, uint8_t compressed_out[40]) {
+    if (!st || !delta || !compressed_out) return BZK_E_ARG;
+    std::vector<uint64_t> off(1, 0), loc;
+    std::vector<uint8_t> vals;
+    uint64_t n = 0;
+    if (!delta_decode_append(delta, delta_len, off, loc, vals, &n)) return BZK_E_ARG;
     uint64_t size = 0;
     BZK_TRY(state_entry_update(st, off.data(), loc.data(), vals.data(), n, target_height, compressed_out, &size, nullptr));
     memcpy(compressed_out + 32, &size, 8);
     return BZK_OK;
+}
+
+// a refused delta of a chain is a verdict under BZK_OK: the refusal outlives the call's status, unlike refusal_scope's
+static int32_t state_entry_update_chain(bzk_state* st, uint64_t m, uint64_t m_out, const char* tail_refusal, const uint64_t* delta_off, const uint64_t* loc_off,
+                                        const uint64_t* loc, const uint8_t* values, const uint64_t* target_heights, const uint8_t* claims, uint64_t round_versions,
+                                        uint8_t* states_out, uint8_t* verdict, uint64_t* applied, uint8_t* prev_values_out) {
+    std::lock_guard<std::mutex> g(st->m);
+    st->ctx->last_refusal = BZK_REFUSE_NONE;
+    const int32_t s = state_chain_impl(st, m, m_out, tail_refusal, delta_off, loc_off, loc, values, target_heights, claims, round_versions, states_out, verdict,
+                                       applied, prev_values_out);
+    if (s == BZK_E_ARG) st->ctx->last_refusal = BZK_REFUSE_OTHER;
+    return s;
+}
+int32_t bzk_state_update_chain(bzk_state* st, uint64_t m, const uint64_t* delta_off, const uint64_t* loc_off, const uint64_t* loc, const uint8_t* values,
+                               const uint64_t* target_heights, const uint8_t* claims, uint64_t round_versions, uint8_t* states_out, uint8_t* verdict,
+                               uint64_t* applied, uint8_t* prev_values_out) {
+    if (!st) return BZK_E_ARG;
+    if (m == 0) {  // a no-op that refuses nothing
+        st->ctx->last_refusal = BZK_REFUSE_NONE;
+        if (applied) *applied = 0;
+        return BZK_OK;
+    }
+    if (!delta_off || !target_heights || !states_out || !verdict || !applied) return BZK_E_ARG;
+    if (delta_off[m] && (!loc_off || !values)) return BZK_E_ARG;
+    if (delta_off[m] && delta_off[0] <= delta_off[m] && loc_off[delta_off[m]] && !loc) return BZK_E_ARG;
+    static const uint64_t zero_off[1] = {0};
+    return state_entry_update_chain(st, m, m, nullptr, delta_off, delta_off[m] ? loc_off : zero_off, loc, values, target_heights, claims, round_versions, states_out,
+                                    verdict, applied, prev_values_out);
+}
+int32_t bzk_state_update_chain_bincode(bzk_state* st, uint64_t m, const uint8_t* deltas, const uint64_t* delta_byte_off, const uint64_t* target_heights,
+                                       const uint8_t* claims, uint64_t round_versions, uint8_t* states_out, uint8_t* verdict, uint64_t* applied) {
+    if (!st) return BZK_E_ARG;
+    if (m == 0) {  // a no-op that refuses nothing
+        st->ctx->last_refusal = BZK_REFUSE_NONE;
+        if (applied) *applied = 0;
+        return BZK_OK;
+    }
+    if (!deltas || !delta_byte_off || !target_heights || !states_out || !verdict || !applied) return BZK_E_ARG;
+    for (uint64_t j = 0; j < m; ++j)
+        if (delta_byte_off[j] > delta_byte_off[j + 1]) return BZK_E_ARG;
+    std::vector<uint64_t> d_off(1, 0), off(1, 0), loc;
+    std::vector<uint8_t> vals;
+    uint64_t good = 0;  // the blobs before the first that does not decode
+    for (; good < m; ++good) {
+        const size_t o0 = off.size(), l0 = loc.size(), v0 = vals.size();
+        uint64_t n = 0;
+        if (!delta_decode_append(deltas + delta_byte_off[good], delta_byte_off[good + 1] - delta_byte_off[good], off, loc, vals, &n)) {
+            off.resize(o0), loc.resize(l0), vals.resize(v0);
+            break;
+        }
+        d_off.push_back(d_off.back() + n);
+    }
+    if (loc.empty()) loc.push_back(0);
+    if (vals.empty()) vals.resize(32, 0);
+    return state_entry_update_chain(st, good, m, good < m ? "not a bincode ZkDeltaPairs" : nullptr, d_off.data(), off.data(), loc.data(), vals.data(), target_heights,
+                                    claims, round_versions, states_out, verdict, applied, nullptr);
 }
 
 int32_t bzk_state_root(bzk_state* st, uint8_t state_hash[32], uint64_t* state_size, uint64_t* height) {

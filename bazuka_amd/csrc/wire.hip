@@ -422,4 +422,23 @@ int32_t bzk_l1_tx_updates(const uint8_t* txs, uint64_t len, uint64_t n, uint32_t
     }
 }
 
+int32_t bzk_l1_tx_deltas(const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, const uint8_t contract_id[32], uint64_t* spans_out, uint64_t cap,
+                         uint64_t* n_out) {
+    if (form > BZK_L1_FORM_TX_AND_DELTA || !contract_id || !n_out || (n && !txs) || (cap && !spans_out)) return BZK_E_ARG;
+    *n_out = 0;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        L1Parsed P;
+        UpdSpans S;
+        S.cid = contract_id;
+        if (!parse_l1_txs(txs, len, n, form == BZK_L1_FORM_TX_AND_DELTA, g_wire_flags.load(), P, g_work_error, &S)) return BZK_E_ARG;
+        const uint64_t found = S.deltas.size() / 4;
+        if (found && cap) memcpy(spans_out, S.deltas.data(), (size_t)std::min(found, cap) * 32);
+        *n_out = found;
+        return BZK_OK;
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
 }  // extern "C"

@@ -68,6 +68,7 @@ SIGNATURES = {
     "bzk_block_bodies_check": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "bzk_contract_updates_check": (_i32, [_vp, _vp, _vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "bzk_l1_tx_updates": (_i32, [_vp, _u64, _u64, C.c_uint32, _vp, _vp, _u64, _vp]),
+    "bzk_l1_tx_deltas": (_i32, [_vp, _u64, _u64, C.c_uint32, _vp, _vp, _u64, _vp]),
     "bzk_merkle4_root": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_merkle4_root_dev": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     "bzk_state_compress": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
@@ -77,6 +78,8 @@ SIGNATURES = {
     "bzk_state_free": (None, [_vp]),
     "bzk_state_update": (_i32, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, C.POINTER(_u64), _vp]),
     "bzk_state_update_bincode": (_i32, [_vp, _vp, _u64, _u64, _vp]),
+    "bzk_state_update_chain": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, C.POINTER(_u64), _vp]),
+    "bzk_state_update_chain_bincode": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, C.POINTER(_u64)]),
     "bzk_state_root": (_i32, [_vp, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "bzk_state_get": (_i32, [_vp, _vp, _vp, _u64, _vp]),
     "bzk_state_prove": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, C.POINTER(_u32)]),
@@ -1398,6 +1401,9 @@ def _csr(locators):
     return (_u64 * len(off))(*off), (_u64 * max(1, len(loc)))(*loc)
 
 
+CHAIN_APPLIED, CHAIN_MISMATCH, CHAIN_REFUSED, CHAIN_NOT_REACHED = 0, 1, 2, 3  # BZK_CHAIN_*
+
+
 class DeviceState:
     """`KvStoreStateManager` for one contract with the values resident on the device (bzk_state_*): update / root / get / prove"""
 
@@ -1434,6 +1440,48 @@ class DeviceState:
         out = C.create_string_buffer(40)
         self.ctx._ck(self.lib.bzk_state_update_bincode(self.h, _ptr(delta_bincode), len(delta_bincode), target_height, out), "state_update_bincode")
         return out.raw
+
+    def update_chain(self, deltas, target_heights, claims=None, round_versions: int = 0, want_rollback=False):
+        """deltas: m lists of (locator, 32-byte Montgomery scalar) as `update` takes them, applied in order while each is accepted and gives
+        claims[j] (m x 40 bytes: state_hash | state_size; None: nothing can mismatch).  -> (applied, [CHAIN_* verdicts], [40-byte state per
+        delta][, per delta the previous values of its pairs]).  A refused delta is a verdict: ctx.last_refusal() / last_error name it"""
+        deltas = [list(d) for d in deltas]
+        m, flat = len(deltas), [p for d in deltas for p in d]
+        d_off = [0]
+        for d in deltas:
+            d_off.append(d_off[-1] + len(d))
+        o, lo = _csr(l for l, _ in flat)
+        vals = b"".join(v for _, v in flat)
+        hs = (_u64 * max(1, m))(*[int(h) for h in target_heights])
+        states, verdict, applied = C.create_string_buffer(max(1, 40 * m)), C.create_string_buffer(max(1, m)), _u64()
+        prev = C.create_string_buffer(max(1, 32 * len(flat))) if want_rollback else None
+        if claims is not None:
+            claims = b"".join(claims) if not isinstance(claims, (bytes, bytearray)) else bytes(claims)
+            assert len(claims) == 40 * m
+        self.ctx._ck(self.lib.bzk_state_update_chain(self.h, m, (_u64 * len(d_off))(*d_off), o, lo, _ptr(vals) if vals else None, hs,
+                                                     _ptr(claims) if claims else None, round_versions, states, verdict, C.byref(applied), prev),
+                     "state_update_chain")
+        out = (applied.value, list(verdict.raw[:m]), [states.raw[40 * j:40 * j + 40] for j in range(m)])
+        if want_rollback:
+            return out + ([[prev.raw[32 * i:32 * i + 32] for i in range(d_off[j], d_off[j + 1])] for j in range(m)],)
+        return out
+
+    def update_chain_bincode(self, blobs, target_heights, claims=None, round_versions: int = 0):
+        """the same over m bincode(ZkDeltaPairs) blobs; one that does not decode is refused"""
+        blobs = [bytes(b) for b in blobs]
+        m = len(blobs)
+        b_off = [0]
+        for b in blobs:
+            b_off.append(b_off[-1] + len(b))
+        data = b"".join(blobs) or b"\0"
+        hs = (_u64 * max(1, m))(*[int(h) for h in target_heights])
+        states, verdict, applied = C.create_string_buffer(max(1, 40 * m)), C.create_string_buffer(max(1, m)), _u64()
+        if claims is not None:
+            claims = b"".join(claims) if not isinstance(claims, (bytes, bytearray)) else bytes(claims)
+            assert len(claims) == 40 * m
+        self.ctx._ck(self.lib.bzk_state_update_chain_bincode(self.h, m, _ptr(data), (_u64 * len(b_off))(*b_off), hs, _ptr(claims) if claims else None,
+                                                             round_versions, states, verdict, C.byref(applied)), "state_update_chain_bincode")
+        return applied.value, list(verdict.raw[:m]), [states.raw[40 * j:40 * j + 40] for j in range(m)]
 
     def root(self):
         """-> (state_hash, state_size, height)"""
@@ -1807,6 +1855,25 @@ def l1_tx_updates(txs: bytes, n: int, contract_id: bytes, form: int = L1_FORM_TX
         if st != 0:
             raise BzkError(f"l1_tx_updates: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
         return [tuple(spans[3 * i:3 * i + 3]) for i in range(min(k, found.value))]
+    out = call(0 if cap is None else cap)
+    if cap is None and found.value:
+        out = call(found.value)
+    return found.value, out
+
+
+def l1_tx_deltas(txs: bytes, n: int, contract_id: bytes, form: int = L1_FORM_TX, cap=None):
+    """host only: (found, [(transaction index, offset of the ZkDeltaPairs body, length, source)]) for every UpdateContract of contract_id among
+    n Transaction / TransactionAndDelta records - source 0: the transaction's `delta`, 1: the record's `state_delta`, 2 (length 0): neither;
+    at most cap spans are returned (None: all of them)"""
+    lib = load_library()
+    found = C.c_uint64(0)
+
+    def call(k):
+        spans = (C.c_uint64 * max(4 * k, 1))()
+        st = lib.bzk_l1_tx_deltas(_ptr(txs) if txs else None, len(txs), n, form, _ptr(contract_id), spans, k, C.byref(found))
+        if st != 0:
+            raise BzkError(f"l1_tx_deltas: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+        return [tuple(spans[4 * i:4 * i + 4]) for i in range(min(k, found.value))]
     out = call(0 if cap is None else cap)
     if cap is None and found.value:
         out = call(found.value)

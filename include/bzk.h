@@ -257,6 +257,12 @@ int32_t bzk_contract_updates_check(bzk_ctx* ctx, const bzk_contract_desc* c, con
  * bzk_block_bodies_check's input to bzk_contract_updates_check's. */
 int32_t bzk_l1_tx_updates(const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, const uint8_t contract_id[32], uint64_t* spans_out, uint64_t cap,
                           uint64_t* n_out);
+/* Its sibling for the state step: for every UpdateContract of the given contract, four words - transaction index, offset of the ZkDeltaPairs body
+ * in txs, its length, and its source: 0 = `delta` inside the transaction, 1 = the record's `state_delta` (form TransactionAndDelta, `delta` None),
+ * 2 with length 0 = neither is present (StateNotGiven).  Same parser, same refusals, same cap / n_out rule.  The spans are what
+ * bzk_state_update_chain_bincode takes; its claims are each transaction's last next_state. */
+int32_t bzk_l1_tx_deltas(const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, const uint8_t contract_id[32], uint64_t* spans_out, uint64_t cap,
+                         uint64_t* n_out);
 
 /* ---- K2: dense 4-ary ZkState tree re-hash ----------------------------------------------------
  * Root of `ZkStateModel::List{log4_size, Scalar}` with every leaf present, as
@@ -359,6 +365,38 @@ int32_t bzk_state_get(bzk_state* st, const uint64_t* loc_off, const uint64_t* lo
 int32_t bzk_state_prove(bzk_state* st, const uint64_t* tree_loc, uint64_t tree_loc_len, const uint64_t* indices, uint64_t n,
                         uint8_t* proof_out, uint32_t* log4_size);
 int32_t bzk_state_stats(bzk_state* st, uint64_t* slots, uint64_t* device_bytes, uint64_t* keys);
+
+/* A CHAIN of m deltas in one pass (`update_contract/mod.rs:129-144` per block: apply the transaction's ZkDeltaPairs, then require
+ * root == cont_account.compressed_state).  Exactly this loop: for j = 0 .. m - 1 call bzk_state_update(delta j, target_heights[j]), compare the
+ * 40 bytes of bincode(ZkCompressedState) (hash, then size) with claims[j], stop at the first delta that is refused or does not match; a delta that
+ * stops the loop leaves no trace.  All deltas go through the tree together - one launch per (level, arity) over every (node, time) pair of a
+ * round - and nothing in the value store changes before the roots have been compared.
+ *   delta_off        m + 1 offsets in PAIRS: delta j is pairs delta_off[j] .. delta_off[j + 1] of loc_off / loc / values (as bzk_state_update)
+ *   claims           m x 40 bytes, or NULL: nothing can mismatch
+ *   round_versions   0 = 2^22: whole deltas share a round while their written scalars + hashed nodes stay at most this; a larger delta runs alone
+ *   states_out       m x 40: for an applied and for a mismatching delta the state it produces; zeros from a refused delta onwards
+ *   verdict          m x BZK_CHAIN_*;  *applied = the deltas that are part of the state now.  Afterwards the handle is indistinguishable from
+ *                    one that received the first *applied deltas through bzk_state_update (root, size, height, get, prove, keys)
+ *   prev_values_out  pairs x 32 or NULL: for every pair of an applied delta what that scalar held just before its delta (the per-block rollback
+ *                    of `ZkState::push_delta`); zeros elsewhere
+ * An empty delta moves the height only and repeats the state before it.  BZK_OK whenever the verdicts tell the story: a refused delta is a
+ * verdict, bzk_last_refusal / bzk_last_error name its reason and its index.  BZK_E_ARG for call-level faults only, nothing changed: NULL pointers
+ * with m > 0, offsets that do not ascend.  m = 0 is a no-op.  BZK_E_DEVICE poisons the handle.
+ * _bincode: m bincode(ZkDeltaPairs) blobs back to back, blob j at delta_byte_off[j] .. delta_byte_off[j + 1], read by bzk_state_update_bincode's
+ * decoder; a blob that does not decode is REFUSED.
+ * Measured (DESIGN 3.15, 1 024 pairs per delta at the production depth): ONE delta through this call costs what a bzk_state_update of it costs
+ * (0.8 - 1.3 x across runs) - the same 20 dependent launches, and the versioning costs the host what the fused kernel saves; 16 deltas cost 2.6 x
+ * less than 16 calls, 64 and more 3.1 - 3.2 x less, bounded by the host's planning.  With one or two deltas keep bzk_state_update. */
+#define BZK_CHAIN_APPLIED     0u  /* the delta is part of the state now */
+#define BZK_CHAIN_MISMATCH    1u  /* applied alone it gives another ZkCompressedState than claimed (BlockchainError::InvalidState) */
+#define BZK_CHAIN_REFUSED     2u  /* bzk_state_update would refuse it (locator errors, duplicate, non-canonical value) */
+#define BZK_CHAIN_NOT_REACHED 3u  /* behind the first delta that was not applied */
+int32_t bzk_state_update_chain(bzk_state* st, uint64_t m, const uint64_t* delta_off, const uint64_t* loc_off, const uint64_t* loc,
+                               const uint8_t* values, const uint64_t* target_heights, const uint8_t* claims, uint64_t round_versions,
+                               uint8_t* states_out, uint8_t* verdict, uint64_t* applied, uint8_t* prev_values_out);
+int32_t bzk_state_update_chain_bincode(bzk_state* st, uint64_t m, const uint8_t* deltas, const uint64_t* delta_byte_off,
+                                       const uint64_t* target_heights, const uint8_t* claims, uint64_t round_versions, uint8_t* states_out,
+                                       uint8_t* verdict, uint64_t* applied);
 
 /* ---- K3: radix-2 NTT over Fr -----------------------------------------------------------------
  * bellman 0.14 `EvaluationDomain::{fft, ifft, coset_fft, icoset_fft}` (third-party crate; reached

@@ -500,6 +500,42 @@ impl<'g> DeviceStateManager<'g> {
         }
     }
 
+    /// A chain of deltas in one pass, every root checked (`update_contract/mod.rs:129-144` per block: apply the transaction's `ZkDeltaPairs`, then require
+    /// `root == cont_account.compressed_state`): `update_contract(patches[j], target_heights[j])` for j = 0, 1, .. while each is accepted and gives
+    /// `claims[j]` (None: nothing can mismatch).  Returns how many deltas are part of the state now, the verdict of each (`sys::BZK_CHAIN_APPLIED`, `sys::BZK_CHAIN_MISMATCH`, `sys::BZK_CHAIN_REFUSED`, `sys::BZK_CHAIN_NOT_REACHED`), and the
+    /// state each applied (or mismatching) delta produces.  A refused delta is a verdict, not an error; it and everything behind it leave no trace.
+    pub fn update_contract_chain(&mut self, patches: &[ZkDeltaPairs], target_heights: &[u64], claims: Option<&[ZkCompressedState]>)
+                                 -> Result<(usize, Vec<u8>, Vec<ZkCompressedState>), DeviceStateError> {
+        let m = patches.len();
+        assert!(target_heights.len() == m && claims.map_or(true, |c| c.len() == m), "one height and one claim per delta");
+        let (mut blobs, mut off) = (Vec::new(), vec![0u64]);
+        for p in patches {
+            blobs.extend_from_slice(&bincode::serialize(p).map_err(GpuError::from)?);
+            off.push(blobs.len() as u64);
+        }
+        let mut claim_bytes = Vec::new();
+        for c in claims.unwrap_or(&[]) {
+            claim_bytes.extend_from_slice(&bincode::serialize(c).map_err(GpuError::from)?);
+        }
+        let (mut states, mut verdict, mut applied) = (vec![0u8; 40 * m], vec![0u8; m], 0u64);
+        if blobs.is_empty() {
+            blobs.push(0);
+        }
+        let st = unsafe {
+            sys::bzk_state_update_chain_bincode(self.st, m as u64, blobs.as_ptr(), off.as_ptr(), target_heights.as_ptr(),
+                                                if claims.is_some() { claim_bytes.as_ptr() } else { ptr::null() }, 0, states.as_mut_ptr(),
+                                                verdict.as_mut_ptr(), &mut applied)
+        };
+        if st != sys::BZK_OK {
+            return Err(state_error(self.gpu.0, st));
+        }
+        let mut out = Vec::with_capacity(m);
+        for s in states.chunks_exact(40) {
+            out.push(bincode::deserialize(s).map_err(GpuError::from)?);
+        }
+        Ok((applied as usize, verdict, out))
+    }
+
     /// `root` (:274-284) and `height_of` (:210-216)
     pub fn root(&self) -> Result<(ZkCompressedState, u64), DeviceStateError> {
         let (mut hash, mut size, mut height) = (ZkScalar::default(), 0u64, 0u64);
@@ -900,4 +936,30 @@ pub fn contract_update_spans(bytes: &[u8], n: usize, with_delta: bool, contract_
         spans = vec![0u64; 3 * found as usize];
     }
     Ok(spans.chunks_exact(3).take(found as usize).map(|s| (s[0], s[1], s[2])).collect())
+}
+
+/// Its sibling for the state step: per `UpdateContract` of `contract_id` (transaction index, offset of the `ZkDeltaPairs` body, length, source) -
+/// source 0: the transaction's `delta`, 1: the record's `state_delta`, 2 (length 0): neither (`StateNotGiven`).  The spans re-slice to the input of
+/// `bzk_state_update_chain_bincode`; the claims are each transaction's last `next_state`.
+pub fn contract_delta_spans(bytes: &[u8], n: usize, with_delta: bool, contract_id: ContractId) -> Result<Vec<(u64, u64, u64, u64)>, GpuError> {
+    let id: ZkScalar = contract_id.into();
+    let form: u32 = if with_delta { 1 } else { 0 }; // BZK_L1_FORM_TX_AND_DELTA / BZK_L1_FORM_TX
+    let mut found = 0u64;
+    let mut spans: Vec<u64> = Vec::new();
+    for _ in 0..2 {
+        let st = unsafe {
+            sys::bzk_l1_tx_deltas(bytes.as_ptr(), bytes.len() as u64, n as u64, form, scalars_ptr(std::slice::from_ref(&id)), spans.as_mut_ptr(),
+                                  (spans.len() / 4) as u64, &mut found)
+        };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(ptr::null_mut(), st)?;
+        if spans.len() as u64 >= 4 * found {
+            break;
+        }
+        spans = vec![0u64; 4 * found as usize];
+    }
+    Ok(spans.chunks_exact(4).take(found as usize).map(|s| (s[0], s[1], s[2], s[3])).collect())
 }

@@ -207,6 +207,7 @@ __device__ __forceinline__ void lds_st(uint32_t* tile, uint32_t idx, const Fr29&
     for (int i = 0; i < 9; ++i) p[i] = v.l[i];
 }
 
+// (restated in tests/host/ntt_pass_check.hip, first_load: the CPU replay that asserts the bounds - change both)
 __device__ __forceinline__ Fr29 ntt_first_load(const NttPass& a, uint64_t addr, const Fr29& c_in) {
     const Fr29 x = fr29::repack_from32(((const Fr*)a.src)[addr]);
     if (a.first_mode == FIRST_RAW) return x;
@@ -273,6 +274,9 @@ __global__ void __launch_bounds__(256, OCC) ntt_pass_kernel(NttPass a) {
     // Butterfly stages, two per LDS round trip (radix 4 in registers: half the barriers and half the LDS traffic of one stage per
     // round).  Stage 0 has the single twiddle w^0 = one and its operands are fresh products or raw inputs below 2^256 (what sub3
     // needs), so it multiplies nothing.  An odd stage count starts with that lone multiplication-free stage.
+    // The arithmetic of both loops (not their indexing) is restated in tests/host/ntt_pass_check.hip, lone_stage and round4: the CPU replay that walks
+    // whole transforms through it with ka * kb <= 70, sub3's limb condition, the 2^256 of repack_to32 and the k <= 35 of from29_scaled asserted on
+    // exact integers - change both.
     int s0 = 0;
     if (b & 1) {
         for (uint32_t q = threadIdx.x; q < tile_n / 2; q += blockDim.x) {
@@ -408,6 +412,7 @@ static int32_t ntt_tables(bzk_ctx* ctx, int log_n, NttTables** out) {
     const uint64_t n = (uint64_t)1 << log_n;
     NttTables* T = new NttTables();
     const int bm = ntt_bmax();
+    // the digit split (restated in tests/host/ntt_pass_check.hip, digit_split - change both)
     if (log_n <= bm) { T->nb = 1; T->b[0] = log_n; }
     else if (log_n <= 2 * bm) { T->nb = 2; T->b[0] = (log_n + 1) / 2; T->b[1] = log_n / 2; }
     else {

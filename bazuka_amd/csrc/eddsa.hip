@@ -225,7 +225,7 @@ __global__ void __launch_bounds__(256) sha3_merkle_roots_kernel(const uint32_t* 
     }
 }
 
-static int32_t eddsa_table_dev(bzk_ctx* ctx, const Fr29** out) {
+int32_t eddsa_table_dev(bzk_ctx* ctx, const Fr29** out) {
     if (!ctx->eddsa_tab) {
         std::vector<Fr29> tab;
         eddsa::base_table_build(tab);

@@ -548,7 +548,7 @@ inline ZkScalar mpn_work_commitment(const uint8_t prover_pub[32], uint64_t rewar
 // and no field arithmetic, so that the device paths (eddsa.hip mpn_*_verify_run) leave none on the host.
 struct TxParsed {
     std::vector<uint8_t> src_x, dst_x, src_odd, dst_odd, tok, sig;
-    std::vector<uint64_t> nums;
+    std::vector<uint64_t> nums, rec_end;  // rec_end n: where record i ends in the input (its signature is the 96 bytes before)
     TxSoA soa() const { return {src_x.data(), dst_x.data(), src_odd.data(), dst_odd.data(), tok.data(), nums.data(), sig.data()}; }
 };
 // ContractId as the scalar the circuits use, copied as bytes (Null = 0, Ziesha = 1: constants)
@@ -569,7 +569,7 @@ inline bool parse_txs(const uint8_t* txs, uint64_t len, uint64_t n, TxParsed& P,
         return false;
     }
     P.src_x.resize(n * 32); P.dst_x.resize(n * 32); P.src_odd.resize(n); P.dst_odd.resize(n);
-    P.tok.resize(n * 64); P.sig.resize(n * 96); P.nums.resize(n * 3);
+    P.tok.resize(n * 64); P.sig.resize(n * 96); P.nums.resize(n * 3); P.rec_end.resize(n);
     BinReader r(txs, (size_t)len);
     for (uint64_t i = 0; i < n && r.ok; ++i) {
         P.nums[3 * i] = r.u32("MpnTransaction.nonce");
@@ -582,6 +582,7 @@ inline bool parse_txs(const uint8_t* txs, uint64_t len, uint64_t n, TxParsed& P,
         parse_contract_id(r, &P.tok[64 * i + 32]);
         P.nums[3 * i + 2] = r.u64("Amount");
         if (const uint8_t* b = r.bytes(96, "Signature")) memcpy(&P.sig[96 * i], b, 96);
+        P.rec_end[i] = r.pos;
         if (!r.ok) r.err = "record " + std::to_string(i) + ": " + r.err;
     }
     if (r.ok && r.pos != len) r.fail("bytes after the last record");

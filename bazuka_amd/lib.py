@@ -53,6 +53,11 @@ SIGNATURES = {
     "bzk_jubjub_verify_batch_compressed": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_jubjub_verify_batch_compressed_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_mpn_tx_verify_batch": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp]),
+    "bzk_jubjub_keys_batch": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "bzk_jubjub_keys_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "bzk_jubjub_sign_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_jubjub_sign_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_mpn_txs_sign": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "bzk_sha3_256_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "bzk_sha3_256_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "bzk_mpn_withdraw_verify_batch": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp]),
@@ -423,6 +428,20 @@ class Bzk:
                  "jubjub_verify_batch_compressed")
         return out.raw[:n]
 
+    def jubjub_keys_batch(self, seeds) -> bytes:
+        """JubJub::generate_keys for each of the byte strings in seeds on the device: n x 128 (pub.x | pub.y | randomness | scalar)"""
+        return _jubjub_keys_batch(self.h, seeds)
+
+    def jubjub_sign_batch(self, keys: bytes, msg: bytes):
+        """n = len(msg) / 32 rows (keys n x 128 as jubjub_keys_batch writes them): (signatures n x 96 = r.x | r.y | s, verdict bytes); a row with
+        a field that is not a residue's limbs gets 96 zero bytes and verdict 0"""
+        return _jubjub_sign_batch(self.h, keys, msg)
+
+    def mpn_txs_sign(self, keys: bytes, txs: bytes, n: int, want_hash: bool = True):
+        """n consecutive bincode(MpnTransaction) and n keys (n x 128): (the records with each signed one's signature replaced, verdict bytes,
+        tx hashes n x 32 or None); a malformed record raises"""
+        return _mpn_txs_sign(self.h, keys, txs, n, want_hash)
+
     def mpn_tx_verify_batch(self, txs: bytes, n: int, want_hash: bool = True):
         """n consecutive bincode(MpnTransaction): (verdict bytes, tx hashes n x 32 or None); a malformed record raises"""
         return _mpn_tx_verify_batch(self.h, txs, n, want_hash)
@@ -530,6 +549,14 @@ class Bzk:
     def jubjub_verify_batch_compressed_dev(self, pk_x, pk_odd, msg, sig, n: int, ok):
         self._ck(self.lib.bzk_jubjub_verify_batch_compressed_dev(self.h, _ptr(pk_x), _ptr(pk_odd), _ptr(msg), _ptr(sig), n, _ptr(ok)),
                  "jubjub_verify_batch_compressed_dev")
+
+    def jubjub_keys_batch_dev(self, seeds, off, n: int, keys_out):
+        """device tensors: seeds (bytes), off (n + 1 uint64 offsets from 0), keys_out n x 128 bytes; enqueues on the context's stream"""
+        self._ck(self.lib.bzk_jubjub_keys_batch_dev(self.h, _ptr(seeds), _ptr(off), n, _ptr(keys_out)), "jubjub_keys_batch_dev")
+
+    def jubjub_sign_batch_dev(self, keys, msg, n: int, sig_out, ok):
+        """device tensors: keys n x 128, msg n x 32, sig_out n x 96, ok n bytes; enqueues on the context's stream and leaves keys alone"""
+        self._ck(self.lib.bzk_jubjub_sign_batch_dev(self.h, _ptr(keys), _ptr(msg), n, _ptr(sig_out), _ptr(ok)), "jubjub_sign_batch_dev")
 
     def sha3_256_batch_dev(self, data, off, n: int, digest=None, scalar=None):
         """device buffers: data bytes, off n + 1 u64; digest n x 32 and / or scalar n x 32 are written in stream order"""
@@ -1566,6 +1593,56 @@ def host_jubjub_decompress(x: bytes, odd: bool):
     if r < 0:
         raise BzkError("jubjub_decompress: bad argument")
     return out.raw if r else None
+
+
+JUBJUB_SIGN_ROUND = 1 << 16  # rows a host-pointer signing or key call stages per round (sign.hip SIGN_ROUND)
+
+
+def _jubjub_keys_batch(ctx_handle, seeds) -> bytes:
+    n = len(seeds)
+    off = (_u64 * (n + 1))()
+    for i, m in enumerate(seeds):
+        off[i + 1] = off[i] + len(m)
+    data = b"".join(seeds)
+    out = C.create_string_buffer(max(128 * n, 1))
+    _st(load_library().bzk_jubjub_keys_batch(ctx_handle, _ptr(data) if data else _ptr(b"\0"), off, n, out), "jubjub_keys_batch")
+    return out.raw[: 128 * n]
+
+
+def _jubjub_sign_batch(ctx_handle, keys: bytes, msg: bytes):
+    n = len(msg) // 32
+    if len(keys) != 128 * n or len(msg) != 32 * n:
+        raise BzkError("jubjub_sign_batch: keys and msg describe different counts")
+    sig, ok = C.create_string_buffer(max(96 * n, 1)), C.create_string_buffer(max(n, 1))
+    _st(load_library().bzk_jubjub_sign_batch(ctx_handle, _ptr(keys), _ptr(msg), n, sig, ok), "jubjub_sign_batch")
+    return sig.raw[: 96 * n], ok.raw[:n]
+
+
+def _mpn_txs_sign(ctx_handle, keys: bytes, txs: bytes, n: int, want_hash: bool):
+    lib = load_library()
+    if len(keys) != 128 * n:
+        raise BzkError("mpn_txs_sign: keys is not n x 128 bytes")
+    out, ok = C.create_string_buffer(max(len(txs), 1)), C.create_string_buffer(max(n, 1))
+    hashes = C.create_string_buffer(max(32 * n, 1)) if want_hash else None
+    st = lib.bzk_mpn_txs_sign(ctx_handle, _ptr(keys), _ptr(txs), len(txs), n, out, ok, hashes)
+    if st != 0:
+        raise BzkError(f"mpn_txs_sign: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+    return out.raw[: len(txs)], ok.raw[:n], (hashes.raw[: 32 * n] if want_hash else None)
+
+
+def host_jubjub_keys_batch(seeds) -> bytes:
+    """Bzk.jubjub_keys_batch without a device: the same per-lane code on host threads"""
+    return _jubjub_keys_batch(None, seeds)
+
+
+def host_jubjub_sign_batch(keys: bytes, msg: bytes):
+    """Bzk.jubjub_sign_batch without a device: the same per-lane code on host threads"""
+    return _jubjub_sign_batch(None, keys, msg)
+
+
+def host_mpn_txs_sign(keys: bytes, txs: bytes, n: int, want_hash: bool = True):
+    """Bzk.mpn_txs_sign without a device: the same per-lane code on host threads"""
+    return _mpn_txs_sign(None, keys, txs, n, want_hash)
 
 
 def _mpn_tx_verify_batch(ctx_handle, txs: bytes, n: int, want_hash: bool):

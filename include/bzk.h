@@ -131,6 +131,33 @@ int32_t bzk_jubjub_verify_batch_compressed_dev(bzk_ctx* ctx, const void* pk_x_de
  * checked on the device, in rounds of 2^16 transactions; synchronises.  ctx = NULL: the same on host threads (bzk_host_default_threads). */
 int32_t bzk_mpn_tx_verify_batch(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* ok, uint8_t* hash_out);
 
+/* ---- batched EdDSA key derivation and signing ------------------------------------------------------------
+ * JubJub::generate_keys and JubJub::sign (src/crypto/jubjub/mod.rs:112-150) for n independent rows, one lane each.  Signing is deterministic:
+ * r = Poseidon(randomness, msg), R = r BASE, h = Poseidon(R.x, R.y, pk.x, pk.y, msg), s = (r + h a) mod ORDER, so the bytes equal
+ * bzk_host_jubjub_sign's and bzk_host_jubjub_keys'.
+ * keys: seed i = seeds[off[i] .. off[i+1]) (off: n + 1 non-decreasing entries from 0, as bzk_sha3_256_batch takes its messages), keys_out
+ * n x 128 (pub.x | pub.y | randomness | scalar).
+ * sign: keys n x 128 in that layout, msg n x 32, sig_out n x 96 (r.x | r.y | s), ok n bytes.  pub is taken as given (not checked against
+ * scalar BASE).  A key field or message that is not the limbs of a residue gives ok = 0 and 96 zero bytes for its row, not an error
+ * (bzk_host_jubjub_sign does not validate).  n = 0 is a no-op.
+ * The host forms stage through the context's workspace in rounds of 2^16 rows, synchronise, and overwrite the workspace regions that held
+ * key bytes before they return; the _dev forms enqueue on the context's stream, trust off and leave the caller's buffers alone.  ctx = NULL
+ * (host forms): the same per-lane code on host threads (bzk_host_default_threads).  The fixed-base walk indexes a table by nibbles of the
+ * secret nonce: fixed-flow, not address-independent - a throughput signer, not a hardened one. */
+int32_t bzk_jubjub_keys_batch(bzk_ctx* ctx, const uint8_t* seeds, const uint64_t* off, uint64_t n, uint8_t* keys_out);
+int32_t bzk_jubjub_keys_batch_dev(bzk_ctx* ctx, const void* seeds_dev, const void* off_dev, uint64_t n, void* keys_out_dev);
+int32_t bzk_jubjub_sign_batch(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* msg, uint64_t n, uint8_t* sig_out, uint8_t* ok);
+int32_t bzk_jubjub_sign_batch_dev(bzk_ctx* ctx, const void* keys_dev, const void* msg_dev, uint64_t n, void* sig_out_dev, void* ok_dev);
+/* TxBuilder::create_mpn_transaction's signing step for n transactions given as n consecutive bincode(MpnTransaction) (bzk_mpn_tx_verify_batch's
+ * input; the 96 signature bytes of the input are ignored) and n keys (n x 128).  The host only parses; per record the device decompresses
+ * dst, computes tx.hash(), checks that src is the compression of the key's pub, and signs.  txs_out (len bytes) = the input with each signed
+ * record's signature replaced; ok[i] = 0 and record i copied unchanged where dst does not decompress, a token id is not a residue's limbs,
+ * src does not match the key or a key field is not a residue's limbs.  hash_out (n x 32, may be NULL) = tx.hash(), zeros where it could not
+ * be computed.  BZK_E_ARG with bzk_mpn_work_last_error() set when the bytes are not n well-formed records.  Rounds of 2^16 records;
+ * synchronises; the staged key bytes are overwritten.  ctx = NULL: the same on host threads. */
+int32_t bzk_mpn_txs_sign(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* txs_out, uint8_t* ok,
+                         uint8_t* hash_out);
+
 /* ---- batched SHA3-256 and hash_to_scalar -----------------------------------------------------------------
  * n messages: message i = data[off[i] .. off[i+1]), off has n + 1 entries, off[0] = 0, non-decreasing.  One lane per message, which loops
  * over as many 136-byte blocks as its own length needs (FIPS 202: rate 136, suffix 0x06, final 0x80).

@@ -8,6 +8,9 @@
 //! Each public item names the reference interface it stands beside (paths relative to ziesha-network/bazuka v0.19.20):
 //!   * `GpuPoseidonHasher`      - `impl ZkHasher` (src/zk/mod.rs:152-155, 496-511) + the BULK path `hash_batch`
 //!   * `Gpu::jubjub_verify_batch` - `JubJub::<ZkHasher>::verify` (src/crypto/jubjub/mod.rs:151-167) for many signatures at once
+//!   * `Gpu::jubjub_keys_batch` / `Gpu::jubjub_sign_batch` - `JubJub::generate_keys` and `JubJub::sign` (src/crypto/jubjub/mod.rs:112-150) for many
+//!                                seeds / (key, message) pairs at once; `Gpu::mpn_txs_sign` - the signing step of
+//!                                `TxBuilder::create_mpn_transaction` (src/wallet/tx_builder.rs:287-306) for many transactions at once
 //!   * `Gpu::mpn_tx_verify_batch` - `MpnTransaction::verify_signature` (src/zk/mod.rs:610-627) for many wire-form transactions at once
 //!   * `Gpu::mpn_withdraw_verify_batch` - `MpnWithdraw::verify_signature` and `verify_calldata` (src/core/transaction.rs:177-189) for many
 //!                                wire-form withdrawals at once, with `payment.fingerprint()` (:204-211, a SHA3-256) taken on the device
@@ -41,7 +44,7 @@
 //! Layout assumptions (already relied upon by the reference's own `transmute`s, src/zk/groth16/mod.rs:7-17): `ZkScalar` is
 //! `[u64; 4]` little-endian Montgomery limbs; bincode 1.3 with default options; `Groth16Proof` = 97 + 193 + 97 bytes under bincode.
 use bazuka::core::{Address, Block, ContractId, ContractUpdate, MpnDeposit, MpnWithdraw, Transaction};
-use bazuka::crypto::jubjub::{PublicKey, Signature};
+use bazuka::crypto::jubjub::{PointAffine, PrivateKey, PublicKey, Signature};
 use bazuka::mpn::MpnWork;
 use bazuka::zk::groth16::Groth16Proof;
 use bazuka::zk::{
@@ -130,6 +133,77 @@ impl Gpu {
             return Err(GpuError::Status(st, why));
         }
         check(self.0, st)?;
+        Ok(ok.into_iter().map(|b| b != 0).collect())
+    }
+
+    /// Bulk `JubJub::<PoseidonHasher>::generate_keys(seed)` (src/crypto/jubjub/mod.rs:112-124): both SHA3-256 hashes and `scalar BASE` run on the
+    /// device, one lane per seed.  The staged seeds and keys are overwritten in the device workspace before the call returns.
+    pub fn jubjub_keys_batch(&self, seeds: &[&[u8]]) -> Result<Vec<(PublicKey, PrivateKey)>, GpuError> {
+        let mut off = Vec::with_capacity(seeds.len() + 1);
+        let mut data = Vec::new();
+        off.push(0u64);
+        for m in seeds {
+            data.extend_from_slice(m);
+            off.push(data.len() as u64);
+        }
+        let mut out = vec![ZkScalar::default(); 4 * seeds.len()];
+        check(self.0, unsafe { sys::bzk_jubjub_keys_batch(self.0, data.as_ptr(), off.as_ptr(), seeds.len() as u64, out.as_mut_ptr() as *mut u8) })?;
+        Ok(out
+            .chunks_exact(4)
+            .map(|k| {
+                let point = PointAffine(k[0], k[1]);
+                (PublicKey(point.compress()), PrivateKey { public_key: point, randomness: k[2], scalar: k[3] })
+            })
+            .collect())
+    }
+
+    /// Bulk `JubJub::<PoseidonHasher>::sign(sk, msg)` (src/crypto/jubjub/mod.rs:125-150): deterministic, so the signatures are the reference's own.
+    /// A throughput signer: the fixed-base walk is fixed-flow but indexes a table by nibbles of the nonce.
+    pub fn jubjub_sign_batch(&self, items: &[(PrivateKey, ZkScalar)]) -> Result<Vec<Signature>, GpuError> {
+        let n = items.len();
+        let (mut keys, mut msg) = (Vec::with_capacity(4 * n), Vec::with_capacity(n));
+        for (k, m) in items {
+            keys.extend_from_slice(&[k.public_key.0, k.public_key.1, k.randomness, k.scalar]);
+            msg.push(*m);
+        }
+        let mut sig = vec![ZkScalar::default(); 3 * n];
+        let mut ok = vec![0u8; n];
+        check(self.0, unsafe {
+            sys::bzk_jubjub_sign_batch(self.0, scalars_ptr(&keys), scalars_ptr(&msg), n as u64, sig.as_mut_ptr() as *mut u8, ok.as_mut_ptr())
+        })?;
+        Ok(sig.chunks_exact(3).map(|s| Signature { r: PointAffine(s[0], s[1]), s: s[2] }).collect())
+    }
+
+    /// The signing step of `TxBuilder::create_mpn_transaction` for many transactions (`tx.sign(&key)`, src/wallet/tx_builder.rs:304: `sig = JubJub::sign(key, tx.hash())`), with the hash, the
+    /// decompression of `dst` and the check that `src_pub_key` belongs to the key on the device.  Returns, per transaction, whether it was signed
+    /// (`false`: `dst` does not decompress or `src_pub_key` is not the key's; `sig` is left as it was).
+    pub fn mpn_txs_sign(&self, keys: &[PrivateKey], txs: &mut [MpnTransaction]) -> Result<Vec<bool>, GpuError> {
+        assert!(keys.len() == txs.len());
+        let mut flat = Vec::with_capacity(4 * keys.len());
+        for k in keys {
+            flat.extend_from_slice(&[k.public_key.0, k.public_key.1, k.randomness, k.scalar]);
+        }
+        let mut bytes = Vec::with_capacity(254 * txs.len());
+        let mut ends = Vec::with_capacity(txs.len());
+        for tx in txs.iter() {
+            bytes.extend_from_slice(&bincode::serialize(tx)?);
+            ends.push(bytes.len());
+        }
+        let mut out = vec![0u8; bytes.len()];
+        let mut ok = vec![0u8; txs.len()];
+        let st = unsafe {
+            sys::bzk_mpn_txs_sign(self.0, scalars_ptr(&flat), bytes.as_ptr(), bytes.len() as u64, txs.len() as u64, out.as_mut_ptr(), ok.as_mut_ptr(), ptr::null_mut())
+        };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(self.0, st)?;
+        for (i, tx) in txs.iter_mut().enumerate() {
+            if ok[i] != 0 {
+                tx.sig = bincode::deserialize(&out[ends[i] - 96..ends[i]])?;
+            }
+        }
         Ok(ok.into_iter().map(|b| b != 0).collect())
     }
 

@@ -1,7 +1,8 @@
 // Wire-form admission: bincode records as the node receives them in, verdicts out, accepted ones queued into a world.  This file holds the
 // extern "C" entry points of every wire-form path and, for the three MPN record kinds, the dispatcher that runs a parsed batch on the device
 // (eddsa.hip mpn_*_verify_run) or - the same checks - on host threads.  The parsers are host_bincode.h's (structure only: byte ranges, integers,
-// tags); the kernels and their orchestration are eddsa.hip's and updates.hip's.  No kernel lives here.
+// tags); the kernels and their orchestration are eddsa.hip's, updates.hip's and ed_sign.hip's.  No kernel lives here.
+#include "bzk_ed25519_sign.h"  // the signing stage of bzk_mpn_deposits_sign / bzk_l1_txs_sign (ed_sign.hip)
 #include "bzk_internal.h"
 #include "host_bincode.h"
 #include "host_mpn_world.h"  // struct bzk_mpn (the queues the push entry points fill), g_work_error
@@ -164,6 +165,34 @@ int32_t deposit_verify_all(bzk_ctx* ctx, int threads, const DpParsed& P, uint64_
         }
     });
     return BZK_OK;
+}
+// where signed record i is written: head bytes of the input, the tag, the optional length prefix, the signature, then the input from tail_at on
+struct SignedSplice {
+    uint64_t head_end, tail_at;  // in the input: the tag's position, and the first byte after the input's own signature field
+};
+// out_len, and with out set the records themselves: record i as it stands where ok[i] = 0, else spliced.  tag4: the tag is a u32 (an enum's), not a
+// byte (an Option's)
+uint64_t write_signed(const uint8_t* txs, const uint64_t* rec_off, const std::vector<SignedSplice>& at, const uint8_t* ok, const uint8_t* sig, uint64_t n,
+                      bool tag4, uint32_t flags, uint8_t* out) {
+    uint64_t pos = 0;
+    auto put = [&](const void* p, uint64_t k) {
+        if (out && k) memcpy(out + pos, p, k);
+        pos += k;
+    };
+    for (uint64_t i = 0; i < n; ++i) {
+        if (!ok[i]) {
+            put(txs + rec_off[i], rec_off[i + 1] - rec_off[i]);
+            continue;
+        }
+        const uint8_t tag[4] = {1, 0, 0, 0};
+        const uint64_t len64 = 64;
+        put(txs + rec_off[i], at[i].head_end - rec_off[i]);
+        put(tag, tag4 ? 4 : 1);
+        if (flags & BZK_WORK_SIG_LEN_PREFIXED) put(&len64, 8);
+        put(sig + 64 * i, 64);
+        put(txs + at[i].tail_at, rec_off[i + 1] - at[i].tail_at);
+    }
+    return pos;
 }
 }  // namespace
 
@@ -348,6 +377,71 @@ int32_t bzk_block_bodies_check(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, c
         if (!parse_l1_txs(txs, len, n, false, g_wire_flags.load(), P, g_work_error)) return BZK_E_ARG;
         if (ctx) return l1_check_run(ctx, P.soa(), n, count, m, tx_ok_out, hash_out, sig_ok_out, root_out);
         return l1_check_host(host_default_threads(), P.soa(), n, count, m, tx_ok_out, hash_out, sig_ok_out, root_out);
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The producers of the two Ed25519-signed record kinds: `TxBuilder::sign_deposit` and `TxBuilder::sign_tx` (src/wallet/tx_builder.rs:63-70) for
+// n records and n keys.  The parsers, and so the refusals, are the verify entries'; the signing is ed_sign.hip's, on the device or on host
+// threads; this file writes the records back with their signature filled in, spelled as bzk_mpn_set_wire_flags says.
+// ------------------------------------------------------------------------------------------------
+int32_t bzk_mpn_deposits_sign(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* sig_out, uint8_t* ok,
+                              uint8_t* txs_out, uint64_t cap, uint64_t* out_len) {
+    if (n && (!keys || !txs || !sig_out || !ok)) return BZK_E_ARG;
+    if (out_len) *out_len = 0;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        const uint32_t flags = g_wire_flags.load();
+        DpParsed P;
+        if (!parse_deposits(txs, len, n, flags, P, g_work_error)) return BZK_E_ARG;
+        std::vector<uint8_t> sig(n * 64), verdict(n);
+        BZK_TRY(mpn_deposits_sign_all(ctx, host_default_threads(), P.soa(), keys, n, sig.data(), verdict.data()));
+        std::vector<SignedSplice> at(n);
+        for (uint64_t i = 0; i < n; ++i) at[i] = {P.pay_off[i] + P.tag_off[i], P.pay_off[i] + P.pay_len[i]};
+        const uint64_t need = write_signed(txs, P.rec_off.data(), at, verdict.data(), sig.data(), n, false, flags, nullptr);
+        if (out_len) *out_len = need;
+        if (txs_out && cap < need) {
+            g_work_error = "txs_out holds " + std::to_string(cap) + " bytes, the signed records need " + std::to_string(need);
+            return BZK_E_ARG;
+        }
+        memcpy(sig_out, sig.data(), n * 64);
+        memcpy(ok, verdict.data(), n);
+        if (txs_out) write_signed(txs, P.rec_off.data(), at, verdict.data(), sig.data(), n, false, flags, txs_out);
+        return BZK_OK;
+    } catch (const std::bad_alloc&) {
+        return BZK_E_ALLOC;
+    }
+}
+
+int32_t bzk_l1_txs_sign(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, uint8_t* sig_out, uint8_t* ok,
+                        uint8_t* hash_out, uint8_t* txs_out, uint64_t cap, uint64_t* out_len) {
+    if (form > BZK_L1_FORM_TX_AND_DELTA || (n && (!keys || !txs || !sig_out || !ok))) return BZK_E_ARG;
+    if (out_len) *out_len = 0;
+    if (n == 0 && len == 0) return BZK_OK;
+    try {
+        const uint32_t flags = g_wire_flags.load();
+        L1Parsed P;
+        if (!parse_l1_txs(txs, len, n, form == BZK_L1_FORM_TX_AND_DELTA, flags, P, g_work_error)) return BZK_E_ARG;
+        std::vector<uint8_t> sig(n * 64), verdict(n), hash(hash_out ? n * 32 : 0);
+        BZK_TRY(l1_txs_sign_all(ctx, host_default_threads(), P.soa(), keys, n, sig.data(), verdict.data(), hash_out ? hash.data() : nullptr));
+        std::vector<SignedSplice> at(n);
+        for (uint64_t i = 0; i < n; ++i) {
+            const l1::L1Rec& r = P.rec[i];
+            at[i] = {P.rec_off[i] + r.sig_tag, P.rec_off[i] + ((r.flags & l1::SIGNED) ? r.sig_off + 64 : r.sig_tag + 4)};
+        }
+        const uint64_t need = write_signed(txs, P.rec_off.data(), at, verdict.data(), sig.data(), n, true, flags, nullptr);
+        if (out_len) *out_len = need;
+        if (txs_out && cap < need) {
+            g_work_error = "txs_out holds " + std::to_string(cap) + " bytes, the signed records need " + std::to_string(need);
+            return BZK_E_ARG;
+        }
+        memcpy(sig_out, sig.data(), n * 64);
+        memcpy(ok, verdict.data(), n);
+        if (hash_out) memcpy(hash_out, hash.data(), n * 32);
+        if (txs_out) write_signed(txs, P.rec_off.data(), at, verdict.data(), sig.data(), n, true, flags, txs_out);
+        return BZK_OK;
     } catch (const std::bad_alloc&) {
         return BZK_E_ALLOC;
     }

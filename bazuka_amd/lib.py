@@ -68,6 +68,12 @@ SIGNATURES = {
     "bzk_mpn_deposit_verify_batch": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "bzk_mpn_set_wire_flags": (_i32, [C.c_uint32]),
     "bzk_l1_tx_verify_batch": (_i32, [_vp, _vp, _u64, _u64, C.c_uint32, _vp, _vp]),
+    "bzk_ed25519_keys_batch": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "bzk_ed25519_keys_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "bzk_ed25519_sign_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_ed25519_sign_batch_dev": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_mpn_deposits_sign": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _u64, _vp]),
+    "bzk_l1_txs_sign": (_i32, [_vp, _vp, _vp, _u64, _u64, C.c_uint32, _vp, _vp, _vp, _vp, _u64, _vp]),
     "bzk_sha3_merkle_roots": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "bzk_sha3_merkle_roots_dev": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
     "bzk_block_bodies_check": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
@@ -178,6 +184,8 @@ SIGNATURES = {
     "bzk_host_sha3_256": (_i32, [_vp, _u64, _vp]),
     "bzk_host_sha512": (_i32, [_vp, _u64, _vp]),
     "bzk_host_ed25519_verify": (_i32, [_vp, _vp, _u64, _vp]),
+    "bzk_host_ed25519_keys": (_i32, [_vp, _u64, _vp]),
+    "bzk_host_ed25519_sign": (_i32, [_vp, _vp, _u64, _vp]),
     "bzk_host_jubjub_keys": (_i32, [_vp, _u32, _vp]),
     "bzk_host_jubjub_sign": (_i32, [_vp, _vp, _vp]),
     "bzk_host_jubjub_verify": (_i32, [_vp, _vp, _vp]),
@@ -485,6 +493,24 @@ class Bzk:
         n x 64 or None); a malformed record raises"""
         return _mpn_deposit_verify_batch(self.h, txs, n, want_address)
 
+    def ed25519_keys_batch(self, seeds) -> bytes:
+        """Ed25519::generate_keys for each of the byte strings in seeds on the device: n x 64 (secret | public)"""
+        return _ed25519_keys_batch(self.h, seeds)
+
+    def ed25519_sign_batch(self, keys: bytes, msgs) -> bytes:
+        """len(msgs) rows (keys n x 64 as ed25519_keys_batch writes them): the signatures, n x 64 = R | s"""
+        return _ed25519_sign_batch(self.h, keys, msgs)
+
+    def mpn_deposits_sign(self, keys: bytes, txs: bytes, n: int, want_txs: bool = True):
+        """n consecutive bincode(MpnDeposit) and n keys (n x 64): (signatures n x 64, verdict bytes, the records with Some(sig) filled in or
+        None); a record whose payment.src is not its key's public half keeps verdict 0, a zero signature and its bytes; a malformed record raises"""
+        return _mpn_deposits_sign(self.h, keys, txs, n, want_txs)
+
+    def l1_txs_sign(self, keys: bytes, txs: bytes, n: int, form: int = L1_FORM_TX, want_hash: bool = True, want_txs: bool = True):
+        """n consecutive bincode(Transaction) / bincode(TransactionAndDelta) and n keys (n x 64): (signatures n x 64, verdict bytes, hashes
+        n x 32 or None, the records with Signature::Signed(sig) or None); src None or another key's: verdict 0; a malformed record raises"""
+        return _l1_txs_sign(self.h, keys, txs, n, form, want_hash, want_txs)
+
     def l1_tx_verify_batch(self, txs: bytes, n: int, form: int = L1_FORM_TX, want_hash: bool = True):
         """n consecutive bincode(Transaction) (form L1_FORM_TX) or bincode(TransactionAndDelta) (L1_FORM_TX_AND_DELTA): (verdict bytes of
         Transaction::verify_signature, Transaction::hash n x 32 or None); a malformed record raises"""
@@ -557,6 +583,15 @@ class Bzk:
     def jubjub_sign_batch_dev(self, keys, msg, n: int, sig_out, ok):
         """device tensors: keys n x 128, msg n x 32, sig_out n x 96, ok n bytes; enqueues on the context's stream and leaves keys alone"""
         self._ck(self.lib.bzk_jubjub_sign_batch_dev(self.h, _ptr(keys), _ptr(msg), n, _ptr(sig_out), _ptr(ok)), "jubjub_sign_batch_dev")
+
+    def ed25519_keys_batch_dev(self, seeds, off, n: int, keys_out):
+        """device tensors: seeds (bytes), off (n + 1 uint64 offsets from 0), keys_out n x 64 bytes; enqueues on the context's stream"""
+        self._ck(self.lib.bzk_ed25519_keys_batch_dev(self.h, _ptr(seeds), _ptr(off), n, _ptr(keys_out)), "ed25519_keys_batch_dev")
+
+    def ed25519_sign_batch_dev(self, keys, msg, off, n: int, sig_out):
+        """device tensors: keys n x 64, msg (bytes), off (n + 1 uint64 offsets from 0), sig_out n x 64; enqueues on the context's stream and
+        leaves keys and msg alone"""
+        self._ck(self.lib.bzk_ed25519_sign_batch_dev(self.h, _ptr(keys), _ptr(msg), _ptr(off), n, _ptr(sig_out)), "ed25519_sign_batch_dev")
 
     def sha3_256_batch_dev(self, data, off, n: int, digest=None, scalar=None):
         """device buffers: data bytes, off n + 1 u64; digest n x 32 and / or scalar n x 32 are written in stream order"""
@@ -1709,6 +1744,94 @@ def _ed25519_verify_batch(ctx_handle, pks: bytes, msgs, sigs: bytes) -> bytes:
 def host_ed25519_verify_batch(pks: bytes, msgs, sigs: bytes) -> bytes:
     """Bzk.ed25519_verify_batch without a device: the same per-lane code on host threads"""
     return _ed25519_verify_batch(None, pks, msgs, sigs)
+
+
+ED25519_SIGN_ROUND = 1 << 16  # rows a host-pointer Ed25519 signing or key call stages per round (bzk_ed25519_sign.h ED25519_SIGN_ROUND)
+
+
+def _ed25519_keys_batch(ctx_handle, seeds) -> bytes:
+    n = len(seeds)
+    off, data = _offsets(seeds)
+    out = C.create_string_buffer(max(64 * n, 1))
+    _st(load_library().bzk_ed25519_keys_batch(ctx_handle, _ptr(data), off, n, out), "ed25519_keys_batch")
+    return out.raw[: 64 * n]
+
+
+def _ed25519_sign_batch(ctx_handle, keys: bytes, msgs) -> bytes:
+    n = len(msgs)
+    if len(keys) != 64 * n:
+        raise BzkError("ed25519_sign_batch: keys must hold 64 bytes per message")
+    off, data = _offsets(msgs)
+    sig = C.create_string_buffer(max(64 * n, 1))
+    _st(load_library().bzk_ed25519_sign_batch(ctx_handle, _ptr(keys) if n else None, _ptr(data), off, n, sig), "ed25519_sign_batch")
+    return sig.raw[: 64 * n]
+
+
+def host_ed25519_keys_batch(seeds) -> bytes:
+    """Bzk.ed25519_keys_batch without a device: the same per-lane code on host threads"""
+    return _ed25519_keys_batch(None, seeds)
+
+
+def host_ed25519_sign_batch(keys: bytes, msgs) -> bytes:
+    """Bzk.ed25519_sign_batch without a device: the same per-lane code on host threads"""
+    return _ed25519_sign_batch(None, keys, msgs)
+
+
+def host_ed25519_keys(seed: bytes) -> bytes:
+    """Ed25519::generate_keys(seed) on the host: secret | public"""
+    out = C.create_string_buffer(64)
+    _st(load_library().bzk_host_ed25519_keys(_ptr(seed) if seed else None, len(seed), out), "host_ed25519_keys")
+    return out.raw
+
+
+def host_ed25519_sign(keys: bytes, msg: bytes) -> bytes:
+    """Ed25519::sign on the host: keys = secret | public, the signature R | s"""
+    if len(keys) != 64:
+        raise BzkError("host_ed25519_sign: keys is secret | public, 64 bytes")
+    out = C.create_string_buffer(64)
+    _st(load_library().bzk_host_ed25519_sign(_ptr(keys), _ptr(msg) if msg else None, len(msg), out), "host_ed25519_sign")
+    return out.raw
+
+
+def _signed_records(name: str, call, n: int, want_txs: bool, in_len: int):
+    """runs call(sig, ok, txs_out, cap, out_len) with txs_out sized for every record gaining a signature"""
+    lib = load_library()
+    sig, ok = C.create_string_buffer(max(64 * n, 1)), C.create_string_buffer(max(n, 1))
+    cap = in_len + 76 * n  # a record grows by at most a tag's change, a length prefix and the signature
+    out = C.create_string_buffer(max(cap, 1)) if want_txs else None
+    out_len = _u64(0)
+    st = call(sig, ok, out, cap if want_txs else 0, C.byref(out_len))
+    if st != 0:
+        raise BzkError(f"{name}: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+    return sig.raw[: 64 * n], ok.raw[:n], (out.raw[: out_len.value] if want_txs else None)
+
+
+def _mpn_deposits_sign(ctx_handle, keys: bytes, txs: bytes, n: int, want_txs: bool):
+    if len(keys) != 64 * n:
+        raise BzkError("mpn_deposits_sign: keys is not n x 64 bytes")
+    lib = load_library()
+    return _signed_records("mpn_deposits_sign", lambda sig, ok, out, cap, out_len: lib.bzk_mpn_deposits_sign(
+        ctx_handle, _ptr(keys) if n else None, _ptr(txs) if txs else None, len(txs), n, sig, ok, out, cap, out_len), n, want_txs, len(txs))
+
+
+def _l1_txs_sign(ctx_handle, keys: bytes, txs: bytes, n: int, form: int, want_hash: bool, want_txs: bool):
+    if len(keys) != 64 * n:
+        raise BzkError("l1_txs_sign: keys is not n x 64 bytes")
+    lib = load_library()
+    h = C.create_string_buffer(max(32 * n, 1)) if want_hash else None
+    sig, ok, out = _signed_records("l1_txs_sign", lambda sig, ok, out, cap, out_len: lib.bzk_l1_txs_sign(
+        ctx_handle, _ptr(keys) if n else None, _ptr(txs) if txs else None, len(txs), n, form, sig, ok, h, out, cap, out_len), n, want_txs, len(txs))
+    return sig, ok, (h.raw[: 32 * n] if want_hash else None), out
+
+
+def host_mpn_deposits_sign(keys: bytes, txs: bytes, n: int, want_txs: bool = True):
+    """Bzk.mpn_deposits_sign without a device: the same per-lane code on host threads"""
+    return _mpn_deposits_sign(None, keys, txs, n, want_txs)
+
+
+def host_l1_txs_sign(keys: bytes, txs: bytes, n: int, form: int = L1_FORM_TX, want_hash: bool = True, want_txs: bool = True):
+    """Bzk.l1_txs_sign without a device: the same per-lane code on host threads"""
+    return _l1_txs_sign(None, keys, txs, n, form, want_hash, want_txs)
 
 
 def _groth16_verify_batch(ctx_handle, vk_bincode: bytes, inputs: bytes, n_inputs: int, proofs: bytes) -> bytes:

@@ -238,6 +238,42 @@ int32_t bzk_sha3_merkle_roots_dev(bzk_ctx* ctx, const void* leaves_dev, const vo
 int32_t bzk_block_bodies_check(bzk_ctx* ctx, const uint8_t* txs, uint64_t len, const uint64_t* count, uint64_t m, uint8_t* sig_ok_out,
                                uint8_t* root_out, uint8_t* tx_ok_out, uint8_t* hash_out);
 
+/* ---- batched Ed25519 key derivation and signing; the producers of deposits and L1 transactions -----------------
+ * Ed25519::<Sha3_256>::generate_keys and Ed25519::sign (src/crypto/ed25519.rs:70-80 over `ed25519-dalek = "1"`) for n independent rows, one
+ * lane each.  Signing is RFC 8032 5.1.6 and deterministic: h = SHA-512(secret), a = the clamped low half, r = SHA-512(h[32 .. 64) | M) mod l,
+ * R = encode([r]B), k = SHA-512(R | A | M) mod l, s = (k a + r) mod l, so every route gives the bytes of bzk_host_ed25519_sign, of dalek and
+ * of OpenSSL.
+ * keys: seed i = seeds[off[i] .. off[i+1]) (off: n + 1 non-decreasing entries from 0, as bzk_sha512_batch takes its messages);
+ * secret = SHA3-256(seed) with bit 255 cleared; keys_out n x 64 (secret | public, the layout of Keypair::to_bytes()).
+ * sign: keys n x 64 in that layout, message i = msg[off[i] .. off[i+1]), sig_out n x 64 (R | s).  The public half is taken as given, as
+ * dalek's ExpandedSecretKey::sign(message, &public) takes it.  Every key is valid, so there is no ok output.  n = 0 is a no-op.
+ * The host forms check off, stage through the context's workspace in rounds that end at 2^16 rows or 64 MiB, synchronise, and overwrite the
+ * workspace regions that held staged keys, seeds, expanded scalars and prefixes before they return; the _dev forms enqueue on the context's
+ * stream, trust off and leave the caller's buffers alone (the signer's own 64 bytes per row of workspace are overwritten behind the launch).
+ * ctx = NULL (host forms): the same per-lane code on host threads (bzk_host_default_threads).  The fixed-base walk indexes a table by
+ * nibbles of the secret nonce (of the secret scalar for keys): fixed-flow, not address-independent - a throughput signer, not a hardened one. */
+int32_t bzk_ed25519_keys_batch(bzk_ctx* ctx, const uint8_t* seeds, const uint64_t* off, uint64_t n, uint8_t* keys_out);
+int32_t bzk_ed25519_keys_batch_dev(bzk_ctx* ctx, const void* seeds_dev, const void* off_dev, uint64_t n, void* keys_out_dev);
+int32_t bzk_ed25519_sign_batch(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* msg, const uint64_t* off, uint64_t n, uint8_t* sig_out);
+int32_t bzk_ed25519_sign_batch_dev(bzk_ctx* ctx, const void* keys_dev, const void* msg_dev, const void* off_dev, uint64_t n, void* sig_out_dev);
+/* TxBuilder::sign_deposit (src/wallet/tx_builder.rs:63-66) for n deposits given as n consecutive bincode(MpnDeposit)
+ * (bzk_mpn_deposit_verify_batch's input; payment.sig may be None or Some, a Some's bytes are ignored) and n keys (n x 64).  The signed bytes
+ * are the payment up to the Option tag followed by a None tag, hashed in place from the uploaded record.  sig_out n x 64; ok[i] = 1 where
+ * payment.src equals the key's public half, else ok[i] = 0, a zero sig_out row and the record copied through unchanged.  txs_out (may be
+ * NULL: only sig_out and ok are written) receives the records with Some(sig), spelled as bzk_mpn_set_wire_flags says; *out_len is always set
+ * to the length they need; where cap is smaller, BZK_E_ARG and nothing else written.  Refusals of malformed input are
+ * bzk_mpn_deposit_verify_batch's, naming the record.  Rounds end at 2^16 records or 64 MiB; synchronises; staged keys and their expansions
+ * are overwritten.  ctx = NULL: the same per-lane code on host threads. */
+int32_t bzk_mpn_deposits_sign(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* sig_out, uint8_t* ok,
+                              uint8_t* txs_out, uint64_t cap, uint64_t* out_len);
+/* TxBuilder::sign_tx (src/wallet/tx_builder.rs:67-70) for n records of either BZK_L1_FORM_* form and any TransactionData variant; the
+ * signature may be Unsigned or Signed (ignored).  The signed form is bzk_l1_tx_verify_batch's (the state / delta cut and Signature::Unsigned),
+ * hashed in place.  ok[i] = 0, a zero sig_out row and the record copied unchanged where src is None or differs from the key's public half.
+ * hash_out (n x 32, may be NULL) = Transaction::hash of every record.  txs_out, cap, out_len, rounds, hygiene and ctx = NULL as
+ * bzk_mpn_deposits_sign; the records come back with Signature::Signed(sig).  Refusals are bzk_l1_tx_verify_batch's. */
+int32_t bzk_l1_txs_sign(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* txs, uint64_t len, uint64_t n, uint32_t form, uint8_t* sig_out, uint8_t* ok,
+                        uint8_t* hash_out, uint8_t* txs_out, uint64_t cap, uint64_t* out_len);
+
 /* ---- wire-form ContractUpdates: commitment, aux data, deposit signatures and proof -------------------------------
  * What `update_contract` (src/blockchain/ops/apply_tx/update_contract/mod.rs:28-116) computes and verifies per ContractUpdate before and when
  * it calls zk::check_proof, for the updates of m consecutive UpdateContract transactions of ONE contract: the commitment
@@ -807,6 +843,9 @@ int32_t bzk_host_jubjub_decompress(const uint8_t x[32], int32_t odd, uint8_t xy_
 int32_t bzk_host_sha512(const uint8_t* in, uint64_t len, uint8_t out[64]);
 /* the verdict of bzk_ed25519_verify_batch for one signature, on the host */
 int32_t bzk_host_ed25519_verify(const uint8_t pk[32], const uint8_t* msg, uint64_t len, const uint8_t sig[64]);  /* 1 / 0 */
+/* one row of bzk_ed25519_keys_batch / bzk_ed25519_sign_batch on the host: keys_out / keys = secret | public, sig_out = R | s */
+int32_t bzk_host_ed25519_keys(const uint8_t* seed, uint64_t len, uint8_t keys_out[64]);
+int32_t bzk_host_ed25519_sign(const uint8_t keys[64], const uint8_t* msg, uint64_t len, uint8_t sig_out[64]);
 
 /* ---- static-base tables (the Groth16 CRS queries are fixed point sets) -------------------------------------------
  * build: tab[w][i] = 2^(c w) * base_i for every window, kept in HBM (W x the base memory, internal limb form).  With a

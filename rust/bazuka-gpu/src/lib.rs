@@ -11,6 +11,9 @@
 //!   * `Gpu::jubjub_keys_batch` / `Gpu::jubjub_sign_batch` - `JubJub::generate_keys` and `JubJub::sign` (src/crypto/jubjub/mod.rs:112-150) for many
 //!                                seeds / (key, message) pairs at once; `Gpu::mpn_txs_sign` - the signing step of
 //!                                `TxBuilder::create_mpn_transaction` (src/wallet/tx_builder.rs:287-306) for many transactions at once
+//!   * `Gpu::ed25519_keys_batch` / `Gpu::ed25519_sign_batch` - `Ed25519::generate_keys` and `Ed25519::sign` (src/crypto/ed25519.rs:70-80) for many
+//!                                seeds / (keypair, message) pairs at once; `Gpu::mpn_deposits_sign` / `Gpu::l1_txs_sign` - `TxBuilder::sign_deposit`
+//!                                and `TxBuilder::sign_tx` (src/wallet/tx_builder.rs:63-70) for many records at once
 //!   * `Gpu::mpn_tx_verify_batch` - `MpnTransaction::verify_signature` (src/zk/mod.rs:610-627) for many wire-form transactions at once
 //!   * `Gpu::mpn_withdraw_verify_batch` - `MpnWithdraw::verify_signature` and `verify_calldata` (src/core/transaction.rs:177-189) for many
 //!                                wire-form withdrawals at once, with `payment.fingerprint()` (:204-211, a SHA3-256) taken on the device
@@ -397,6 +400,98 @@ impl Gpu {
             sys::bzk_ed25519_verify_batch(self.0, pk.as_ptr(), data.as_ptr(), off.as_ptr(), sig.as_ptr(), n as u64, ok.as_mut_ptr())
         })?;
         Ok(ok.into_iter().map(|b| b != 0).collect())
+    }
+
+    /// Bulk `Ed25519::<Sha3_256>::generate_keys(seed)` (src/crypto/ed25519.rs:70-77): SHA3-256, SHA-512 and `[a]B` run on the device, one lane per
+    /// seed.  Every key is the 64 bytes of `Keypair::to_bytes()` (secret | public).  The staged seeds and keys are overwritten in the device
+    /// workspace before the call returns.
+    pub fn ed25519_keys_batch(&self, seeds: &[&[u8]]) -> Result<Vec<[u8; 64]>, GpuError> {
+        let mut off = Vec::with_capacity(seeds.len() + 1);
+        let mut data = Vec::new();
+        off.push(0u64);
+        for m in seeds {
+            data.extend_from_slice(m);
+            off.push(data.len() as u64);
+        }
+        let mut out = vec![[0u8; 64]; seeds.len()];
+        check(self.0, unsafe { sys::bzk_ed25519_keys_batch(self.0, data.as_ptr(), off.as_ptr(), seeds.len() as u64, out.as_mut_ptr() as *mut u8) })?;
+        Ok(out)
+    }
+
+    /// Bulk `Ed25519::sign(sk, msg)` (src/crypto/ed25519.rs:78-80: ed25519-dalek 1 `Keypair::sign`, RFC 8032 5.1.6) over raw bytes: 64-byte
+    /// keypairs in, 64-byte signatures out.  Deterministic, so the signatures are dalek's own.  A throughput signer: the fixed-base walk is
+    /// fixed-flow but indexes a table by nibbles of the nonce.
+    pub fn ed25519_sign_batch(&self, items: &[(&[u8; 64], &[u8])]) -> Result<Vec<[u8; 64]>, GpuError> {
+        let n = items.len();
+        let (mut keys, mut data, mut off) = (Vec::with_capacity(64 * n), Vec::new(), Vec::with_capacity(n + 1));
+        off.push(0u64);
+        for (k, m) in items {
+            keys.extend_from_slice(&k[..]);
+            data.extend_from_slice(m);
+            off.push(data.len() as u64);
+        }
+        let mut out = vec![[0u8; 64]; n];
+        check(self.0, unsafe {
+            sys::bzk_ed25519_sign_batch(self.0, keys.as_ptr(), data.as_ptr(), off.as_ptr(), n as u64, out.as_mut_ptr() as *mut u8)
+        })?;
+        Ok(out)
+    }
+
+    /// `TxBuilder::sign_deposit` (src/wallet/tx_builder.rs:63-66) for many deposits: `payment.sig = Some(sign(bincode(payment with sig None)))`,
+    /// hashed in place on the device.  `keys[i]` is the 64-byte keypair of deposit i.  Returns, per deposit, whether it was signed (`false`:
+    /// `payment.src` is not the key's public half; `sig` is left as it was).
+    pub fn mpn_deposits_sign(&self, keys: &[[u8; 64]], txs: &mut [MpnDeposit]) -> Result<Vec<bool>, GpuError> {
+        assert!(keys.len() == txs.len());
+        let mut bytes = Vec::with_capacity(246 * txs.len());
+        for tx in txs.iter() {
+            bytes.extend_from_slice(&bincode::serialize(tx)?);
+        }
+        let n = txs.len();
+        let (mut sig, mut ok, mut out_len) = (vec![0u8; 64 * n], vec![0u8; n], 0u64);
+        let st = unsafe {
+            sys::bzk_mpn_deposits_sign(self.0, keys.as_ptr() as *const u8, bytes.as_ptr(), bytes.len() as u64, n as u64, sig.as_mut_ptr(),
+                                       ok.as_mut_ptr(), ptr::null_mut(), 0, &mut out_len)
+        };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(self.0, st)?;
+        for (i, tx) in txs.iter_mut().enumerate() {
+            if ok[i] != 0 {
+                tx.payment.sig = Some(bincode::deserialize(&sig[64 * i..64 * i + 64])?);
+            }
+        }
+        Ok(ok.into_iter().map(|b| b != 0).collect())
+    }
+
+    /// `TxBuilder::sign_tx` (src/wallet/tx_builder.rs:67-70) for many transactions of any `TransactionData` variant:
+    /// `tx.sig = Signature::Signed(sign(bincode(tx.sig_state_excluded())))`, hashed in place on the device.  Returns, per transaction, whether it
+    /// was signed (`false`: `src` is `None` or not the key's public half; `sig` is left as it was) and `tx.hash()`.
+    pub fn l1_txs_sign(&self, keys: &[[u8; 64]], txs: &mut [Transaction]) -> Result<Vec<(bool, [u8; 32])>, GpuError> {
+        assert!(keys.len() == txs.len());
+        let mut bytes = Vec::new();
+        for tx in txs.iter() {
+            bytes.extend_from_slice(&bincode::serialize(tx)?);
+        }
+        let n = txs.len();
+        let (mut sig, mut ok, mut hash, mut out_len) = (vec![0u8; 64 * n], vec![0u8; n], vec![0u8; 32 * n], 0u64);
+        let form = 0u32; // BZK_L1_FORM_TX: the records are bincode(Transaction)
+        let st = unsafe {
+            sys::bzk_l1_txs_sign(self.0, keys.as_ptr() as *const u8, bytes.as_ptr(), bytes.len() as u64, n as u64, form, sig.as_mut_ptr(),
+                                 ok.as_mut_ptr(), hash.as_mut_ptr(), ptr::null_mut(), 0, &mut out_len)
+        };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(self.0, st)?;
+        for (i, tx) in txs.iter_mut().enumerate() {
+            if ok[i] != 0 {
+                tx.sig = bazuka::core::Signature::Signed(bincode::deserialize(&sig[64 * i..64 * i + 64])?);
+            }
+        }
+        Ok(ok.iter().zip(hash.chunks_exact(32)).map(|(b, h)| (*b != 0, h.try_into().unwrap())).collect())
     }
 
     /// Bulk `groth16_verify` (src/zk/groth16/mod.rs:67-121) for proofs of ONE verifying key, one device lane per proof: what

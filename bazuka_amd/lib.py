@@ -58,6 +58,7 @@ SIGNATURES = {
     "bzk_jubjub_sign_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "bzk_jubjub_sign_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "bzk_mpn_txs_sign": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "bzk_mpn_withdraws_sign": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp]),
     "bzk_sha3_256_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "bzk_sha3_256_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "bzk_mpn_withdraw_verify_batch": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp]),
@@ -449,6 +450,11 @@ class Bzk:
         """n consecutive bincode(MpnTransaction) and n keys (n x 128): (the records with each signed one's signature replaced, verdict bytes,
         tx hashes n x 32 or None); a malformed record raises"""
         return _mpn_txs_sign(self.h, keys, txs, n, want_hash)
+
+    def mpn_withdraws_sign(self, keys: bytes, txs: bytes, n: int, want_fingerprint: bool = True):
+        """n consecutive bincode(MpnWithdraw) and n keys (n x 128): (the records with each signed one's mpn_sig and payment.calldata replaced,
+        verdict bytes, payment fingerprints n x 32 or None); a malformed record raises"""
+        return _mpn_withdraws_sign(self.h, keys, txs, n, want_fingerprint)
 
     def mpn_tx_verify_batch(self, txs: bytes, n: int, want_hash: bool = True):
         """n consecutive bincode(MpnTransaction): (verdict bytes, tx hashes n x 32 or None); a malformed record raises"""
@@ -1631,6 +1637,8 @@ def host_jubjub_decompress(x: bytes, odd: bool):
 
 
 JUBJUB_SIGN_ROUND = 1 << 16  # rows a host-pointer signing or key call stages per round (sign.hip SIGN_ROUND)
+MPN_TX_CHUNK = 1 << 16  # wire-form records staged per round (bzk_mpn_wire.h MPN_TX_CHUNK)
+MPN_WD_CHUNK_BYTES = 64 << 20  # payment bytes of wire-form withdrawals staged per round (bzk_mpn_wire.h MPN_WD_CHUNK_BYTES)
 
 
 def _jubjub_keys_batch(ctx_handle, seeds) -> bytes:
@@ -1665,6 +1673,18 @@ def _mpn_txs_sign(ctx_handle, keys: bytes, txs: bytes, n: int, want_hash: bool):
     return out.raw[: len(txs)], ok.raw[:n], (hashes.raw[: 32 * n] if want_hash else None)
 
 
+def _mpn_withdraws_sign(ctx_handle, keys: bytes, txs: bytes, n: int, want_fingerprint: bool):
+    lib = load_library()
+    if len(keys) != 128 * n:
+        raise BzkError("mpn_withdraws_sign: keys is not n x 128 bytes")
+    out, ok = C.create_string_buffer(max(len(txs), 1)), C.create_string_buffer(max(n, 1))
+    fps = C.create_string_buffer(max(32 * n, 1)) if want_fingerprint else None
+    st = lib.bzk_mpn_withdraws_sign(ctx_handle, _ptr(keys), _ptr(txs), len(txs), n, out, ok, fps)
+    if st != 0:
+        raise BzkError(f"mpn_withdraws_sign: {lib.bzk_strerror(st).decode()} [{lib.bzk_mpn_work_last_error().decode()}]")
+    return out.raw[: len(txs)], ok.raw[:n], (fps.raw[: 32 * n] if want_fingerprint else None)
+
+
 def host_jubjub_keys_batch(seeds) -> bytes:
     """Bzk.jubjub_keys_batch without a device: the same per-lane code on host threads"""
     return _jubjub_keys_batch(None, seeds)
@@ -1678,6 +1698,11 @@ def host_jubjub_sign_batch(keys: bytes, msg: bytes):
 def host_mpn_txs_sign(keys: bytes, txs: bytes, n: int, want_hash: bool = True):
     """Bzk.mpn_txs_sign without a device: the same per-lane code on host threads"""
     return _mpn_txs_sign(None, keys, txs, n, want_hash)
+
+
+def host_mpn_withdraws_sign(keys: bytes, txs: bytes, n: int, want_fingerprint: bool = True):
+    """Bzk.mpn_withdraws_sign without a device: the same per-lane code on host threads"""
+    return _mpn_withdraws_sign(None, keys, txs, n, want_fingerprint)
 
 
 def _mpn_tx_verify_batch(ctx_handle, txs: bytes, n: int, want_hash: bool):

@@ -157,6 +157,22 @@ int32_t bzk_jubjub_sign_batch_dev(bzk_ctx* ctx, const void* keys_dev, const void
  * synchronises; the staged key bytes are overwritten.  ctx = NULL: the same on host threads. */
 int32_t bzk_mpn_txs_sign(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* txs_out, uint8_t* ok,
                          uint8_t* hash_out);
+/* TxBuilder::withdraw_mpn (src/wallet/tx_builder.rs:376-425) for n withdrawals given as n consecutive bincode(MpnWithdraw)
+ * (bzk_mpn_withdraw_verify_batch's input; the 96 mpn_sig bytes and the 32 payment.calldata bytes of the input are ignored whatever they hold)
+ * and n keys (n x 128, the layout of bzk_jubjub_sign_batch).  The host only parses; per record the device computes payment.fingerprint()
+ * (SHA3-256 with the calldata read as zeros, then ZkScalar::new), checks that mpn_address is the compression of the key's pub, signs
+ * Poseidon(fingerprint, nonce) and computes calldata = Poseidon(pub.x, pub.y, nonce, sig.r.x, sig.r.y, sig.s).  txs_out (len bytes, may be
+ * txs) = the input with each signed record's mpn_sig and payment.calldata replaced, both as bzk_mpn_withdraw_verify_batch reads them (32-byte
+ * Montgomery limbs); a record's length never changes.  ok[i] = 1 where record i was signed; ok[i] = 0 and record i copied unchanged where a
+ * key field is not the limbs of a residue or mpn_address does not match the key, not an error.  fingerprint_out (n x 32, may be NULL) =
+ * payment.fingerprint() for every record, signed or not: the bytes bzk_mpn_withdraw_verify_batch returns.  BZK_E_ARG with
+ * bzk_mpn_work_last_error() naming the record when the bytes are not n well-formed records, nothing written; a payment longer than 65 536
+ * bytes counts as malformed, as on the verify side.  n = 0 is a no-op.  Rounds end at 2^16 records or 64 MiB of payment bytes, whichever
+ * comes first; synchronises; the workspace region that held key bytes is overwritten before the call returns, on the error paths too.
+ * ctx = NULL: the same per-lane code on host threads (bzk_host_default_threads).  The fixed-base walk indexes a table by nibbles of the secret
+ * nonce: fixed-flow, not address-independent - a throughput signer, not a hardened one. */
+int32_t bzk_mpn_withdraws_sign(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* txs_out, uint8_t* ok,
+                               uint8_t* fingerprint_out);
 
 /* ---- batched SHA3-256 and hash_to_scalar -----------------------------------------------------------------
  * n messages: message i = data[off[i] .. off[i+1]), off has n + 1 entries, off[0] = 0, non-decreasing.  One lane per message, which loops

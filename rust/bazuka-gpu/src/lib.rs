@@ -10,7 +10,8 @@
 //!   * `Gpu::jubjub_verify_batch` - `JubJub::<ZkHasher>::verify` (src/crypto/jubjub/mod.rs:151-167) for many signatures at once
 //!   * `Gpu::jubjub_keys_batch` / `Gpu::jubjub_sign_batch` - `JubJub::generate_keys` and `JubJub::sign` (src/crypto/jubjub/mod.rs:112-150) for many
 //!                                seeds / (key, message) pairs at once; `Gpu::mpn_txs_sign` - the signing step of
-//!                                `TxBuilder::create_mpn_transaction` (src/wallet/tx_builder.rs:287-306) for many transactions at once
+//!                                `TxBuilder::create_mpn_transaction` (src/wallet/tx_builder.rs:287-306) for many transactions at once;
+//!                                `Gpu::mpn_withdraws_sign` - the signature and calldata of `TxBuilder::withdraw_mpn` (:376-425) for many withdrawals
 //!   * `Gpu::ed25519_keys_batch` / `Gpu::ed25519_sign_batch` - `Ed25519::generate_keys` and `Ed25519::sign` (src/crypto/ed25519.rs:70-80) for many
 //!                                seeds / (keypair, message) pairs at once; `Gpu::mpn_deposits_sign` / `Gpu::l1_txs_sign` - `TxBuilder::sign_deposit`
 //!                                and `TxBuilder::sign_tx` (src/wallet/tx_builder.rs:63-70) for many records at once
@@ -205,6 +206,42 @@ impl Gpu {
         for (i, tx) in txs.iter_mut().enumerate() {
             if ok[i] != 0 {
                 tx.sig = bincode::deserialize(&out[ends[i] - 96..ends[i]])?;
+            }
+        }
+        Ok(ok.into_iter().map(|b| b != 0).collect())
+    }
+
+    /// What `TxBuilder::withdraw_mpn` (src/wallet/tx_builder.rs:376-425) computes, for many withdrawals: `mpn_sig = JubJub::sign(key,
+    /// Poseidon(payment.fingerprint(), nonce))` and `payment.calldata = Poseidon(pk.x, pk.y, nonce, sig.r.x, sig.r.y, sig.s)`, with the fingerprint
+    /// (a SHA3-256 of the payment with its calldata blanked), both hashes and the signature on the device.  Whatever `mpn_sig` and `calldata`
+    /// hold on entry is ignored.  Returns, per withdrawal, whether it was signed (`false`: `mpn_address` is not the key's; the withdrawal is left
+    /// as it was).  A payment longer than 65 536 bytes is refused (`GpuError::Status`).  A throughput signer, as `jubjub_sign_batch`.
+    pub fn mpn_withdraws_sign(&self, keys: &[PrivateKey], txs: &mut [MpnWithdraw]) -> Result<Vec<bool>, GpuError> {
+        assert!(keys.len() == txs.len());
+        let mut flat = Vec::with_capacity(4 * keys.len());
+        for k in keys {
+            flat.extend_from_slice(&[k.public_key.0, k.public_key.1, k.randomness, k.scalar]);
+        }
+        let mut bytes = Vec::with_capacity(277 * txs.len());
+        let mut ends = Vec::with_capacity(txs.len() + 1);
+        ends.push(0usize);
+        for tx in txs.iter() {
+            bytes.extend_from_slice(&bincode::serialize(tx)?);
+            ends.push(bytes.len());
+        }
+        let mut out = vec![0u8; bytes.len()];
+        let mut ok = vec![0u8; txs.len()];
+        let st = unsafe {
+            sys::bzk_mpn_withdraws_sign(self.0, scalars_ptr(&flat), bytes.as_ptr(), bytes.len() as u64, txs.len() as u64, out.as_mut_ptr(), ok.as_mut_ptr(), ptr::null_mut())
+        };
+        if st == sys::BZK_E_ARG {
+            let why = unsafe { CStr::from_ptr(sys::bzk_mpn_work_last_error()).to_string_lossy().into_owned() };
+            return Err(GpuError::Status(st, why));
+        }
+        check(self.0, st)?;
+        for (i, tx) in txs.iter_mut().enumerate() {
+            if ok[i] != 0 {
+                *tx = bincode::deserialize(&out[ends[i]..ends[i + 1]])?;
             }
         }
         Ok(ok.into_iter().map(|b| b != 0).collect())

@@ -205,6 +205,14 @@ void g16k_host_run(const std::vector<G16kGroup>& groups);
 // on host records; on_device: the records already are in device memory.  sg_host_one: the verdict of one record on the host
 int32_t sg_first_bad(bzk_ctx* ctx, const char* who, bool g2, const uint8_t* pts, bool on_device, uint64_t n, uint64_t* idx, uint8_t* code);
 uint8_t sg_host_one(bool g2, const uint8_t* raw);
+// r1cs_eval.hip: the launches behind bzk_r1cs_eval_dev as a stage of bzk_groth16_prove_witness, in stream order, arguments checked by the caller.
+// r1cs_eval_enqueue: A.z, B.z, C.z of device-resident matrices into a / b / c (a null one is skipped), rows n_rows .. pad_rows written as zero;
+// r1cs_sat_enqueue: *first_dev = the first of n_rows rows with a * b != c, ~0 where every row holds; r1cs_mats_shape: *device = -1 for a handle in host memory
+int32_t r1cs_eval_enqueue(bzk_ctx* ctx, const bzk_r1cs_mats* m, const void* z_dev, void* a_dev, void* b_dev, void* c_dev, uint64_t pad_rows);
+int32_t r1cs_sat_enqueue(bzk_ctx* ctx, const void* a_dev, const void* b_dev, const void* c_dev, uint64_t n_rows, uint64_t* first_dev);
+void r1cs_mats_shape(const bzk_r1cs_mats* m, uint64_t* n_rows, uint64_t* n_vars, int* device);
+std::string& null_ctx_error();                   // ctx.hip: what bzk_last_error(NULL) answers on this thread
+void set_null_ctx_error(const std::string& e);
 int32_t ntt_run(bzk_ctx* ctx, void* data_dev, uint32_t log_n, int inverse, int coset);  // ntt.hip
 int32_t ntt_h_chain(bzk_ctx* ctx, void* a, void* b, void* c, uint32_t log_m);              // ntt.hip: the h polynomial's 7 transforms, fused
 // msm_g1.hip / msm_g2.hip: windows [w_begin, w_end) (w_end < 0: all) of an MSM over a resident base set (or raw bases when `bases` is

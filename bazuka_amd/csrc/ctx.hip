@@ -16,6 +16,13 @@ namespace bzk {
 
 void ntt_free_tables(bzk_ctx* ctx);  // ntt.hip
 
+// what bzk_last_error(NULL) answers on this thread: "null ctx" until a call on the ctx = NULL route has refused something
+std::string& null_ctx_error() {
+    static thread_local std::string e = "null ctx";
+    return e;
+}
+void set_null_ctx_error(const std::string& e) { null_ctx_error() = e; }
+
 int32_t ws_reserve(bzk_ctx* ctx, size_t bytes, const char* who) {
     if (ctx->ws_live) {
         ctx->last_error = std::string(who) + ": workspace reserved while the layout of " + ctx->ws_live + " is live";
@@ -373,7 +380,8 @@ int32_t bzk_sync(bzk_ctx* ctx) {
     return BZK_OK;
 }
 
-const char* bzk_last_error(bzk_ctx* ctx) { return ctx ? ctx->last_error.c_str() : "null ctx"; }
+// a call that takes ctx = NULL for its host route (bzk_r1cs_mats_load, bzk_r1cs_eval) leaves its refusal here, per thread
+const char* bzk_last_error(bzk_ctx* ctx) { return ctx ? ctx->last_error.c_str() : bzk::null_ctx_error().c_str(); }
 int32_t bzk_last_refusal(bzk_ctx* ctx) { return ctx ? ctx->last_refusal : BZK_REFUSE_NONE; }
 
 int32_t bzk_dev_alloc(bzk_ctx* ctx, uint64_t bytes, void** dptr) {

@@ -49,6 +49,13 @@ struct CrsShared {
 struct bzk_params {
     CrsShared* crs;
     void *d_z, *d_a, *d_b, *d_c, *d_sa, *d_sb;  // device scratch sized for this circuit, one set per slot
+    // bzk_groth16_prove_witness with BZK_PROVE_CHECK_SAT: the first unsatisfied row (~0: none) on the device and its pinned host copy, made on first use
+    uint64_t *d_unsat, *h_unsat;
+};
+// bzk_groth16_prove_witness: the evaluations are computed from resident matrices behind the upload of z instead of being uploaded
+struct WitnessEval {
+    const bzk_r1cs_mats* mats;
+    bool check;
 };
 
 namespace bzk {
@@ -230,6 +237,8 @@ void bzk_params_free(bzk_ctx* ctx, bzk_params* p) {
     void* bufs[] = {p->d_z, p->d_a, p->d_b, p->d_c, p->d_sa, p->d_sb};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    if (p->d_unsat) (void)hipFree(p->d_unsat);
+    if (p->h_unsat) (void)hipHostFree(p->h_unsat);
     crs_release(ctx, p->crs);
     delete p;
 }
@@ -426,9 +435,9 @@ int32_t bzk_groth16_h_dev(bzk_ctx* ctx, void* a, void* b, void* c, uint32_t log_
 }
 
 static int32_t groth16_prove_impl(bzk_ctx* ctx, bzk_params* p, const bzk_assignment* asg, const bzk::DeferData* dd, const bzk_staged* st, const uint8_t r32[32],
-                                  const uint8_t s32[32], uint8_t proof[387]);
+                                  const uint8_t s32[32], uint8_t proof[387], const WitnessEval* we);
 static int32_t groth16_prove_entry(bzk_ctx* ctx, bzk_params* p, const bzk_assignment* asg, const bzk::DeferData* dd, const bzk_staged* st, const uint8_t r32[32],
-                                   const uint8_t s32[32], uint8_t proof[387]);
+                                   const uint8_t s32[32], uint8_t proof[387], const WitnessEval* we = nullptr);
 
 int32_t bzk_groth16_prove(bzk_ctx* ctx, bzk_params* p, const bzk_assignment* asg, const uint8_t r32[32], const uint8_t s32[32],
                           uint8_t proof[387]) {
@@ -553,13 +562,44 @@ int32_t bzk_groth16_prove_staged(bzk_ctx* ctx, bzk_params* p, const bzk_staged* 
     return groth16_prove_entry(ctx, p, &asg, nullptr, st, r32, s32, proof);
 }
 
+// From the witness alone: A.z, B.z, C.z are computed on the device from the resident matrices `m` (bzk_r1cs_mats_load, r1cs_eval.hip) behind the upload of
+// z, straight into the slot's d_a / d_b / d_c with the pad zeroed by the same launch - no host arrays, no three uploads ahead of the h polynomial.
+int32_t bzk_groth16_prove_witness(bzk_ctx* ctx, bzk_params* p, const bzk_r1cs_mats* m, const uint8_t* z, uint64_t n_vars, const uint8_t r32[32],
+                                  const uint8_t s32[32], uint32_t flags, uint8_t proof[387]) {
+    if (!ctx || !p || !r32 || !s32 || !proof) return BZK_E_ARG;
+    auto refuse = [&](const std::string& why) {
+        ctx->last_error = "groth16_prove_witness: " + why;
+        return BZK_E_ARG;
+    };
+    if (!m) return refuse("no matrices");
+    if (!z) return refuse("z is NULL");
+    if (flags & ~BZK_PROVE_CHECK_SAT) return refuse("unknown flags");
+    uint64_t n_rows = 0, nv = 0;
+    int device = -1;
+    bzk::r1cs_mats_shape(m, &n_rows, &nv, &device);
+    if (device < 0) return refuse("the matrices were loaded without a context (host memory)");
+    if (device != ctx->device || p->crs->device != ctx->device) return refuse("the matrices or the parameters are resident on another device");
+    if (n_vars != nv) return refuse("the witness has " + std::to_string(n_vars) + " variables, the matrices " + std::to_string(nv));
+    if (n_vars != (uint64_t)p->crs->n_in + p->crs->n_aux)
+        return refuse("the witness has " + std::to_string(n_vars) + " variables, the parameters " + std::to_string((uint64_t)p->crs->n_in + p->crs->n_aux));
+    if (n_rows > ((uint64_t)1 << p->crs->log_m))
+        return refuse("the matrices have " + std::to_string(n_rows) + " rows, the parameters' domain 2^" + std::to_string(p->crs->log_m));
+    bzk_assignment asg;
+    asg.z = z;
+    asg.az = asg.bz = asg.cz = nullptr;
+    asg.n_rows = n_rows;
+    asg.n_vars = n_vars;
+    const WitnessEval we{m, (flags & BZK_PROVE_CHECK_SAT) != 0};
+    return groth16_prove_entry(ctx, p, &asg, nullptr, nullptr, r32, s32, proof, &we);
+}
+
 static int32_t groth16_prove_entry(bzk_ctx* ctx, bzk_params* p, const bzk_assignment* asg, const bzk::DeferData* dd, const bzk_staged* st_in,
-                                   const uint8_t r32[32], const uint8_t s32[32], uint8_t proof[387]) {
-    if (!ctx || !p || !asg || !r32 || !s32 || !proof || !asg->z || !asg->az || !asg->bz || !asg->cz) return BZK_E_ARG;
+                                   const uint8_t r32[32], const uint8_t s32[32], uint8_t proof[387], const WitnessEval* we) {
+    if (!ctx || !p || !asg || !r32 || !s32 || !proof || !asg->z || (!we && (!asg->az || !asg->bz || !asg->cz))) return BZK_E_ARG;
     if (p->crs->device != ctx->device) return BZK_E_ARG;
     (void)hipSetDevice(ctx->device);
     crs_prepare(ctx, p->crs);
-    int32_t st = groth16_prove_impl(ctx, p, asg, dd, st_in, r32, s32, proof);
+    int32_t st = groth16_prove_impl(ctx, p, asg, dd, st_in, r32, s32, proof, we);
     auto quiesce = [&] {
         // the caller frees (re-uses) the assignment arrays as soon as this returns: no copy out of them may still be in
         // flight, on the main stream or on a lane
@@ -596,7 +636,7 @@ static int32_t groth16_prove_entry(bzk_ctx* ctx, bzk_params* p, const bzk_assign
         if (dropped) {
             for (bzk_ctx* l : ctx->lanes) (void)bzk_ctx_trim(l, nullptr);
             (void)bzk_ctx_trim(ctx, nullptr);
-            st = groth16_prove_impl(ctx, p, asg, dd, st_in, r32, s32, proof);
+            st = groth16_prove_impl(ctx, p, asg, dd, st_in, r32, s32, proof, we);
         }
     }
     if (st != BZK_OK) quiesce();
@@ -654,7 +694,7 @@ int32_t bzk_params_h_table(bzk_ctx* ctx, bzk_params* p, int32_t on) {
 }
 
 static int32_t groth16_prove_impl(bzk_ctx* ctx, bzk_params* slot, const bzk_assignment* asg, const bzk::DeferData* dd, const bzk_staged* staged,
-                                  const uint8_t r32[32], const uint8_t s32[32], uint8_t proof[387]) {
+                                  const uint8_t r32[32], const uint8_t s32[32], uint8_t proof[387], const WitnessEval* we) {
     // a staged assignment is device memory another stream has been filling: this stream waits for that work, and every "upload" below is a device-to-device copy
     const hipMemcpyKind up = staged ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (staged) BZK_HIP(ctx, hipStreamWaitEvent(ctx->stream, staged->ready, 0));
@@ -677,6 +717,15 @@ static int32_t groth16_prove_impl(bzk_ctx* ctx, bzk_params* slot, const bzk_assi
     bzk_ctx* lane[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < n_lanes; ++i)
         if (!(lane[i] = bzk::ctx_lane(ctx, (size_t)i))) return BZK_E_DEVICE;
+    if (we && we->check && !slot->d_unsat) {
+        if (hipMalloc((void**)&slot->d_unsat, 8) != hipSuccess || hipHostMalloc((void**)&slot->h_unsat, 8) != hipSuccess) {
+            (void)hipGetLastError();
+            if (slot->d_unsat) (void)hipFree(slot->d_unsat);
+            slot->d_unsat = nullptr;
+            ctx->last_error = "groth16_prove_witness: allocation of the satisfaction check's word";
+            return BZK_E_ALLOC;
+        }
+    }
     BZK_HIP(ctx, hipMemcpyAsync(slot->d_z, asg->z, nv * 32, up, ctx->stream));
     if (dd) {
         // deferred witness values: z is not complete until the instance's program has run, and the program also writes into the three
@@ -850,11 +899,20 @@ static int32_t groth16_prove_impl(bzk_ctx* ctx, bzk_params* slot, const bzk_assi
             StreamSwap(bzk_ctx* c_, hipStream_t s) : c(c_), saved(c_->stream) { if (s) c->stream = s; }
             ~StreamSwap() { c->stream = saved; }
         };
-        const bool side = h_prio && ctx->hprio && !dd && !staged;
+        const bool side = h_prio && ctx->hprio && !dd && !staged && !we;  // (the evaluation kernels read d_z: they stay behind its upload on the main stream)
         {
         StreamSwap swap(ctx, side ? ctx->hprio : nullptr);
         if (tm[0]) (void)hipEventRecord(tm[0], ctx->stream);
-        for (int k = 0; k < 3 && !dd; ++k) {
+        if (we) {
+            // the three evaluations from the resident matrices: one launch behind z's upload, the rows n_rows .. m zeroed by it
+            BZK_TRY(bzk::r1cs_eval_enqueue(ctx, we->mats, slot->d_z, ev[0], ev[1], ev[2], m));
+            if (we->check) {
+                *slot->h_unsat = ~0ull;
+                BZK_TRY(bzk::r1cs_sat_enqueue(ctx, ev[0], ev[1], ev[2], asg->n_rows, slot->d_unsat));
+                BZK_HIP(ctx, hipMemcpyAsync(slot->h_unsat, slot->d_unsat, 8, hipMemcpyDeviceToHost, ctx->stream));
+            }
+        }
+        for (int k = 0; k < 3 && !dd && !we; ++k) {
             BZK_HIP(ctx, hipMemcpyAsync(ev[k], hv[k], asg->n_rows * 32, up, ctx->stream));
             if (m > asg->n_rows)
                 BZK_HIP(ctx, hipMemsetAsync((char*)ev[k] + asg->n_rows * 32, 0, (m - asg->n_rows) * 32, ctx->stream));
@@ -880,6 +938,11 @@ static int32_t groth16_prove_impl(bzk_ctx* ctx, bzk_params* slot, const bzk_assi
             ctx->last_error = "lane " + std::to_string(i) + ": " + lane[i]->last_error;
             return st[i];
         }
+    if (we && we->check) BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the h MSM's read-back already has, except over an empty h query)
+    if (we && we->check && *slot->h_unsat != ~0ull) {
+        ctx->last_error = "groth16_prove_witness: constraint " + std::to_string(*slot->h_unsat) + " is not satisfied";
+        return BZK_E_UNSAT;
+    }
     if (dd || staged) {  // (the h MSM's read-back has synchronised the main stream: the program's flags word has landed)
         const uint32_t f = staged ? *staged->flags_host : bzk::witfill_flags(ctx);
         if (f) {

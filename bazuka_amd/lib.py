@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("BZK_LIBBZK") or os.path.join(_HERE, "libbzk.so")
 BZK_F_CANONICAL = 1
 BZK_F_DEDUP = 2
 BZK_F_THROUGHPUT = 4
+BZK_PROVE_CHECK_SAT = 1    # bzk_groth16_prove_witness: one product per row decides satisfaction before a proof is written
 BZK_SYNTH_DEFER = 2        # bzk_mpn_work_synthesize's record_matrices: the hash-dependent values left to the device
 BZK_SYNTH_DEFER_SIG = 4    # ... and the EdDSA gadget's ladders
 L1_FORM_TX = 0             # bzk_l1_tx_verify_batch: the records are bincode(Transaction)
@@ -119,6 +120,13 @@ SIGNATURES = {
     "bzk_staged_free": (None, [_vp]),
     "bzk_staged_read": (_i32, [_vp, _i32, _vp, _u64, C.POINTER(_u64)]),
     "bzk_groth16_prove_staged": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "bzk_r1cs_mats_load": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, C.POINTER(_vp)]),
+    "bzk_r1cs_mats_from_r1cs": (_i32, [_vp, _vp, C.POINTER(_vp)]),
+    "bzk_r1cs_mats_free": (None, [_vp, _vp]),
+    "bzk_r1cs_mats_info": (_i32, [_vp, C.POINTER(_u64)]),
+    "bzk_r1cs_eval": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, C.POINTER(C.c_int64)]),
+    "bzk_r1cs_eval_dev": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64]),
+    "bzk_groth16_prove_witness": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u32, _vp]),
     "bzk_bellman_params_info": (_i32, [_vp, _u64, C.POINTER(_u64)]),
     "bzk_bellman_params_decode": (_i32, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
     "bzk_bellman_params_encode": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
@@ -959,6 +967,38 @@ class Bzk:
         self._ck(self.lib.bzk_groth16_prove_staged(self.h, ph, staged, _ptr(r), _ptr(s), out), "groth16_prove_staged")
         return out.raw
 
+    # ---- proving from the witness alone: the circuit's matrices resident, A.z / B.z / C.z on the device (include/bzk.h)
+    def r1cs_mats_load(self, csr_abc, n_in: int, n_aux: int):
+        """csr_abc as groth16_setup takes it; the matrices become resident on this context's device.  Returns the handle."""
+        return _r1cs_mats_load(self.h, csr_abc, n_in, n_aux)
+
+    def r1cs_mats_from(self, r1cs):
+        """the same from an R1cs synthesized with record_matrices"""
+        return _r1cs_mats_from(self.h, r1cs)
+
+    def r1cs_mats_free(self, mh):
+        self.lib.bzk_r1cs_mats_free(self.h, mh)
+
+    def r1cs_mats_info(self, mh) -> dict:
+        return r1cs_mats_info(mh)
+
+    def r1cs_eval(self, mh, z, want_unsat: bool = False):
+        """(az, bz, cz) of the host witness z on the device; with want_unsat also the first unsatisfied row (-1: none)"""
+        return _r1cs_eval(self.h, mh, z, want_unsat)
+
+    def r1cs_eval_dev(self, mh, z, n_vars: int, az, bz, cz, pad_rows: int):
+        """device buffers (tensors / pointers; an output may be None), enqueued on the context's stream; rows n_rows .. pad_rows are zeroed"""
+        self._ck(self.lib.bzk_r1cs_eval_dev(self.h, mh, _ptr(z), n_vars, _ptr(az), _ptr(bz), _ptr(cz), pad_rows), "r1cs_eval_dev")
+
+    def groth16_prove_witness(self, ph, mh, z, r: bytes, s: bytes, check: bool = False, out=None) -> bytes:
+        """groth16_prove from z alone: the evaluations come from the resident matrices `mh`.  check: BZK_PROVE_CHECK_SAT - an unsatisfied
+        witness raises (status BZK_E_UNSAT, the row in the message) and nothing is written to `out` (a 387-byte ctypes buffer, optional)."""
+        zz = bytes(z) if isinstance(z, bytearray) else z
+        out = C.create_string_buffer(387) if out is None else out
+        self._ck(self.lib.bzk_groth16_prove_witness(self.h, ph, mh, _ptr(zz), len(zz) // 32, _ptr(r), _ptr(s),
+                                                    BZK_PROVE_CHECK_SAT if check else 0, out), "groth16_prove_witness")
+        return out.raw
+
     def params_read(self, ph, which: int) -> bytes:
         n = _u64()
         self._ck(self.lib.bzk_params_read(self.h, ph, which, None, 0, C.byref(n)), "params_read")
@@ -1130,6 +1170,67 @@ class Mg:
 def _st(st, what):
     if st != 0:
         raise BzkError(f"{what}: {load_library().bzk_strerror(st).decode()}")
+
+
+def _ck_ctx(ctx_h, st, what):
+    """raises with bzk_last_error of the context - of this thread's ctx = NULL route when there is none"""
+    if st != 0:
+        lib = load_library()
+        raise BzkError(f"{what}: {lib.bzk_strerror(st).decode()} [{lib.bzk_last_error(ctx_h).decode()}]", st)
+
+
+def _r1cs_mats_load(ctx_h, csr_abc, n_in, n_aux):
+    lib = load_library()
+    keep, descs = [], []
+    for n_rows, rp, col, val in csr_abc:
+        # None stays a NULL pointer (the loader refuses it unless the count is zero); bytes are copied, ctypes arrays passed by address
+        bufs = [x if x is None or isinstance(x, C.Array) else C.create_string_buffer(bytes(x), max(1, len(x))) for x in (rp, col, val)]
+        keep.append(bufs)
+        descs.append(CsrDesc(n_rows, *[None if b is None else C.cast(C.addressof(b), C.c_void_p) for b in bufs]))
+    h = C.c_void_p()
+    _ck_ctx(ctx_h, lib.bzk_r1cs_mats_load(ctx_h, C.byref(descs[0]), C.byref(descs[1]), C.byref(descs[2]), n_in, n_aux, C.byref(h)), "r1cs_mats_load")
+    return h
+
+
+def _r1cs_mats_from(ctx_h, r1cs):
+    h = C.c_void_p()
+    _ck_ctx(ctx_h, load_library().bzk_r1cs_mats_from_r1cs(ctx_h, r1cs.h, C.byref(h)), "r1cs_mats_from_r1cs")
+    return h
+
+
+def _r1cs_eval(ctx_h, mh, z, want_unsat):
+    lib = load_library()
+    n_rows = r1cs_mats_info(mh)["n_rows"]
+    zz = bytes(z) if isinstance(z, bytearray) else z
+    outs = [C.create_string_buffer(max(1, 32 * n_rows)) for _ in range(3)]
+    first = C.c_int64(-2)
+    _ck_ctx(ctx_h, lib.bzk_r1cs_eval(ctx_h, mh, _ptr(zz), len(zz) // 32, outs[0], outs[1], outs[2], C.byref(first) if want_unsat else None), "r1cs_eval")
+    res = tuple(o.raw[: 32 * n_rows] for o in outs)
+    return res + (first.value,) if want_unsat else res
+
+
+def r1cs_mats_load(csr_abc, n_in: int, n_aux: int):
+    """ctx = NULL: the matrices kept in host memory, for r1cs_eval below (host threads).  csr_abc as Bzk.groth16_setup takes it."""
+    return _r1cs_mats_load(None, csr_abc, n_in, n_aux)
+
+
+def r1cs_mats_from(r1cs):
+    return _r1cs_mats_from(None, r1cs)
+
+
+def r1cs_mats_free(mh):
+    load_library().bzk_r1cs_mats_free(None, mh)
+
+
+def r1cs_mats_info(mh) -> dict:
+    info = (_u64 * 8)()
+    _st(load_library().bzk_r1cs_mats_info(mh, info), "r1cs_mats_info")
+    return dict(zip(("n_rows", "n_vars", "nnzA", "nnzB", "nnzC", "n_coeffs", "resident_bytes"), [int(x) for x in info]))
+
+
+def r1cs_eval(mh, z, want_unsat: bool = False):
+    """(az, bz, cz[, first unsatisfied row or -1]) on host threads, from a handle loaded without a context"""
+    return _r1cs_eval(None, mh, z, want_unsat)
 
 
 class R1cs:

@@ -800,6 +800,48 @@ void bzk_staged_free(bzk_staged* staged);
 int32_t bzk_staged_read(const bzk_staged* staged, int32_t which, uint8_t* out, uint64_t cap, uint64_t* size_out);
 int32_t bzk_groth16_prove_staged(bzk_ctx* ctx, bzk_params* params, const bzk_staged* staged, const uint8_t r_blind[32], const uint8_t s_blind[32],
                                  uint8_t proof_out[387]);
+/* ---- proving from the witness alone: A.z, B.z, C.z on the device ------------------------------------------------------
+ * bzk_groth16_prove wants <A_k, z>, <B_k, z>, <C_k, z> of every constraint from its caller.  The MPN generator produces them while it builds
+ * the witness; a caller with a circuit of its own (the reference lets every contract bring its Groth16 key) holds a CRS from bzk_groth16_setup
+ * and a witness, nothing else.  The circuit shape is fixed per CRS, so its matrices are resident data like the CRS: bzk_r1cs_mats_load once,
+ * then bzk_groth16_prove_witness per proof - z is the only upload, the evaluations are written straight into the slot's h-stage buffers.
+ * A handle is read-only after load: any number of prover slots of its device (one context + one slot per thread, as for bzk_params_slot) may
+ * evaluate and prove from it at once.  Resident form: 8 bytes per non-zero (column + index into a dictionary of the distinct coefficients)
+ * + 4 bytes per row and matrix; DESIGN.md 3.19. */
+typedef struct bzk_r1cs_mats bzk_r1cs_mats;
+
+/* A, B, C as bzk_groth16_setup takes them (flat variable indices, inputs then aux, rows including bellman's trailing
+ * input_i * 0 = 0 constraints), made resident.  ctx = NULL: kept in host memory for the host-thread route.
+ * A row may be empty, a column may repeat inside a row (the terms add), a stored coefficient may be zero.  BZK_E_ARG with bzk_last_error(ctx)
+ * - bzk_last_error(NULL) on the ctx = NULL route - naming the matrix and the row, nothing allocated: the three n_rows differ; row_ptr[0] != 0 or
+ * row_ptr descends; a column >= n_in + n_aux; a coefficient whose limbs are >= r; a NULL array with a non-zero count; n_in = 0. */
+int32_t bzk_r1cs_mats_load(bzk_ctx* ctx, const bzk_csr* A, const bzk_csr* B, const bzk_csr* C,
+                           uint32_t n_in, uint32_t n_aux, bzk_r1cs_mats** out);
+/* the same from views 6 - 14 of an instance synthesized with record_matrices */
+int32_t bzk_r1cs_mats_from_r1cs(bzk_ctx* ctx, const bzk_r1cs* r, bzk_r1cs_mats** out);
+void    bzk_r1cs_mats_free(bzk_ctx* ctx, bzk_r1cs_mats* m);
+/* info: n_rows, n_vars, nnz(A), nnz(B), nnz(C), distinct coefficients, resident bytes, 0 */
+int32_t bzk_r1cs_mats_info(const bzk_r1cs_mats* m, uint64_t info[8]);
+
+/* az / bz / cz: n_rows x 32 B each, any of them may be NULL: canonical Montgomery scalars, byte for byte what bzk_r1cs_data views 1 - 3 hold.
+ * z is taken as canonical; an entry whose limbs are >= r is not refused and no read leaves the arrays whatever it evaluates to.
+ * first_unsat (may be NULL): index of the first row with az * bz != cz, or -1.
+ * ctx = NULL: the same per-row function on host threads (a handle loaded with ctx = NULL; a device-resident one is refused there, and a
+ * host one here).  BZK_E_ARG, nothing launched: n_vars != n_in + n_aux of the handle, a NULL z, a handle of the other kind or of another device. */
+int32_t bzk_r1cs_eval(bzk_ctx* ctx, const bzk_r1cs_mats* m, const uint8_t* z, uint64_t n_vars,
+                      uint8_t* az, uint8_t* bz, uint8_t* cz, int64_t* first_unsat);
+/* device pointers, enqueued on the context's stream.  Each output holds pad_rows >= n_rows scalars,
+ * rows n_rows .. pad_rows are written as zero (the h stage's padding).  BZK_E_ARG as above, and for pad_rows < n_rows. */
+int32_t bzk_r1cs_eval_dev(bzk_ctx* ctx, const bzk_r1cs_mats* m, const void* z_dev, uint64_t n_vars,
+                          void* az_dev, void* bz_dev, void* cz_dev, uint64_t pad_rows);
+
+#define BZK_PROVE_CHECK_SAT 1u  /* BZK_E_UNSAT, bzk_last_error naming the first unsatisfied row, nothing written to proof_out */
+/* bzk_groth16_prove from z alone: the 387 bytes bzk_groth16_prove gives for the same z, r, s and the evaluations of z.  BZK_E_ARG, nothing
+ * launched, the context proves normally afterwards: n_vars != n_in + n_aux of the handle or of the params, n_rows > 2^log_m, a NULL z, a handle
+ * in host memory or of another device.  Without BZK_PROVE_CHECK_SAT an unsatisfied witness yields an (invalid) proof, as bzk_groth16_prove does;
+ * with it, one product per row on the device decides, and the smallest failing index is reported. */
+int32_t bzk_groth16_prove_witness(bzk_ctx* ctx, bzk_params* params, const bzk_r1cs_mats* m, const uint8_t* z, uint64_t n_vars,
+                                  const uint8_t r[32], const uint8_t s[32], uint32_t flags, uint8_t proof_out[387]);
 /* CPU mirrors of `ZkHasher::hash`, `hash_to_scalar`'s SHA3 and `JubJub::{generate_keys, sign, verify}` */
 /* ---- f-2: the proving worker's wire format ---------------------------------------------------------------------------
  * `MpnWork` (src/mpn/mod.rs:263-270) as `GET /bincode/mpn/work` delivers it (src/node/mod.rs:393-398,

@@ -952,6 +952,75 @@ pub fn groth16_prove(params: &ProvingParams, witness: &Witness, r: ZkScalar, s: 
     Ok(bincode::deserialize(&buf)?) // private fields: through bincode, never a pointer cast
 }
 
+/// The three matrices of a circuit shape resident on the parameters' device (`bzk_r1cs_mats_load`): what `prove_witness` evaluates A.z, B.z, C.z
+/// from.  For a circuit of the caller's own - the reference lets every contract bring its Groth16 key - whose witness comes without evaluations.
+/// Read-only after loading; freed on drop (after the last proof from it has returned).
+pub struct CircuitMatrices {
+    h: *mut sys::bzk_r1cs_mats,
+    ctx: *mut sys::bzk_ctx,
+}
+unsafe impl Send for CircuitMatrices {}
+unsafe impl Sync for CircuitMatrices {}
+
+/// One CSR matrix as `bzk_groth16_setup` takes it: `row_ptr` (n_rows + 1), flat variable indices (inputs, then aux), Montgomery coefficients
+pub struct CsrMatrix<'a> {
+    pub row_ptr: &'a [u32],
+    pub col: &'a [u32],
+    pub val: &'a [ZkScalar],
+}
+
+impl CsrMatrix<'_> {
+    fn raw(&self) -> sys::bzk_csr {
+        sys::bzk_csr { n_rows: self.row_ptr.len().saturating_sub(1) as u64, row_ptr: self.row_ptr.as_ptr(), col: self.col.as_ptr(), val: scalars_ptr(self.val) }
+    }
+}
+
+impl CircuitMatrices {
+    /// A, B, C over `n_in` inputs (ONE first) and `n_aux` aux variables, rows including bellman's trailing `input_i * 0 = 0` constraints.
+    /// A malformed matrix is `GpuError::Status(BZK_E_ARG, ..)` naming the matrix and the row.
+    pub fn load(params: &ProvingParams, a: &CsrMatrix<'_>, b: &CsrMatrix<'_>, c: &CsrMatrix<'_>, n_in: u32, n_aux: u32) -> Result<Self, GpuError> {
+        assert!(a.col.len() == a.val.len() && b.col.len() == b.val.len() && c.col.len() == c.val.len());
+        assert!(!a.row_ptr.is_empty() && !b.row_ptr.is_empty() && !c.row_ptr.is_empty());
+        let (ra, rb, rc) = (a.raw(), b.raw(), c.raw());
+        let mut h = ptr::null_mut();
+        check(params.gpu.0, unsafe { sys::bzk_r1cs_mats_load(params.gpu.0, &ra, &rb, &rc, n_in, n_aux, &mut h) })?;
+        Ok(CircuitMatrices { h, ctx: params.gpu.0 })
+    }
+
+    /// the same from an instance synthesized with `record_matrices`
+    pub fn from_witness(params: &ProvingParams, witness: &Witness) -> Result<Self, GpuError> {
+        let mut h = ptr::null_mut();
+        check(params.gpu.0, unsafe { sys::bzk_r1cs_mats_from_r1cs(params.gpu.0, witness.0, &mut h) })?;
+        Ok(CircuitMatrices { h, ctx: params.gpu.0 })
+    }
+
+    /// (rows, variables, nnz(A), nnz(B), nnz(C), distinct coefficients, resident bytes)
+    pub fn info(&self) -> [u64; 7] {
+        let mut info = [0u64; 8];
+        let st = unsafe { sys::bzk_r1cs_mats_info(self.h, info.as_mut_ptr()) };
+        assert_eq!(st, sys::BZK_OK);
+        [info[0], info[1], info[2], info[3], info[4], info[5], info[6]]
+    }
+}
+
+impl Drop for CircuitMatrices {
+    fn drop(&mut self) {
+        unsafe { sys::bzk_r1cs_mats_free(self.ctx, self.h) }
+    }
+}
+
+/// `groth16_prove` from the assignment `z` alone (inputs with z[0] = 1, then aux): A.z, B.z, C.z are computed on the device from `mats`.
+/// `check_satisfied`: one product per constraint first - an unsatisfied witness is `GpuError::Status(BZK_E_UNSAT, ..)` naming the first
+/// failing constraint instead of an invalid proof.
+pub fn prove_witness(params: &ProvingParams, mats: &CircuitMatrices, z: &[ZkScalar], r: ZkScalar, s: ZkScalar, check_satisfied: bool) -> Result<Groth16Proof, GpuError> {
+    let flags: u32 = if check_satisfied { sys::BZK_PROVE_CHECK_SAT } else { 0 };
+    let mut buf = [0u8; 387];
+    check(params.gpu.0, unsafe {
+        sys::bzk_groth16_prove_witness(params.gpu.0, params.params, mats.h, scalars_ptr(z), z.len() as u64, &r as *const _ as *const u8, &s as *const _ as *const u8, flags, buf.as_mut_ptr())
+    })?;
+    Ok(bincode::deserialize(&buf)?)
+}
+
 /// `synthesize_work` with the hash-dependent witness values of the work's transitions LEFT TO THE DEVICE (include/bzk.h: BZK_SYNTH_DEFER): the
 /// Poseidon gadget's variables, the Merkle muxes and the root checks - four fifths of a transition - are not evaluated on the host;
 /// `groth16_prove_witness` completes them on the GPU before proving.  All three kinds of work (update, deposit, withdraw).

@@ -126,6 +126,27 @@ struct bzk_ctx {
         if (s__ != BZK_OK) return s__; \
     } while (0)
 
+// the device operations of a staged call (bzk_stage.h Stage<StreamOps>) on the context's stream
+struct StreamOps {
+    bzk_ctx* ctx;
+    int32_t up(void* dev, const void* host, size_t bytes) const {
+        BZK_HIP(ctx, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return BZK_OK;
+    }
+    int32_t down(void* host, const void* dev, size_t bytes) const {
+        BZK_HIP(ctx, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return BZK_OK;
+    }
+    int32_t zero(void* dev, size_t bytes) const {
+        BZK_HIP(ctx, hipMemsetAsync(dev, 0, bytes, ctx->stream));
+        return BZK_OK;
+    }
+    int32_t sync() const {
+        BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return BZK_OK;
+    }
+};
+
 // groth16.hip hooks used by setup.hip
 int32_t bzk_params_alloc_internal(bzk_ctx* ctx, const bzk_params_desc* d, bzk_params** out);
 void bzk_params_buffers_internal(bzk_params* p, void** h, void** l, void** a, void** b_g1, void** b_g2);

@@ -41,6 +41,11 @@ struct WsLayout {
         for (size_t i = 0; i < n_; ++i) buf_[i].set(buf_[i].var, (char*)base + buf_[i].off);
         return true;
     }
+    // instead of a slab: every declared variable gets alloc(its bytes), a block of its own (a CPU harness, whose sanitizer then sees each buffer's end)
+    template <class A>
+    void bind_each(A alloc) const {
+        for (size_t i = 0; i < n_; ++i) buf_[i].set(buf_[i].var, (char*)alloc(buf_[i].bytes));
+    }
     int32_t commit(bzk_ctx* ctx);  // ctx.hip: ws_reserve(bytes()), bind into ctx->ws; BZK_E_INTERNAL on a bad layout or inside another live one
 
 private:

@@ -7,7 +7,7 @@
 #include "bzk_ed25519_sign.h"
 #include "bzk_internal.h"
 #include "bzk_l1.cuh"
-#include "bzk_rounds.h"
+#include "bzk_stage.h"
 #include "host_threads.h"
 
 namespace bzk {
@@ -97,48 +97,30 @@ __global__ void __launch_bounds__(256) l1_tx_sign_hash_kernel(const uint8_t* __r
 
 constexpr uint64_t ED_SIGN_LAUNCH_MAX = (uint64_t)1 << 24;  // rows per launch, as the verifier's
 
-// Overwrites workspace regions that held staged secrets when the call leaves early (a failed copy or launch); the ordinary way out enqueues the
-// same overwrites itself, so that their failure is reported, and disarms this
-struct EdWipeOnError {
-    bzk_ctx* ctx;
-    void *a, *b;
-    size_t na, nb;
-    bool armed = true;
-    ~EdWipeOnError() {
-        if (!armed) return;
-        if (a) (void)hipMemsetAsync(a, 0, na, ctx->stream);
-        if (b) (void)hipMemsetAsync(b, 0, nb, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-};
-
 // exp_dev: 64 bytes for each of min(n, ED_SIGN_LAUNCH_MAX) rows; launches follow one another on the stream, so they share it
 static int32_t ed25519_sign_launch(bzk_ctx* ctx, const void* keys_dev, const void* data_dev, const void* begin_dev, const void* end_dev,
                                    const void* src_at_dev, uint64_t base, int32_t tail, uint64_t n, void* exp_dev, void* sig_dev, void* ok_dev) {
     if (n == 0) return BZK_OK;
     const uint32_t* tab;
     BZK_TRY(ed25519_table_dev(ctx, &tab));
-    for (uint64_t off = 0; off < n; off += ED_SIGN_LAUNCH_MAX) {
-        const uint64_t m = n - off < ED_SIGN_LAUNCH_MAX ? n - off : ED_SIGN_LAUNCH_MAX;
-        BZK_LAUNCH(ctx, "ed25519_sign", ed25519_sign_kernel, dim3((unsigned)((m + ED_SIGN_BLOCK - 1) / ED_SIGN_BLOCK)), dim3(ED_SIGN_BLOCK), 0,
-                   (const uint8_t*)keys_dev + 64 * off, (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off,
+    return launch_rows(n, ED_SIGN_LAUNCH_MAX, ED_SIGN_BLOCK, [&](uint64_t off, uint64_t m, unsigned grid) {
+        BZK_LAUNCH(ctx, "ed25519_sign", ed25519_sign_kernel, dim3(grid), dim3(ED_SIGN_BLOCK), 0, (const uint8_t*)keys_dev + 64 * off,
+                   (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off,
                    src_at_dev ? (const uint64_t*)src_at_dev + off : nullptr, base, tail, m, tab, (uint8_t*)exp_dev, (uint8_t*)sig_dev + 64 * off,
                    ok_dev ? (uint8_t*)ok_dev + off : nullptr);
-    }
-    return BZK_OK;
+        return BZK_OK;
+    });
 }
 static int32_t ed25519_keys_launch(bzk_ctx* ctx, const void* data_dev, const void* begin_dev, const void* end_dev, uint64_t base, uint64_t n,
                                    void* keys_dev) {
     if (n == 0) return BZK_OK;
     const uint32_t* tab;
     BZK_TRY(ed25519_table_dev(ctx, &tab));
-    for (uint64_t off = 0; off < n; off += ED_SIGN_LAUNCH_MAX) {
-        const uint64_t m = n - off < ED_SIGN_LAUNCH_MAX ? n - off : ED_SIGN_LAUNCH_MAX;
-        BZK_LAUNCH(ctx, "ed25519_keys", ed25519_keys_kernel, dim3((unsigned)((m + ED_SIGN_BLOCK - 1) / ED_SIGN_BLOCK)), dim3(ED_SIGN_BLOCK), 0,
-                   (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off, base, m, tab,
-                   (uint8_t*)keys_dev + 64 * off);
-    }
-    return BZK_OK;
+    return launch_rows(n, ED_SIGN_LAUNCH_MAX, ED_SIGN_BLOCK, [&](uint64_t off, uint64_t m, unsigned grid) {
+        BZK_LAUNCH(ctx, "ed25519_keys", ed25519_keys_kernel, dim3(grid), dim3(ED_SIGN_BLOCK), 0, (const uint8_t*)data_dev,
+                   (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off, base, m, tab, (uint8_t*)keys_dev + 64 * off);
+        return BZK_OK;
+    });
 }
 
 // one row on the host: a | prefix on the stack, overwritten before it leaves
@@ -150,48 +132,24 @@ static void sign_row_host(const uint8_t* key, const sha512::Msg& body, uint8_t* 
     for (int k = 0; k < ed25519::EXPANDED_BYTES; ++k) v[k] = 0;
 }
 
-static bool offsets_ok(const uint64_t* off, uint64_t n) {
-    if (off[0] != 0) return false;
-    for (uint64_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
-
 static int32_t mpn_deposits_sign_run(bzk_ctx* ctx, const DpSoA& t, const uint8_t* keys, uint64_t n, uint8_t* sig, uint8_t* ok) {
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> round_at =
-        cut_rounds(n, ED25519_SIGN_ROUND, ED25519_SIGN_ROUND_BYTES, [&](uint64_t i) { return t.rec_off[i + 1] - t.rec_off[i]; });
-    const auto [cap, cap_bytes] = round_caps(round_at, t.rec_off);
-    std::vector<uint64_t> begin(n), end(n), src_at(n);  // relative to their round's first byte
-    for (size_t c = 0; c + 1 < round_at.size(); ++c)
-        for (uint64_t i = round_at[c]; i < round_at[c + 1]; ++i) {
-            begin[i] = t.pay_off[i] - t.rec_off[round_at[c]];
-            end[i] = begin[i] + t.tag_off[i];
-            src_at[i] = begin[i] + t.src_off[i];
-        }
-    WsLayout ws("mpn_deposits_sign_run");
-    uint8_t *dbytes, *dbeg, *dend, *dsrc, *dkeys, *dexp, *dsig, *dok;
-    ws.take(dbytes, cap_bytes); ws.take(dbeg, cap * 8); ws.take(dend, cap * 8); ws.take(dsrc, cap * 8); ws.take(dkeys, cap * 64);
-    ws.take(dexp, cap * 64); ws.take(dsig, cap * 64); ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    EdWipeOnError wipe{ctx, dkeys, dexp, cap * 64, cap * 64};
-    for (size_t c = 0; c + 1 < round_at.size(); ++c) {  // one stream: a round's uploads follow the previous round's kernel
-        const uint64_t off = round_at[c], m = round_at[c + 1] - off;
-        BZK_HIP(ctx, hipMemcpyAsync(dbytes, t.txs + t.rec_off[off], t.rec_off[off + m] - t.rec_off[off], hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dbeg, begin.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dend, end.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dsrc, src_at.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dkeys, keys + off * 64, m * 64, hipMemcpyHostToDevice, ctx->stream));
-        BZK_TRY(ed25519_sign_launch(ctx, dkeys, dbytes, dbeg, dend, dsrc, 0, 0, m, dexp, dsig, dok));  // tail 0: the None tag of the unsigned form
-        BZK_HIP(ctx, hipMemcpyAsync(sig + off * 64, dsig, m * 64, hipMemcpyDeviceToHost, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
+    Stage<StreamOps> st({ctx}, "mpn_deposits_sign_run", n, ED25519_SIGN_ROUND, ED25519_SIGN_ROUND_BYTES,
+                        lengths(t.rec_off), t.rec_off);
+    std::vector<uint64_t> begin = round_bases(st.round_at, t.rec_off), end(n), src_at(n);  // relative to their round's first byte
+    for (uint64_t i = 0; i < n; ++i) {
+        begin[i] = t.pay_off[i] - begin[i];
+        end[i] = begin[i] + t.tag_off[i];
+        src_at[i] = begin[i] + t.src_off[i];
     }
-    BZK_HIP(ctx, hipMemsetAsync(dkeys, 0, cap * 64, ctx->stream));  // neither the staged keys nor their expansions outlive the call
-    BZK_HIP(ctx, hipMemsetAsync(dexp, 0, cap * 64, ctx->stream));
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    wipe.armed = false;
-    return BZK_OK;
+    uint8_t *dbytes, *dbeg, *dend, *dsrc, *dkeys, *dexp, *dsig, *dok;
+    st.bytes(dbytes, t.txs, 0, 0); st.in(dbeg, begin.data(), 8); st.in(dend, end.data(), 8); st.in(dsrc, src_at.data(), 8); st.in(dkeys, keys, 64);
+    st.scratch(dexp, 64); st.out(dsig, sig, 64); st.out(dok, ok, 1);
+    st.wipe(dkeys, st.cap * 64); st.wipe(dexp, st.cap * 64);  // neither the staged keys nor their expansions outlive the call
+    BZK_TRY(st.ws.commit(ctx));
+    // tail 0: the None tag of the unsigned form
+    return st.run([&](uint64_t, uint64_t m) { return ed25519_sign_launch(ctx, dkeys, dbytes, dbeg, dend, dsrc, 0, 0, m, dexp, dsig, dok); });
 }
 
 int32_t mpn_deposits_sign_all(bzk_ctx* ctx, int threads, const DpSoA& t, const uint8_t* keys, uint64_t n, uint8_t* sig, uint8_t* ok) {
@@ -211,46 +169,29 @@ int32_t mpn_deposits_sign_all(bzk_ctx* ctx, int threads, const DpSoA& t, const u
 static int32_t l1_txs_sign_run(bzk_ctx* ctx, const L1SoA& t, const uint8_t* keys, uint64_t n, uint8_t* sig, uint8_t* ok, uint8_t* hash_out) {
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> round_at =
-        cut_rounds(n, ED25519_SIGN_ROUND, ED25519_SIGN_ROUND_BYTES, [&](uint64_t i) { return t.rec_off[i + 1] - t.rec_off[i]; });
-    const auto [cap, cap_bytes] = round_caps(round_at, t.rec_off);
-    const uint64_t hdr_bytes = cap * L1_SIGN_HDR;  // at most 8 MiB in front of at most 64 MiB + one record: offsets stay far below 2^32
-    WsLayout ws("l1_txs_sign_run");
-    uint8_t *dbytes, *dkeys, *dsig, *dok, *dhash;
-    l1::L1Rec* drec;
-    ws.take(dbytes, hdr_bytes + cap_bytes + 8); ws.take(drec, cap); ws.take(dkeys, cap * 64); ws.take(dsig, cap * 64); ws.take(dok, cap);
-    ws.take(dhash, hash_out ? cap * 32 : 32);
-    BZK_TRY(ws.commit(ctx));
+    Stage<StreamOps> st({ctx}, "l1_txs_sign_run", n, ED25519_SIGN_ROUND, ED25519_SIGN_ROUND_BYTES,
+                        lengths(t.rec_off), t.rec_off);
+    const uint64_t hdr_bytes = st.cap * L1_SIGN_HDR;  // at most 8 MiB in front of at most 64 MiB + one record: offsets stay far below 2^32
+    const std::vector<uint64_t> base = round_bases(st.round_at, t.rec_off);
+    std::vector<l1::L1Rec> recs(t.rec, t.rec + n);  // at: behind the lanes' headers, relative to the round's first byte
+    for (uint64_t i = 0; i < n; ++i) recs[i].at = (uint32_t)(hdr_bytes + (t.rec_off[i] - base[i]));
+    uint8_t *dbytes, *drec, *dkeys, *dsig, *dok, *dhash;
+    st.bytes(dbytes, t.txs, hdr_bytes, 8); st.in(drec, recs.data(), sizeof(l1::L1Rec)); st.in(dkeys, keys, 64); st.out(dsig, sig, 64);
+    st.out(dok, ok, 1);
+    if (hash_out) st.out(dhash, hash_out, 32);
+    else st.ws.take(dhash, 32);
+    st.wipe(dkeys, st.cap * 64); st.wipe(dbytes, hdr_bytes);  // the staged keys and the lanes' a | prefix do not outlive the call
+    BZK_TRY(st.ws.commit(ctx));
     const uint32_t* tab;
     BZK_TRY(ed25519_table_dev(ctx, &tab));
-    EdWipeOnError wipe{ctx, dkeys, dbytes, cap * 64, hdr_bytes};
-    std::vector<l1::L1Rec> recs(cap);
-    for (size_t c = 0; c + 1 < round_at.size(); ++c) {  // one stream: a round's uploads follow the previous round's kernels
-        const uint64_t off = round_at[c], m = round_at[c + 1] - off;
-        if (c) BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // recs is reused: the previous round's upload has to have left it
-        for (uint64_t i = 0; i < m; ++i) {
-            recs[i] = t.rec[off + i];
-            recs[i].at = (uint32_t)(hdr_bytes + (t.rec_off[off + i] - t.rec_off[off]));
-        }
-        BZK_HIP(ctx, hipMemcpyAsync(dbytes + hdr_bytes, t.txs + t.rec_off[off], t.rec_off[off + m] - t.rec_off[off], hipMemcpyHostToDevice,
-                                    ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(drec, recs.data(), m * sizeof(l1::L1Rec), hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dkeys, keys + off * 64, m * 64, hipMemcpyHostToDevice, ctx->stream));
+    return st.run([&](uint64_t, uint64_t m) {
         BZK_LAUNCH(ctx, "l1_tx_sign", l1_tx_sign_kernel, dim3((unsigned)((m + ED_SIGN_BLOCK - 1) / ED_SIGN_BLOCK)), dim3(ED_SIGN_BLOCK), 0, dbytes,
                    (const l1::L1Rec*)drec, (const uint8_t*)dkeys, m, tab, dsig, dok);
-        if (hash_out) {
+        if (hash_out)
             BZK_LAUNCH(ctx, "l1_tx_sign_hash", l1_tx_sign_hash_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (const uint8_t*)dbytes,
                        (const l1::L1Rec*)drec, m, (uint32_t*)dhash);
-            BZK_HIP(ctx, hipMemcpyAsync(hash_out + off * 32, dhash, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        BZK_HIP(ctx, hipMemcpyAsync(sig + off * 64, dsig, m * 64, hipMemcpyDeviceToHost, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipMemsetAsync(dkeys, 0, cap * 64, ctx->stream));  // the staged keys and the lanes' a | prefix do not outlive the call
-    BZK_HIP(ctx, hipMemsetAsync(dbytes, 0, hdr_bytes, ctx->stream));
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    wipe.armed = false;
-    return BZK_OK;
+        return BZK_OK;
+    });
 }
 
 int32_t l1_txs_sign_all(bzk_ctx* ctx, int threads, const L1SoA& t, const uint8_t* keys, uint64_t n, uint8_t* sig, uint8_t* ok, uint8_t* hash_out) {
@@ -313,27 +254,15 @@ int32_t bzk_ed25519_sign_batch(bzk_ctx* ctx, const uint8_t* keys, const uint8_t*
         return BZK_OK;
     }
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> round_at =
-        cut_rounds(n, ED25519_SIGN_ROUND, ED25519_SIGN_ROUND_BYTES, [off](uint64_t i) { return off[i + 1] - off[i]; });
-    const auto [cap, cap_bytes] = round_caps(round_at, off);
-    WsLayout ws("bzk_ed25519_sign_batch");
+    Stage<StreamOps> st({ctx}, "bzk_ed25519_sign_batch", n, ED25519_SIGN_ROUND, ED25519_SIGN_ROUND_BYTES,
+                        lengths(off), off);
     uint8_t *ddata, *doff, *dkeys, *dexp, *dsig;
-    ws.take(ddata, cap_bytes + 8); ws.take(doff, (cap + 1) * 8); ws.take(dkeys, cap * 64); ws.take(dexp, cap * 64); ws.take(dsig, cap * 64);
-    BZK_TRY(ws.commit(ctx));
-    EdWipeOnError wipe{ctx, dkeys, dexp, cap * 64, cap * 64};
-    for (size_t c = 0; c + 1 < round_at.size(); ++c) {  // one stream: a round's uploads follow the previous round's kernel
-        const uint64_t a = round_at[c], m = round_at[c + 1] - a, bytes = off[a + m] - off[a];
-        if (bytes) BZK_HIP(ctx, hipMemcpyAsync(ddata, msg + off[a], bytes, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(doff, off + a, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dkeys, keys + a * 64, m * 64, hipMemcpyHostToDevice, ctx->stream));
-        BZK_TRY(ed25519_sign_launch(ctx, dkeys, ddata, doff, doff + 8, nullptr, off[a], -1, m, dexp, dsig, nullptr));
-        BZK_HIP(ctx, hipMemcpyAsync(sig_out + a * 64, dsig, m * 64, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipMemsetAsync(dkeys, 0, cap * 64, ctx->stream));  // neither the staged keys nor their expansions outlive the call
-    BZK_HIP(ctx, hipMemsetAsync(dexp, 0, cap * 64, ctx->stream));
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    wipe.armed = false;
-    return BZK_OK;
+    st.bytes(ddata, msg, 0, 8); st.offsets(doff); st.in(dkeys, keys, 64); st.scratch(dexp, 64); st.out(dsig, sig_out, 64);
+    st.wipe(dkeys, st.cap * 64); st.wipe(dexp, st.cap * 64);  // neither the staged keys nor their expansions outlive the call
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t a, uint64_t m) {
+        return ed25519_sign_launch(ctx, dkeys, ddata, doff, doff + 8, nullptr, off[a], -1, m, dexp, dsig, nullptr);
+    });
 }
 
 int32_t bzk_ed25519_keys_batch_dev(bzk_ctx* ctx, const void* seeds_dev, const void* off_dev, uint64_t n, void* keys_out_dev) {
@@ -355,26 +284,13 @@ int32_t bzk_ed25519_keys_batch(bzk_ctx* ctx, const uint8_t* seeds, const uint64_
         return BZK_OK;
     }
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> round_at =
-        cut_rounds(n, ED25519_SIGN_ROUND, ED25519_SIGN_ROUND_BYTES, [off](uint64_t i) { return off[i + 1] - off[i]; });
-    const auto [cap, cap_bytes] = round_caps(round_at, off);
-    WsLayout ws("bzk_ed25519_keys_batch");
+    Stage<StreamOps> st({ctx}, "bzk_ed25519_keys_batch", n, ED25519_SIGN_ROUND, ED25519_SIGN_ROUND_BYTES,
+                        lengths(off), off);
     uint8_t *ddata, *doff, *dkeys;
-    ws.take(ddata, cap_bytes + 8); ws.take(doff, (cap + 1) * 8); ws.take(dkeys, cap * 64);
-    BZK_TRY(ws.commit(ctx));
-    EdWipeOnError wipe{ctx, ddata, dkeys, cap_bytes + 8, cap * 64};
-    for (size_t c = 0; c + 1 < round_at.size(); ++c) {
-        const uint64_t a = round_at[c], m = round_at[c + 1] - a, bytes = off[a + m] - off[a];
-        if (bytes) BZK_HIP(ctx, hipMemcpyAsync(ddata, seeds + off[a], bytes, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(doff, off + a, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_TRY(ed25519_keys_launch(ctx, ddata, doff, doff + 8, off[a], m, dkeys));
-        BZK_HIP(ctx, hipMemcpyAsync(keys_out + a * 64, dkeys, m * 64, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipMemsetAsync(ddata, 0, cap_bytes + 8, ctx->stream));  // neither the staged seeds nor the keys outlive the call
-    BZK_HIP(ctx, hipMemsetAsync(dkeys, 0, cap * 64, ctx->stream));
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    wipe.armed = false;
-    return BZK_OK;
+    st.bytes(ddata, seeds, 0, 8); st.offsets(doff); st.out(dkeys, keys_out, 64);
+    st.wipe(ddata, st.cap_bytes + 8); st.wipe(dkeys, st.cap * 64);  // neither the staged seeds nor the keys outlive the call
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t a, uint64_t m) { return ed25519_keys_launch(ctx, ddata, doff, doff + 8, off[a], m, dkeys); });
 }
 
 int32_t bzk_host_ed25519_keys(const uint8_t* seed, uint64_t len, uint8_t keys_out[64]) {

@@ -10,7 +10,7 @@
 #include "bzk_ed25519.cuh"
 #include "bzk_l1.cuh"
 #include "bzk_internal.h"
-#include "bzk_rounds.h"
+#include "bzk_stage.h"
 #include "host_threads.h"
 
 namespace bzk {
@@ -251,22 +251,19 @@ int32_t jubjub_verify_launch(bzk_ctx* ctx, const void* pub_xy_dev, const void* m
     BZK_TRY(poseidon_consts_dev_shared(ctx, 6, &pconsts, &rf, &rp));
     const Fr29* tab;
     BZK_TRY(eddsa_table_dev(ctx, &tab));
-    for (uint64_t off = 0; off < n; off += EDDSA_LAUNCH_MAX) {
-        const uint64_t m = n - off < EDDSA_LAUNCH_MAX ? n - off : EDDSA_LAUNCH_MAX;
-        BZK_LAUNCH(ctx, "jubjub_verify", jubjub_verify_kernel, dim3((unsigned)((m + EDDSA_BLOCK - 1) / EDDSA_BLOCK)), dim3(EDDSA_BLOCK), 0,
-                   (const Fr*)pub_xy_dev + 2 * off, (const Fr*)msg_dev + off, (const Fr*)sig_dev + 3 * off, m, (const Fr29*)pconsts, rf, rp, tab,
-                   (uint8_t*)ok_dev + off);
-    }
-    return BZK_OK;
+    return launch_rows(n, EDDSA_LAUNCH_MAX, EDDSA_BLOCK, [&](uint64_t off, uint64_t m, unsigned grid) {
+        BZK_LAUNCH(ctx, "jubjub_verify", jubjub_verify_kernel, dim3(grid), dim3(EDDSA_BLOCK), 0, (const Fr*)pub_xy_dev + 2 * off,
+                   (const Fr*)msg_dev + off, (const Fr*)sig_dev + 3 * off, m, (const Fr29*)pconsts, rf, rp, tab, (uint8_t*)ok_dev + off);
+        return BZK_OK;
+    });
 }
 
 int32_t jubjub_decompress_launch(bzk_ctx* ctx, const void* x_dev, const void* odd_dev, uint64_t n, void* xy_dev, void* ok_dev) {
-    for (uint64_t off = 0; off < n; off += EDDSA_LAUNCH_MAX) {
-        const uint64_t m = n - off < EDDSA_LAUNCH_MAX ? n - off : EDDSA_LAUNCH_MAX;
-        BZK_LAUNCH(ctx, "jubjub_decompress", jubjub_decompress_kernel, dim3((unsigned)((m + DECOMPRESS_BLOCK - 1) / DECOMPRESS_BLOCK)),
-                   dim3(DECOMPRESS_BLOCK), 0, (const Fr*)x_dev + off, (const uint8_t*)odd_dev + off, m, (Fr*)xy_dev + 2 * off, (uint8_t*)ok_dev + off);
-    }
-    return BZK_OK;
+    return launch_rows(n, EDDSA_LAUNCH_MAX, DECOMPRESS_BLOCK, [&](uint64_t off, uint64_t m, unsigned grid) {
+        BZK_LAUNCH(ctx, "jubjub_decompress", jubjub_decompress_kernel, dim3(grid), dim3(DECOMPRESS_BLOCK), 0, (const Fr*)x_dev + off,
+                   (const uint8_t*)odd_dev + off, m, (Fr*)xy_dev + 2 * off, (uint8_t*)ok_dev + off);
+        return BZK_OK;
+    });
 }
 
 // MpnTransaction::verify_signature for n parsed transactions (TxSoA from wire.hip, parsed by host_bincode.h): per chunk one decompress launch over
@@ -275,22 +272,15 @@ int32_t jubjub_decompress_launch(bzk_ctx* ctx, const void* x_dev, const void* od
 int32_t mpn_tx_verify_run(bzk_ctx* ctx, const TxSoA& t, uint64_t n, uint8_t* ok, uint8_t* hash_out, uint8_t* src_xy_out, uint8_t* dst_xy_out) {
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    const uint64_t cap = n < MPN_TX_CHUNK ? n : MPN_TX_CHUNK;
-    WsLayout ws("mpn_tx_verify_run");
+    Stage<StreamOps> st({ctx}, "mpn_tx_verify_run", n, MPN_TX_CHUNK);
     uint8_t *dkx, *dodd, *dxy, *dkok, *dtok, *dnums, *dsig, *dtup, *dmsg, *dfit, *dver, *dok;
-    ws.take(dkx, cap * 64); ws.take(dodd, cap * 2); ws.take(dxy, cap * 128); ws.take(dkok, cap * 2);  // both keys of every transaction
-    ws.take(dtok, cap * 64); ws.take(dnums, cap * 24); ws.take(dsig, cap * 96); ws.take(dtup, cap * 224); ws.take(dmsg, cap * 32);
-    ws.take(dfit, cap); ws.take(dver, cap); ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    for (uint64_t off = 0; off < n; off += MPN_TX_CHUNK) {  // one stream: a chunk's uploads follow the previous chunk's kernels
-        const uint64_t m = n - off < MPN_TX_CHUNK ? n - off : MPN_TX_CHUNK;
-        BZK_HIP(ctx, hipMemcpyAsync(dkx, t.src_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dkx + m * 32, t.dst_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dodd, t.src_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dodd + m, t.dst_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dtok, t.tok + off * 64, m * 64, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dnums, t.nums + off * 3, m * 24, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dsig, t.sig + off * 96, m * 96, hipMemcpyHostToDevice, ctx->stream));
+    // both keys of every transaction: the m src keys, then the m dst keys
+    st.in(dkx, t.src_x, 32, 2); st.in_part(dkx, t.dst_x, 32, 1); st.in(dodd, t.src_odd, 1, 2); st.in_part(dodd, t.dst_odd, 1, 1);
+    st.out(dxy, src_xy_out, 64, 2); st.out_part(dxy, dst_xy_out, 64, 1); st.scratch(dkok, 2);
+    st.in(dtok, t.tok, 64); st.in(dnums, t.nums, 24); st.in(dsig, t.sig, 96); st.scratch(dtup, 224); st.out(dmsg, hash_out, 32);
+    st.scratch(dfit, 1); st.scratch(dver, 1); st.out(dok, ok, 1);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t, uint64_t m) {
         BZK_TRY(jubjub_decompress_launch(ctx, dkx, dodd, 2 * m, dxy, dkok));
         const dim3 grid((unsigned)((m + 255) / 256));
         BZK_LAUNCH(ctx, "mpn_tx_tuple", mpn_tx_tuple_kernel, grid, dim3(256), 0, (const uint64_t*)dnums, (const Fr*)dtok, (const Fr*)(dxy + m * 64),
@@ -298,25 +288,18 @@ int32_t mpn_tx_verify_run(bzk_ctx* ctx, const TxSoA& t, uint64_t n, uint8_t* ok,
         BZK_TRY(poseidon_launch(ctx, dtup, 7, m, dmsg));
         BZK_TRY(jubjub_verify_launch(ctx, dxy, dmsg, dsig, m, dver));
         BZK_LAUNCH(ctx, "mpn_tx_verdict", mpn_tx_verdict_kernel, grid, dim3(256), 0, dver, dkok, dfit, m, (Fr*)dmsg, dok);
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-        if (hash_out) BZK_HIP(ctx, hipMemcpyAsync(hash_out + off * 32, dmsg, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (src_xy_out) BZK_HIP(ctx, hipMemcpyAsync(src_xy_out + off * 64, dxy, m * 64, hipMemcpyDeviceToHost, ctx->stream));
-        if (dst_xy_out) BZK_HIP(ctx, hipMemcpyAsync(dst_xy_out + off * 64, dxy + m * 64, m * 64, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BZK_OK;
+        return BZK_OK;
+    });
 }
 
 int32_t sha3_256_launch(bzk_ctx* ctx, const void* data_dev, const void* begin_dev, const void* end_dev, uint64_t base, const void* blank_dev,
                         uint64_t n, void* digest_dev, void* scalar_dev) {
-    for (uint64_t off = 0; off < n; off += EDDSA_LAUNCH_MAX) {
-        const uint64_t m = n - off < EDDSA_LAUNCH_MAX ? n - off : EDDSA_LAUNCH_MAX;
-        BZK_LAUNCH(ctx, "sha3_256", sha3_256_kernel, dim3((unsigned)((m + SHA3_BLOCK - 1) / SHA3_BLOCK)), dim3(SHA3_BLOCK), 0,
-                   (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off, base,
-                   blank_dev ? (const uint32_t*)blank_dev + off : nullptr, m, digest_dev ? (uint32_t*)digest_dev + 8 * off : nullptr,
-                   scalar_dev ? (Fr*)scalar_dev + off : nullptr);
-    }
-    return BZK_OK;
+    return launch_rows(n, EDDSA_LAUNCH_MAX, SHA3_BLOCK, [&](uint64_t off, uint64_t m, unsigned grid) {
+        BZK_LAUNCH(ctx, "sha3_256", sha3_256_kernel, dim3(grid), dim3(SHA3_BLOCK), 0, (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off,
+                   (const uint64_t*)end_dev + off, base, blank_dev ? (const uint32_t*)blank_dev + off : nullptr, m,
+                   digest_dev ? (uint32_t*)digest_dev + 8 * off : nullptr, scalar_dev ? (Fr*)scalar_dev + off : nullptr);
+        return BZK_OK;
+    });
 }
 
 // MpnWithdraw::verify_signature and verify_calldata for n parsed records (WdSoA from wire.hip, parsed by host_bincode.h).  A chunk ends at
@@ -327,31 +310,19 @@ int32_t sha3_256_launch(bzk_ctx* ctx, const void* data_dev, const void* begin_de
 int32_t mpn_withdraw_verify_run(bzk_ctx* ctx, const WdSoA& t, uint64_t n, uint8_t* ok, uint8_t* fp_out, uint8_t* xy_out) {
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> chunk_at = cut_rounds(n, MPN_TX_CHUNK, MPN_WD_CHUNK_BYTES, [&](uint64_t i) { return (uint64_t)t.pay_len[i]; });
-    const auto [cap, cap_bytes] = round_caps(chunk_at, t.rec_off);
-    std::vector<uint64_t> begin(n), end(n);  // payment ranges relative to their chunk's first byte
-    for (size_t c = 0; c + 1 < chunk_at.size(); ++c)
-        for (uint64_t i = chunk_at[c]; i < chunk_at[c + 1]; ++i) {
-            begin[i] = t.pay_off[i] - t.rec_off[chunk_at[c]];
-            end[i] = begin[i] + t.pay_len[i];
-        }
-    WsLayout ws("mpn_withdraw_verify_run");
+    Stage<StreamOps> st({ctx}, "mpn_withdraw_verify_run", n, MPN_TX_CHUNK, MPN_WD_CHUNK_BYTES, [&](uint64_t i) { return (uint64_t)t.pay_len[i]; }, t.rec_off);
+    std::vector<uint64_t> begin = round_bases(st.round_at, t.rec_off), end(n);  // payment ranges relative to their chunk's first byte
+    for (uint64_t i = 0; i < n; ++i) {
+        begin[i] = t.pay_off[i] - begin[i];
+        end[i] = begin[i] + t.pay_len[i];
+    }
     uint8_t *dbytes, *dbeg, *dend, *dcd, *dnonce, *dkx, *dfp, *dmsg, *dcall, *dxy, *dh2, *dsig, *dh6, *dodd, *dkok, *dfit, *dver, *dok;
-    ws.take(dbytes, cap_bytes); ws.take(dbeg, cap * 8); ws.take(dend, cap * 8); ws.take(dcd, cap * 4); ws.take(dnonce, cap * 4);
-    ws.take(dkx, cap * 32); ws.take(dfp, cap * 32); ws.take(dmsg, cap * 32); ws.take(dcall, cap * 32);
-    ws.take(dxy, cap * 64); ws.take(dh2, cap * 64); ws.take(dsig, cap * 96); ws.take(dh6, cap * 192);
-    ws.take(dodd, cap); ws.take(dkok, cap); ws.take(dfit, cap); ws.take(dver, cap); ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {  // one stream: a chunk's uploads follow the previous chunk's kernels
-        const uint64_t off = chunk_at[c], m = chunk_at[c + 1] - off;
-        BZK_HIP(ctx, hipMemcpyAsync(dbytes, t.txs + t.rec_off[off], t.rec_off[off + m] - t.rec_off[off], hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dbeg, begin.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dend, end.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dcd, t.cd_off + off, m * 4, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dnonce, t.nonce + off, m * 4, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dkx, t.key_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dodd, t.key_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dsig, t.sig + off * 96, m * 96, hipMemcpyHostToDevice, ctx->stream));
+    st.bytes(dbytes, t.txs, 0, 0); st.in(dbeg, begin.data(), 8); st.in(dend, end.data(), 8); st.in(dcd, t.cd_off, 4); st.in(dnonce, t.nonce, 4);
+    st.in(dkx, t.key_x, 32); st.out(dfp, fp_out, 32); st.scratch(dmsg, 32); st.scratch(dcall, 32);
+    st.out(dxy, xy_out, 64); st.scratch(dh2, 64); st.in(dsig, t.sig, 96); st.scratch(dh6, 192);
+    st.in(dodd, t.key_odd, 1); st.scratch(dkok, 1); st.scratch(dfit, 1); st.scratch(dver, 1); st.out(dok, ok, 1);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t, uint64_t m) {
         BZK_TRY(sha3_256_launch(ctx, dbytes, dbeg, dend, 0, dcd, m, nullptr, dfp));
         BZK_TRY(jubjub_decompress_launch(ctx, dkx, dodd, m, dxy, dkok));
         const dim3 grid((unsigned)((m + 255) / 256));
@@ -362,12 +333,8 @@ int32_t mpn_withdraw_verify_run(bzk_ctx* ctx, const WdSoA& t, uint64_t n, uint8_
         BZK_TRY(jubjub_verify_launch(ctx, dxy, dmsg, dsig, m, dver));
         BZK_LAUNCH(ctx, "mpn_withdraw_verdict", mpn_withdraw_verdict_kernel, grid, dim3(256), 0, dver, dfit, (const Fr*)dcall, dbytes,
                    (const uint64_t*)dbeg, (const uint32_t*)dcd, m, dok);
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-        if (fp_out) BZK_HIP(ctx, hipMemcpyAsync(fp_out + off * 32, dfp, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (xy_out) BZK_HIP(ctx, hipMemcpyAsync(xy_out + off * 64, dxy, m * 64, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BZK_OK;
+        return BZK_OK;
+    });
 }
 
 int32_t ed25519_table_dev(bzk_ctx* ctx, const uint32_t** out) {
@@ -388,13 +355,11 @@ int32_t ed25519_table_dev(bzk_ctx* ctx, const uint32_t** out) {
 
 static int32_t sha512_launch(bzk_ctx* ctx, const void* data_dev, const void* begin_dev, const void* end_dev, uint64_t base, uint64_t n,
                              void* digest_dev) {
-    for (uint64_t off = 0; off < n; off += EDDSA_LAUNCH_MAX) {
-        const uint64_t m = n - off < EDDSA_LAUNCH_MAX ? n - off : EDDSA_LAUNCH_MAX;
-        BZK_LAUNCH(ctx, "sha512", sha512_kernel, dim3((unsigned)((m + SHA512_BLOCK - 1) / SHA512_BLOCK)), dim3(SHA512_BLOCK), 0,
-                   (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off, base, m,
-                   (uint32_t*)digest_dev + 16 * off);
-    }
-    return BZK_OK;
+    return launch_rows(n, EDDSA_LAUNCH_MAX, SHA512_BLOCK, [&](uint64_t off, uint64_t m, unsigned grid) {
+        BZK_LAUNCH(ctx, "sha512", sha512_kernel, dim3(grid), dim3(SHA512_BLOCK), 0, (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off,
+                   (const uint64_t*)end_dev + off, base, m, (uint32_t*)digest_dev + 16 * off);
+        return BZK_OK;
+    });
 }
 // pk_at_dev / sig_at_dev null: keys and signatures are packed arrays
 static int32_t ed25519_verify_launch(bzk_ctx* ctx, const void* pk_dev, const void* pk_at_dev, const void* sig_dev, const void* sig_at_dev,
@@ -403,15 +368,14 @@ static int32_t ed25519_verify_launch(bzk_ctx* ctx, const void* pk_dev, const voi
     if (n == 0) return BZK_OK;
     const uint32_t* tab;
     BZK_TRY(ed25519_table_dev(ctx, &tab));
-    for (uint64_t off = 0; off < n; off += EDDSA_LAUNCH_MAX) {
-        const uint64_t m = n - off < EDDSA_LAUNCH_MAX ? n - off : EDDSA_LAUNCH_MAX;
-        BZK_LAUNCH(ctx, "ed25519_verify", ed25519_verify_kernel, dim3((unsigned)((m + ED25519_BLOCK - 1) / ED25519_BLOCK)), dim3(ED25519_BLOCK), 0,
+    return launch_rows(n, EDDSA_LAUNCH_MAX, ED25519_BLOCK, [&](uint64_t off, uint64_t m, unsigned grid) {
+        BZK_LAUNCH(ctx, "ed25519_verify", ed25519_verify_kernel, dim3(grid), dim3(ED25519_BLOCK), 0,
                    (const uint8_t*)pk_dev + (pk_at_dev ? 0 : 32 * off), pk_at_dev ? (const uint64_t*)pk_at_dev + off : nullptr,
                    (const uint8_t*)sig_dev + (sig_at_dev ? 0 : 64 * off), sig_at_dev ? (const uint64_t*)sig_at_dev + off : nullptr,
                    (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off, base, tail, m, tab,
                    (uint8_t*)ok_dev + off);
-    }
-    return BZK_OK;
+        return BZK_OK;
+    });
 }
 
 uint8_t mpn_deposit_sig_host(const DpSoA& t, uint64_t i) {
@@ -428,52 +392,30 @@ uint8_t mpn_deposit_sig_host(const DpSoA& t, uint64_t i) {
 int32_t mpn_deposit_verify_run(bzk_ctx* ctx, const DpSoA& t, uint64_t n, uint8_t* ok, uint8_t* xy_out) {
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> chunk_at = cut_rounds(n, MPN_TX_CHUNK, MPN_WD_CHUNK_BYTES, [&](uint64_t i) { return t.rec_off[i + 1] - t.pay_off[i]; });
-    const auto [cap, cap_bytes] = round_caps(chunk_at, t.rec_off);
-    std::vector<uint64_t> begin(n), end(n), pk_at(n), sig_at(n);  // relative to their chunk's first byte
-    for (size_t c = 0; c + 1 < chunk_at.size(); ++c)
-        for (uint64_t i = chunk_at[c]; i < chunk_at[c + 1]; ++i) {
-            begin[i] = t.pay_off[i] - t.rec_off[chunk_at[c]];
-            end[i] = begin[i] + t.tag_off[i];
-            pk_at[i] = begin[i] + t.src_off[i];
-            sig_at[i] = begin[i] + t.sig_off[i];
-        }
-    WsLayout ws("mpn_deposit_verify_run");
+    Stage<StreamOps> st({ctx}, "mpn_deposit_verify_run", n, MPN_TX_CHUNK, MPN_WD_CHUNK_BYTES, [&](uint64_t i) { return t.rec_off[i + 1] - t.pay_off[i]; },
+                        t.rec_off);
+    std::vector<uint64_t> begin = round_bases(st.round_at, t.rec_off), end(n), pk_at(n), sig_at(n);  // relative to their chunk's first byte
+    for (uint64_t i = 0; i < n; ++i) {
+        begin[i] = t.pay_off[i] - begin[i];
+        end[i] = begin[i] + t.tag_off[i];
+        pk_at[i] = begin[i] + t.src_off[i];
+        sig_at[i] = begin[i] + t.sig_off[i];
+    }
     uint8_t *dbytes, *dbeg, *dend, *dpk, *dsg, *dkx, *dxy, *dodd, *dhas, *dkok, *dver, *dok;
-    ws.take(dbytes, cap_bytes); ws.take(dbeg, cap * 8); ws.take(dend, cap * 8); ws.take(dpk, cap * 8); ws.take(dsg, cap * 8);
-    ws.take(dkx, cap * 32); ws.take(dxy, cap * 64); ws.take(dodd, cap); ws.take(dhas, cap); ws.take(dkok, cap); ws.take(dver, cap);
-    ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {  // one stream: a chunk's uploads follow the previous chunk's kernels
-        const uint64_t off = chunk_at[c], m = chunk_at[c + 1] - off;
-        BZK_HIP(ctx, hipMemcpyAsync(dbytes, t.txs + t.rec_off[off], t.rec_off[off + m] - t.rec_off[off], hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dbeg, begin.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dend, end.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dpk, pk_at.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dsg, sig_at.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dkx, t.key_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dodd, t.key_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dhas, t.has_sig + off, m, hipMemcpyHostToDevice, ctx->stream));
+    st.bytes(dbytes, t.txs, 0, 0); st.in(dbeg, begin.data(), 8); st.in(dend, end.data(), 8); st.in(dpk, pk_at.data(), 8); st.in(dsg, sig_at.data(), 8);
+    st.in(dkx, t.key_x, 32); st.out(dxy, xy_out, 64); st.in(dodd, t.key_odd, 1); st.in(dhas, t.has_sig, 1); st.scratch(dkok, 1); st.scratch(dver, 1);
+    st.out(dok, ok, 1);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t, uint64_t m) {
         BZK_TRY(ed25519_verify_launch(ctx, dbytes, dpk, dbytes, dsg, dbytes, dbeg, dend, 0, 0, m, dver));
         BZK_TRY(jubjub_decompress_launch(ctx, dkx, dodd, m, dxy, dkok));
         BZK_LAUNCH(ctx, "mpn_deposit_verdict", mpn_deposit_verdict_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, dver, dhas, dkok, m, dok);
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-        if (xy_out) BZK_HIP(ctx, hipMemcpyAsync(xy_out + off * 64, dxy, m * 64, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BZK_OK;
+        return BZK_OK;
+    });
 }
 
-// the rounds of a host batch of messages (off: n + 1 byte offsets): at most `chunk` messages or `chunk_bytes` bytes each, and at least one message
-static std::vector<uint64_t> message_rounds(const uint64_t* off, uint64_t n, uint64_t chunk, uint64_t chunk_bytes) {
-    return cut_rounds(n, chunk, chunk_bytes, [off](uint64_t i) { return off[i + 1] - off[i]; });
-}
-static bool offsets_ok(const uint64_t* off, uint64_t n) {
-    if (off[0] != 0) return false;
-    for (uint64_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
+// the rounds of a host batch of messages: at most 2^20 messages or 64 MiB each, and at least one message
+constexpr uint64_t MSG_ROUND = (uint64_t)1 << 20, MSG_ROUND_BYTES = (uint64_t)64 << 20;
 
 // ---- wire-form L1 transactions and the block root (bzk_l1.cuh) -------------------------------------------------------------------------------
 // The layout of a call's m trees: where each tree's nodes and leaves lie and, per level, which lanes are whose.  Host arithmetic only.
@@ -593,7 +535,7 @@ int32_t l1_check_run(bzk_ctx* ctx, const L1SoA& t, uint64_t n, const uint64_t* c
     (void)hipSetDevice(ctx->device);
     MerklePlan P;
     if (count && !P.build(count, m)) return BZK_E_ARG;
-    const std::vector<uint64_t> chunk_at = message_rounds(t.rec_off, n, l1::CHUNK, l1::CHUNK_BYTES);
+    const std::vector<uint64_t> chunk_at = cut_rounds(n, l1::CHUNK, l1::CHUNK_BYTES, lengths(t.rec_off));
     const auto [cap, cap_bytes] = round_caps(chunk_at, t.rec_off);
     const bool want_hash = hash_out || count;
     WsLayout ws("l1_check_run");
@@ -651,22 +593,11 @@ int32_t bzk_jubjub_verify_batch(bzk_ctx* ctx, const uint8_t* pub_xy, const uint8
     if (!ctx || (n && (!pub_xy || !msg || !sig || !ok))) return BZK_E_ARG;
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    constexpr uint64_t CHUNK = (uint64_t)1 << 20;  // 193 bytes per signature: at most 193 MB of workspace
-    const uint64_t cap = n < CHUNK ? n : CHUNK;
-    WsLayout ws("bzk_jubjub_verify_batch");
+    Stage<StreamOps> st({ctx}, "bzk_jubjub_verify_batch", n, (uint64_t)1 << 20);  // 193 bytes per signature: at most 193 MB of workspace
     uint8_t *dpub, *dmsg, *dsig, *dok;
-    ws.take(dpub, cap * 64); ws.take(dmsg, cap * 32); ws.take(dsig, cap * 96); ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    for (uint64_t off = 0; off < n; off += CHUNK) {  // one stream: a chunk's uploads follow the previous chunk's kernel
-        const uint64_t m = n - off < CHUNK ? n - off : CHUNK;
-        BZK_HIP(ctx, hipMemcpyAsync(dpub, pub_xy + off * 64, m * 64, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dmsg, msg + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dsig, sig + off * 96, m * 96, hipMemcpyHostToDevice, ctx->stream));
-        BZK_TRY(jubjub_verify_launch(ctx, dpub, dmsg, dsig, m, dok));
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BZK_OK;
+    st.in(dpub, pub_xy, 64); st.in(dmsg, msg, 32); st.in(dsig, sig, 96); st.out(dok, ok, 1);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t, uint64_t m) { return jubjub_verify_launch(ctx, dpub, dmsg, dsig, m, dok); });
 }
 
 int32_t bzk_jubjub_decompress_batch_dev(bzk_ctx* ctx, const void* x_dev, const void* odd_dev, uint64_t n, void* xy_out_dev, void* ok_dev) {
@@ -680,22 +611,11 @@ int32_t bzk_jubjub_decompress_batch(bzk_ctx* ctx, const uint8_t* x, const uint8_
     if (!ctx || (n && (!x || !odd || !xy_out || !ok))) return BZK_E_ARG;
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    constexpr uint64_t CHUNK = (uint64_t)1 << 20;  // 98 bytes per key
-    const uint64_t cap = n < CHUNK ? n : CHUNK;
-    WsLayout ws("bzk_jubjub_decompress_batch");
+    Stage<StreamOps> st({ctx}, "bzk_jubjub_decompress_batch", n, (uint64_t)1 << 20);  // 98 bytes per key
     uint8_t *dx, *dodd, *dxy, *dok;
-    ws.take(dx, cap * 32); ws.take(dodd, cap); ws.take(dxy, cap * 64); ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    for (uint64_t off = 0; off < n; off += CHUNK) {
-        const uint64_t m = n - off < CHUNK ? n - off : CHUNK;
-        BZK_HIP(ctx, hipMemcpyAsync(dx, x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dodd, odd + off, m, hipMemcpyHostToDevice, ctx->stream));
-        BZK_TRY(jubjub_decompress_launch(ctx, dx, dodd, m, dxy, dok));
-        BZK_HIP(ctx, hipMemcpyAsync(xy_out + off * 64, dxy, m * 64, hipMemcpyDeviceToHost, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BZK_OK;
+    st.in(dx, x, 32); st.in(dodd, odd, 1); st.out(dxy, xy_out, 64); st.out(dok, ok, 1);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t, uint64_t m) { return jubjub_decompress_launch(ctx, dx, dodd, m, dxy, dok); });
 }
 
 // decompress, then verify: a key that does not decompress leaves (0, 0), which is off the curve, so the verifier's verdict is already 0.  The
@@ -718,25 +638,15 @@ int32_t bzk_jubjub_verify_batch_compressed(bzk_ctx* ctx, const uint8_t* pk_x, co
     if (!ctx || (n && (!pk_x || !pk_odd || !msg || !sig || !ok))) return BZK_E_ARG;
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    constexpr uint64_t CHUNK = (uint64_t)1 << 20;  // 227 bytes per signature
-    const uint64_t cap = n < CHUNK ? n : CHUNK;
-    WsLayout ws("bzk_jubjub_verify_batch_compressed");
+    Stage<StreamOps> st({ctx}, "bzk_jubjub_verify_batch_compressed", n, (uint64_t)1 << 20);  // 227 bytes per signature
     uint8_t *dx, *dodd, *dxy, *dkok, *dmsg, *dsig, *dok;
-    ws.take(dx, cap * 32); ws.take(dodd, cap); ws.take(dxy, cap * 64); ws.take(dkok, cap);
-    ws.take(dmsg, cap * 32); ws.take(dsig, cap * 96); ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    for (uint64_t off = 0; off < n; off += CHUNK) {
-        const uint64_t m = n - off < CHUNK ? n - off : CHUNK;
-        BZK_HIP(ctx, hipMemcpyAsync(dx, pk_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dodd, pk_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dmsg, msg + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dsig, sig + off * 96, m * 96, hipMemcpyHostToDevice, ctx->stream));
+    st.in(dx, pk_x, 32); st.in(dodd, pk_odd, 1); st.scratch(dxy, 64); st.scratch(dkok, 1);
+    st.in(dmsg, msg, 32); st.in(dsig, sig, 96); st.out(dok, ok, 1);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t, uint64_t m) {
         BZK_TRY(jubjub_decompress_launch(ctx, dx, dodd, m, dxy, dkok));
-        BZK_TRY(jubjub_verify_launch(ctx, dxy, dmsg, dsig, m, dok));
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BZK_OK;
+        return jubjub_verify_launch(ctx, dxy, dmsg, dsig, m, dok);
+    });
 }
 
 int32_t bzk_sha3_256_batch_dev(bzk_ctx* ctx, const void* data_dev, const void* off_dev, uint64_t n, void* digest_out_dev, void* scalar_out_dev) {
@@ -749,26 +659,15 @@ int32_t bzk_sha3_256_batch_dev(bzk_ctx* ctx, const void* data_dev, const void* o
 int32_t bzk_sha3_256_batch(bzk_ctx* ctx, const uint8_t* data, const uint64_t* off, uint64_t n, uint8_t* digest_out, uint8_t* scalar_out) {
     if (!ctx || (n && (!data || !off || (!digest_out && !scalar_out)))) return BZK_E_ARG;
     if (n == 0) return BZK_OK;
-    if (off[0] != 0) return BZK_E_ARG;
-    for (uint64_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return BZK_E_ARG;
+    if (!offsets_ok(off, n)) return BZK_E_ARG;
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> chunk_at = message_rounds(off, n, (uint64_t)1 << 20, (uint64_t)64 << 20);
-    const auto [cap, cap_bytes] = round_caps(chunk_at, off);
-    WsLayout ws("bzk_sha3_256_batch");
+    Stage<StreamOps> st({ctx}, "bzk_sha3_256_batch", n, MSG_ROUND, MSG_ROUND_BYTES, lengths(off), off);
     uint8_t *ddata, *doff, *ddig, *dsc;
-    ws.take(ddata, cap_bytes ? cap_bytes : 1); ws.take(doff, (cap + 1) * 8); ws.take(ddig, cap * 32); ws.take(dsc, cap * 32);
-    BZK_TRY(ws.commit(ctx));
-    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {
-        const uint64_t a = chunk_at[c], m = chunk_at[c + 1] - a, bytes = off[a + m] - off[a];
-        if (bytes) BZK_HIP(ctx, hipMemcpyAsync(ddata, data + off[a], bytes, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(doff, off + a, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_TRY(sha3_256_launch(ctx, ddata, doff, doff + 8, off[a], nullptr, m, digest_out ? ddig : nullptr, scalar_out ? dsc : nullptr));
-        if (digest_out) BZK_HIP(ctx, hipMemcpyAsync(digest_out + a * 32, ddig, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (scalar_out) BZK_HIP(ctx, hipMemcpyAsync(scalar_out + a * 32, dsc, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BZK_OK;
+    st.bytes(ddata, data, 0, st.cap_bytes ? 0 : 1); st.offsets(doff); st.out(ddig, digest_out, 32); st.out(dsc, scalar_out, 32);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t a, uint64_t m) {
+        return sha3_256_launch(ctx, ddata, doff, doff + 8, off[a], nullptr, m, digest_out ? ddig : nullptr, scalar_out ? dsc : nullptr);
+    });
 }
 
 int32_t bzk_sha512_batch_dev(bzk_ctx* ctx, const void* data_dev, const void* off_dev, uint64_t n, void* digest_out_dev) {
@@ -790,21 +689,11 @@ int32_t bzk_sha512_batch(bzk_ctx* ctx, const uint8_t* data, const uint64_t* off,
         return BZK_OK;
     }
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> chunk_at = message_rounds(off, n, (uint64_t)1 << 20, (uint64_t)64 << 20);
-    const auto [cap, cap_bytes] = round_caps(chunk_at, off);
-    WsLayout ws("bzk_sha512_batch");
+    Stage<StreamOps> st({ctx}, "bzk_sha512_batch", n, MSG_ROUND, MSG_ROUND_BYTES, lengths(off), off);
     uint8_t *ddata, *doff, *ddig;
-    ws.take(ddata, cap_bytes ? cap_bytes : 1); ws.take(doff, (cap + 1) * 8); ws.take(ddig, cap * 64);
-    BZK_TRY(ws.commit(ctx));
-    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {
-        const uint64_t a = chunk_at[c], m = chunk_at[c + 1] - a, bytes = off[a + m] - off[a];
-        if (bytes) BZK_HIP(ctx, hipMemcpyAsync(ddata, data + off[a], bytes, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(doff, off + a, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_TRY(sha512_launch(ctx, ddata, doff, doff + 8, off[a], m, ddig));
-        BZK_HIP(ctx, hipMemcpyAsync(digest_out + a * 64, ddig, m * 64, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BZK_OK;
+    st.bytes(ddata, data, 0, st.cap_bytes ? 0 : 1); st.offsets(doff); st.out(ddig, digest_out, 64);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t a, uint64_t m) { return sha512_launch(ctx, ddata, doff, doff + 8, off[a], m, ddig); });
 }
 
 int32_t bzk_ed25519_verify_batch_dev(bzk_ctx* ctx, const void* pk_dev, const void* msg_dev, const void* off_dev, const void* sig_dev, uint64_t n,
@@ -827,23 +716,11 @@ int32_t bzk_ed25519_verify_batch(bzk_ctx* ctx, const uint8_t* pk, const uint8_t*
         return BZK_OK;
     }
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> chunk_at = message_rounds(off, n, (uint64_t)1 << 20, (uint64_t)64 << 20);
-    const auto [cap, cap_bytes] = round_caps(chunk_at, off);
-    WsLayout ws("bzk_ed25519_verify_batch");
+    Stage<StreamOps> st({ctx}, "bzk_ed25519_verify_batch", n, MSG_ROUND, MSG_ROUND_BYTES, lengths(off), off);
     uint8_t *ddata, *doff, *dpk, *dsig, *dok;
-    ws.take(ddata, cap_bytes ? cap_bytes : 1); ws.take(doff, (cap + 1) * 8); ws.take(dpk, cap * 32); ws.take(dsig, cap * 64); ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    for (size_t c = 0; c + 1 < chunk_at.size(); ++c) {
-        const uint64_t a = chunk_at[c], m = chunk_at[c + 1] - a, bytes = off[a + m] - off[a];
-        if (bytes) BZK_HIP(ctx, hipMemcpyAsync(ddata, msg + off[a], bytes, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(doff, off + a, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dpk, pk + a * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dsig, sig + a * 64, m * 64, hipMemcpyHostToDevice, ctx->stream));
-        BZK_TRY(ed25519_verify_launch(ctx, dpk, nullptr, dsig, nullptr, ddata, doff, doff + 8, off[a], -1, m, dok));
-        BZK_HIP(ctx, hipMemcpyAsync(ok + a, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BZK_OK;
+    st.bytes(ddata, msg, 0, st.cap_bytes ? 0 : 1); st.offsets(doff); st.in(dpk, pk, 32); st.in(dsig, sig, 64); st.out(dok, ok, 1);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t a, uint64_t m) { return ed25519_verify_launch(ctx, dpk, nullptr, dsig, nullptr, ddata, doff, doff + 8, off[a], -1, m, dok); });
 }
 
 int32_t bzk_sha3_merkle_roots(bzk_ctx* ctx, const uint8_t* leaves, const uint64_t* count, uint64_t m, uint8_t* roots_out, uint8_t* nodes_out) {

@@ -10,7 +10,7 @@
 #include "bzk_decompress.cuh"
 #include "bzk_eddsa_sign.cuh"
 #include "bzk_internal.h"
-#include "bzk_rounds.h"
+#include "bzk_stage.h"
 #include "host_bincode.h"
 #include "host_mpn_world.h"  // g_work_error
 #include "host_threads.h"
@@ -91,21 +91,6 @@ constexpr uint64_t SIGN_LAUNCH_MAX = (uint64_t)1 << 24;  // rows per launch, as 
 constexpr uint64_t SIGN_ROUND = (uint64_t)1 << 16;       // rows a host-pointer call stages per round: 257 bytes each, and the kernel's rate has levelled off
 constexpr uint64_t KEYS_ROUND_BYTES = (uint64_t)64 << 20;
 
-// Overwrites a workspace region that held staged secrets when the call leaves early (a failed copy or launch); the ordinary way out enqueues the
-// same overwrite itself, so that its failure is reported, and disarms this
-struct WipeOnError {
-    bzk_ctx* ctx;
-    void *a, *b;
-    size_t na, nb;
-    bool armed = true;
-    ~WipeOnError() {
-        if (!armed) return;
-        if (a) (void)hipMemsetAsync(a, 0, na, ctx->stream);
-        if (b) (void)hipMemsetAsync(b, 0, nb, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-};
-
 static int32_t sign_consts_dev(bzk_ctx* ctx, SignConsts& c) {
     const void *p3, *p6;
     BZK_TRY(poseidon_consts_dev_shared(ctx, 3, &p3, &c.rf3, &c.rp3));
@@ -136,25 +121,22 @@ static int32_t jubjub_sign_launch(bzk_ctx* ctx, const void* keys_dev, const void
     if (n == 0) return BZK_OK;
     SignConsts c;
     BZK_TRY(sign_consts_dev(ctx, c));
-    for (uint64_t off = 0; off < n; off += SIGN_LAUNCH_MAX) {
-        const uint64_t m = n - off < SIGN_LAUNCH_MAX ? n - off : SIGN_LAUNCH_MAX;
-        BZK_LAUNCH(ctx, "jubjub_sign", jubjub_sign_kernel, dim3((unsigned)((m + SIGN_BLOCK - 1) / SIGN_BLOCK)), dim3(SIGN_BLOCK), 0,
-                   (const Fr*)keys_dev + 4 * off, (const Fr*)msg_dev + off, gate_dev ? (const uint8_t*)gate_dev + off : nullptr, m, c,
-                   (Fr*)sig_dev + 3 * off, (uint8_t*)ok_dev + off);
-    }
-    return BZK_OK;
+    return launch_rows(n, SIGN_LAUNCH_MAX, SIGN_BLOCK, [&](uint64_t off, uint64_t m, unsigned grid) {
+        BZK_LAUNCH(ctx, "jubjub_sign", jubjub_sign_kernel, dim3(grid), dim3(SIGN_BLOCK), 0, (const Fr*)keys_dev + 4 * off, (const Fr*)msg_dev + off,
+                   gate_dev ? (const uint8_t*)gate_dev + off : nullptr, m, c, (Fr*)sig_dev + 3 * off, (uint8_t*)ok_dev + off);
+        return BZK_OK;
+    });
 }
 static int32_t jubjub_keys_launch(bzk_ctx* ctx, const void* data_dev, const void* begin_dev, const void* end_dev, uint64_t base, uint64_t n,
                                   void* keys_dev) {
     if (n == 0) return BZK_OK;
     const Fr29* tab;
     BZK_TRY(eddsa_table_dev(ctx, &tab));
-    for (uint64_t off = 0; off < n; off += SIGN_LAUNCH_MAX) {
-        const uint64_t m = n - off < SIGN_LAUNCH_MAX ? n - off : SIGN_LAUNCH_MAX;
-        BZK_LAUNCH(ctx, "jubjub_keys", jubjub_keys_kernel, dim3((unsigned)((m + SIGN_BLOCK - 1) / SIGN_BLOCK)), dim3(SIGN_BLOCK), 0,
-                   (const uint8_t*)data_dev, (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off, base, m, tab, (Fr*)keys_dev + 4 * off);
-    }
-    return BZK_OK;
+    return launch_rows(n, SIGN_LAUNCH_MAX, SIGN_BLOCK, [&](uint64_t off, uint64_t m, unsigned grid) {
+        BZK_LAUNCH(ctx, "jubjub_keys", jubjub_keys_kernel, dim3(grid), dim3(SIGN_BLOCK), 0, (const uint8_t*)data_dev,
+                   (const uint64_t*)begin_dev + off, (const uint64_t*)end_dev + off, base, m, tab, (Fr*)keys_dev + 4 * off);
+        return BZK_OK;
+    });
 }
 
 // one row on the host: bytes in, bytes out (the caller's buffers need no alignment)
@@ -173,24 +155,14 @@ static uint8_t sign_row_host(const SignConsts& c, const uint8_t* key, const uint
 static int32_t mpn_txs_sign_run(bzk_ctx* ctx, const TxSoA& t, const uint8_t* keys, uint64_t n, uint8_t* sig, uint8_t* ok, uint8_t* hash_out) {
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> round_at = cut_rounds(n, MPN_TX_CHUNK, ~(uint64_t)0, [](uint64_t) { return (uint64_t)0; });
-    const uint64_t cap = n < MPN_TX_CHUNK ? n : MPN_TX_CHUNK;
-    WsLayout ws("mpn_txs_sign_run");
+    Stage<StreamOps> st({ctx}, "mpn_txs_sign_run", n, MPN_TX_CHUNK);
     uint8_t *dkeys, *dsx, *ddx, *dsodd, *ddodd, *dxy, *dkok, *dtok, *dnums, *dtup, *dmsg, *dsig, *dhfit, *dfit, *dok;
-    ws.take(dkeys, cap * 128); ws.take(dsx, cap * 32); ws.take(ddx, cap * 32); ws.take(dsodd, cap); ws.take(ddodd, cap);
-    ws.take(dxy, cap * 64); ws.take(dkok, cap); ws.take(dtok, cap * 64); ws.take(dnums, cap * 24); ws.take(dtup, cap * 224);
-    ws.take(dmsg, cap * 32); ws.take(dsig, cap * 96); ws.take(dhfit, cap); ws.take(dfit, cap); ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    WipeOnError wipe{ctx, dkeys, nullptr, cap * 128, 0};
-    for (size_t c = 0; c + 1 < round_at.size(); ++c) {  // one stream: a round's uploads follow the previous round's kernels
-        const uint64_t off = round_at[c], m = round_at[c + 1] - off;
-        BZK_HIP(ctx, hipMemcpyAsync(dkeys, keys + off * 128, m * 128, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dsx, t.src_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(ddx, t.dst_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dsodd, t.src_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(ddodd, t.dst_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dtok, t.tok + off * 64, m * 64, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dnums, t.nums + off * 3, m * 24, hipMemcpyHostToDevice, ctx->stream));
+    st.in(dkeys, keys, 128); st.in(dsx, t.src_x, 32); st.in(ddx, t.dst_x, 32); st.in(dsodd, t.src_odd, 1); st.in(ddodd, t.dst_odd, 1);
+    st.scratch(dxy, 64); st.scratch(dkok, 1); st.in(dtok, t.tok, 64); st.in(dnums, t.nums, 24); st.scratch(dtup, 224);
+    st.out(dmsg, hash_out, 32); st.out(dsig, sig, 96); st.scratch(dhfit, 1); st.scratch(dfit, 1); st.out(dok, ok, 1);
+    st.wipe(dkeys, st.cap * 128);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t, uint64_t m) {
         BZK_TRY(jubjub_decompress_launch(ctx, ddx, ddodd, m, dxy, dkok));
         const dim3 grid((unsigned)((m + 255) / 256));
         BZK_LAUNCH(ctx, "mpn_tx_sign_inputs", mpn_tx_sign_inputs_kernel, grid, dim3(256), 0, (const uint64_t*)dnums, (const Fr*)dtok, (const Fr*)dxy,
@@ -198,14 +170,8 @@ static int32_t mpn_txs_sign_run(bzk_ctx* ctx, const TxSoA& t, const uint8_t* key
         BZK_TRY(poseidon_launch(ctx, dtup, 7, m, dmsg));
         BZK_TRY(jubjub_sign_launch(ctx, dkeys, dmsg, dfit, m, dsig, dok));
         BZK_LAUNCH(ctx, "mpn_tx_sign_hash", mpn_tx_sign_hash_kernel, grid, dim3(256), 0, (const uint8_t*)dhfit, m, (Fr*)dmsg);
-        BZK_HIP(ctx, hipMemcpyAsync(sig + off * 96, dsig, m * 96, hipMemcpyDeviceToHost, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-        if (hash_out) BZK_HIP(ctx, hipMemcpyAsync(hash_out + off * 32, dmsg, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipMemsetAsync(dkeys, 0, cap * 128, ctx->stream));
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    wipe.armed = false;
-    return BZK_OK;
+        return BZK_OK;
+    });
 }
 // the same per-lane functions on host threads
 static int32_t mpn_txs_sign_host(int threads, const TxParsed& P, const uint8_t* keys, uint64_t n, uint8_t* sig, uint8_t* ok, uint8_t* hash_out) {
@@ -234,13 +200,6 @@ static int32_t mpn_txs_sign_host(int threads, const TxParsed& P, const uint8_t* 
     return BZK_OK;
 }
 
-static bool seed_offsets_ok(const uint64_t* off, uint64_t n) {
-    if (off[0] != 0) return false;
-    for (uint64_t i = 0; i < n; ++i)
-        if (off[i + 1] < off[i]) return false;
-    return true;
-}
-
 }  // namespace bzk
 
 using namespace bzk;
@@ -264,25 +223,12 @@ int32_t bzk_jubjub_sign_batch(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* 
         return BZK_OK;
     }
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> round_at = cut_rounds(n, SIGN_ROUND, ~(uint64_t)0, [](uint64_t) { return (uint64_t)0; });
-    const uint64_t cap = n < SIGN_ROUND ? n : SIGN_ROUND;
-    WsLayout ws("bzk_jubjub_sign_batch");
+    Stage<StreamOps> st({ctx}, "bzk_jubjub_sign_batch", n, SIGN_ROUND);
     uint8_t *dkeys, *dmsg, *dsig, *dok;
-    ws.take(dkeys, cap * 128); ws.take(dmsg, cap * 32); ws.take(dsig, cap * 96); ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    WipeOnError wipe{ctx, dkeys, nullptr, cap * 128, 0};
-    for (size_t c = 0; c + 1 < round_at.size(); ++c) {  // one stream: a round's uploads follow the previous round's kernel
-        const uint64_t off = round_at[c], m = round_at[c + 1] - off;
-        BZK_HIP(ctx, hipMemcpyAsync(dkeys, keys + off * 128, m * 128, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dmsg, msg + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_TRY(jubjub_sign_launch(ctx, dkeys, dmsg, nullptr, m, dsig, dok));
-        BZK_HIP(ctx, hipMemcpyAsync(sig_out + off * 96, dsig, m * 96, hipMemcpyDeviceToHost, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipMemsetAsync(dkeys, 0, cap * 128, ctx->stream));  // the staged keys do not outlive the call
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    wipe.armed = false;
-    return BZK_OK;
+    st.in(dkeys, keys, 128); st.in(dmsg, msg, 32); st.out(dsig, sig_out, 96); st.out(dok, ok, 1);
+    st.wipe(dkeys, st.cap * 128);  // the staged keys do not outlive the call
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t, uint64_t m) { return jubjub_sign_launch(ctx, dkeys, dmsg, nullptr, m, dsig, dok); });
 }
 
 int32_t bzk_jubjub_keys_batch_dev(bzk_ctx* ctx, const void* seeds_dev, const void* off_dev, uint64_t n, void* keys_out_dev) {
@@ -295,7 +241,7 @@ int32_t bzk_jubjub_keys_batch_dev(bzk_ctx* ctx, const void* seeds_dev, const voi
 int32_t bzk_jubjub_keys_batch(bzk_ctx* ctx, const uint8_t* seeds, const uint64_t* off, uint64_t n, uint8_t* keys_out) {
     if (n && (!off || !keys_out)) return BZK_E_ARG;
     if (n == 0) return BZK_OK;
-    if (!seed_offsets_ok(off, n) || (off[n] && !seeds)) return BZK_E_ARG;
+    if (!offsets_ok(off, n) || (off[n] && !seeds)) return BZK_E_ARG;
     const uint8_t none = 0;
     if (!seeds) seeds = &none;  // n empty seeds
     if (!ctx) {  // the same per-lane code on host threads
@@ -309,25 +255,12 @@ int32_t bzk_jubjub_keys_batch(bzk_ctx* ctx, const uint8_t* seeds, const uint64_t
         return BZK_OK;
     }
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> round_at = cut_rounds(n, SIGN_ROUND, KEYS_ROUND_BYTES, [off](uint64_t i) { return off[i + 1] - off[i]; });
-    const auto [cap, cap_bytes] = round_caps(round_at, off);
-    WsLayout ws("bzk_jubjub_keys_batch");
+    Stage<StreamOps> st({ctx}, "bzk_jubjub_keys_batch", n, SIGN_ROUND, KEYS_ROUND_BYTES, lengths(off), off);
     uint8_t *ddata, *doff, *dkeys;
-    ws.take(ddata, cap_bytes + 8); ws.take(doff, (cap + 1) * 8); ws.take(dkeys, cap * 128);
-    BZK_TRY(ws.commit(ctx));
-    WipeOnError wipe{ctx, ddata, dkeys, cap_bytes + 8, cap * 128};
-    for (size_t c = 0; c + 1 < round_at.size(); ++c) {
-        const uint64_t a = round_at[c], m = round_at[c + 1] - a, bytes = off[a + m] - off[a];
-        if (bytes) BZK_HIP(ctx, hipMemcpyAsync(ddata, seeds + off[a], bytes, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(doff, off + a, (m + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_TRY(jubjub_keys_launch(ctx, ddata, doff, doff + 8, off[a], m, dkeys));
-        BZK_HIP(ctx, hipMemcpyAsync(keys_out + a * 128, dkeys, m * 128, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipMemsetAsync(ddata, 0, cap_bytes + 8, ctx->stream));  // neither the staged seeds nor the keys outlive the call
-    BZK_HIP(ctx, hipMemsetAsync(dkeys, 0, cap * 128, ctx->stream));
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    wipe.armed = false;
-    return BZK_OK;
+    st.bytes(ddata, seeds, 0, 8); st.offsets(doff); st.out(dkeys, keys_out, 128);
+    st.wipe(ddata, st.cap_bytes + 8); st.wipe(dkeys, st.cap * 128);  // neither the staged seeds nor the keys outlive the call
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t a, uint64_t m) { return jubjub_keys_launch(ctx, ddata, doff, doff + 8, off[a], m, dkeys); });
 }
 
 int32_t bzk_mpn_txs_sign(bzk_ctx* ctx, const uint8_t* keys, const uint8_t* txs, uint64_t len, uint64_t n, uint8_t* txs_out, uint8_t* ok,

@@ -4,6 +4,7 @@
 // rounds and the entry points.  No lane waits for another (no LDS, no barrier).  A flagged or invalid record ends its lane before the ladders (the
 // only divergence: those lanes leave, the others run on); every lane that enters a ladder runs the same steps whatever its point.
 #include "bzk_internal.h"
+#include "bzk_stage.h"
 #include "bzk_subgroup.cuh"
 #include "host_fp64.h"
 #include "host_threads.h"
@@ -80,15 +81,14 @@ void host_run(bool g2, const uint8_t* pts, const uint8_t* inf, uint64_t n, uint8
 // rounds of at most SG_ROUND points whose records, flags and verdict bytes are device pointers
 int32_t launch_rounds(bzk_ctx* ctx, bool g2, const uint8_t* pts, const uint8_t* inf, uint64_t n, uint8_t* ok) {
     const size_t sz = g2 ? 192 : 96;
-    for (uint64_t a = 0; a < n; a += SG_ROUND) {
-        const uint32_t m = (uint32_t)std::min<uint64_t>(n - a, SG_ROUND);
-        const dim3 grid((m + SG_BLOCK - 1) / SG_BLOCK), block(SG_BLOCK);
+    return launch_rows(n, SG_ROUND, SG_BLOCK, [&](uint64_t a, uint64_t rows, unsigned grid) {
+        const uint32_t m = (uint32_t)rows;
         const uint32_t* rp = (const uint32_t*)(pts + sz * a);
         const uint8_t* ri = inf ? inf + a : nullptr;
-        if (g2) BZK_LAUNCH(ctx, "sg_g2", sg_g2_kernel, grid, block, 0, rp, ri, m, ok + a);
-        else BZK_LAUNCH(ctx, "sg_g1", sg_g1_kernel, grid, block, 0, rp, ri, m, ok + a);
-    }
-    return BZK_OK;
+        if (g2) BZK_LAUNCH(ctx, "sg_g2", sg_g2_kernel, dim3(grid), dim3(SG_BLOCK), 0, rp, ri, m, ok + a);
+        else BZK_LAUNCH(ctx, "sg_g1", sg_g1_kernel, dim3(grid), dim3(SG_BLOCK), 0, rp, ri, m, ok + a);
+        return BZK_OK;
+    });
 }
 
 // n records in rounds, the verdicts into host memory.  Host records (on_device false) are staged one round at a time; records that already are in
@@ -97,29 +97,18 @@ int32_t launch_rounds(bzk_ctx* ctx, bool g2, const uint8_t* pts, const uint8_t* 
 int32_t run_rounds(bzk_ctx* ctx, const char* who, bool g2, const uint8_t* pts, bool on_device, const uint8_t* inf, uint64_t n, uint8_t* ok) {
     (void)hipSetDevice(ctx->device);
     const size_t sz = g2 ? 192 : 96;
-    const uint64_t cap = std::min<uint64_t>(n, SG_ROUND);
-    WsLayout ws(who);
+    Stage<StreamOps> st({ctx}, who, n, SG_ROUND);
     uint8_t *dp = nullptr, *di = nullptr, *dok = nullptr;
     if (!on_device) {
-        ws.take(dp, sz * cap);
-        if (inf) ws.take(di, cap);
+        st.in(dp, pts, sz);
+        if (inf) st.in(di, inf, 1);
     }
-    ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    for (uint64_t a = 0; a < n; a += SG_ROUND) {
-        const uint64_t m = std::min<uint64_t>(n - a, SG_ROUND);
-        const uint8_t *rp = pts + sz * a, *ri = inf ? inf + a : nullptr;
-        if (!on_device) {
-            BZK_HIP(ctx, hipMemcpyAsync(dp, rp, sz * m, hipMemcpyHostToDevice, ctx->stream));
-            if (inf) BZK_HIP(ctx, hipMemcpyAsync(di, ri, m, hipMemcpyHostToDevice, ctx->stream));
-            rp = dp;
-            ri = inf ? di : nullptr;
-        }
-        BZK_TRY(launch_rounds(ctx, g2, rp, ri, m, dok));
-        BZK_HIP(ctx, hipMemcpyAsync(ok + a, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return BZK_OK;
+    st.out(dok, ok, 1);
+    BZK_TRY(st.ws.commit(ctx));
+    return st.run([&](uint64_t a, uint64_t m) {
+        if (on_device) return launch_rounds(ctx, g2, pts + sz * a, inf ? inf + a : nullptr, m, dok);
+        return launch_rounds(ctx, g2, dp, di, m, dok);
+    });
 }
 
 int32_t entry_host_ptrs(bzk_ctx* ctx, const char* who, bool g2, const uint8_t* pts, const uint8_t* inf, uint64_t n, uint8_t* ok) {

@@ -9,7 +9,7 @@
 
 #include "bzk_withdraw_sign.cuh"
 #include "bzk_internal.h"
-#include "bzk_rounds.h"
+#include "bzk_stage.h"
 #include "host_bincode.h"
 #include "host_mpn_world.h"  // g_work_error
 #include "host_threads.h"
@@ -39,20 +39,6 @@ __global__ void __launch_bounds__(WD_SIGN_BLOCK) mpn_withdraw_sign_kernel(const 
 }
 
 namespace {
-
-// Overwrites the workspace region that held staged keys when the call leaves early (sign.hip's WipeOnError); the ordinary way out enqueues the
-// same overwrite itself, so that its failure is reported, and disarms this
-struct WipeOnError {
-    bzk_ctx* ctx;
-    void* a;
-    size_t na;
-    bool armed = true;
-    ~WipeOnError() {
-        if (!armed) return;
-        (void)hipMemsetAsync(a, 0, na, ctx->stream);
-        (void)hipStreamSynchronize(ctx->stream);
-    }
-};
 
 int32_t consts_dev(bzk_ctx* ctx, eddsa::WithdrawSignConsts& c) {
     const void *p3, *p6, *p7;
@@ -84,45 +70,26 @@ int32_t mpn_withdraws_sign_run(bzk_ctx* ctx, const WdSoA& t, const uint8_t* keys
                                uint8_t* fp_out) {
     if (n == 0) return BZK_OK;
     (void)hipSetDevice(ctx->device);
-    const std::vector<uint64_t> round_at = cut_rounds(n, MPN_TX_CHUNK, MPN_WD_CHUNK_BYTES, [&](uint64_t i) { return (uint64_t)t.pay_len[i]; });
-    const auto [cap, cap_bytes] = round_caps(round_at, t.rec_off);
-    std::vector<uint64_t> begin(n), end(n);  // payment ranges relative to their round's first byte
-    for (size_t c = 0; c + 1 < round_at.size(); ++c)
-        for (uint64_t i = round_at[c]; i < round_at[c + 1]; ++i) {
-            begin[i] = t.pay_off[i] - t.rec_off[round_at[c]];
-            end[i] = begin[i] + t.pay_len[i];
-        }
-    WsLayout ws("mpn_withdraws_sign_run");
+    Stage<StreamOps> st({ctx}, "mpn_withdraws_sign_run", n, MPN_TX_CHUNK, MPN_WD_CHUNK_BYTES, [&](uint64_t i) { return (uint64_t)t.pay_len[i]; }, t.rec_off);
+    std::vector<uint64_t> begin = round_bases(st.round_at, t.rec_off), end(n);  // payment ranges relative to their round's first byte
+    for (uint64_t i = 0; i < n; ++i) {
+        begin[i] = t.pay_off[i] - begin[i];
+        end[i] = begin[i] + t.pay_len[i];
+    }
     uint8_t *dbytes, *dbeg, *dend, *dcd, *dnonce, *dkeys, *dkx, *dodd, *dfp, *dsig, *dcall, *dok;
-    ws.take(dbytes, cap_bytes); ws.take(dbeg, cap * 8); ws.take(dend, cap * 8); ws.take(dcd, cap * 4); ws.take(dnonce, cap * 4);
-    ws.take(dkeys, cap * 128); ws.take(dkx, cap * 32); ws.take(dodd, cap); ws.take(dfp, cap * 32); ws.take(dsig, cap * 96);
-    ws.take(dcall, cap * 32); ws.take(dok, cap);
-    BZK_TRY(ws.commit(ctx));
-    WipeOnError wipe{ctx, dkeys, cap * 128};
+    st.bytes(dbytes, t.txs, 0, 0); st.in(dbeg, begin.data(), 8); st.in(dend, end.data(), 8); st.in(dcd, t.cd_off, 4); st.in(dnonce, t.nonce, 4);
+    st.in(dkeys, keys, 128); st.in(dkx, t.key_x, 32); st.in(dodd, t.key_odd, 1); st.out(dfp, fp_out, 32); st.out(dsig, sig, 96);
+    st.out(dcall, calldata, 32); st.out(dok, ok, 1);
+    st.wipe(dkeys, st.cap * 128);  // the staged keys do not outlive the call
+    BZK_TRY(st.ws.commit(ctx));
     eddsa::WithdrawSignConsts k;
     BZK_TRY(consts_dev(ctx, k));
-    for (size_t c = 0; c + 1 < round_at.size(); ++c) {  // one stream: a round's uploads follow the previous round's kernels
-        const uint64_t off = round_at[c], m = round_at[c + 1] - off;
-        BZK_HIP(ctx, hipMemcpyAsync(dbytes, t.txs + t.rec_off[off], t.rec_off[off + m] - t.rec_off[off], hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dbeg, begin.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dend, end.data() + off, m * 8, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dcd, t.cd_off + off, m * 4, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dnonce, t.nonce + off, m * 4, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dkeys, keys + off * 128, m * 128, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dkx, t.key_x + off * 32, m * 32, hipMemcpyHostToDevice, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(dodd, t.key_odd + off, m, hipMemcpyHostToDevice, ctx->stream));
+    return st.run([&](uint64_t, uint64_t m) {
         BZK_TRY(sha3_256_launch(ctx, dbytes, dbeg, dend, 0, dcd, m, nullptr, dfp));
         BZK_LAUNCH(ctx, "mpn_withdraw_sign", mpn_withdraw_sign_kernel, dim3((unsigned)((m + WD_SIGN_BLOCK - 1) / WD_SIGN_BLOCK)), dim3(WD_SIGN_BLOCK), 0,
                    (const Fr*)dkeys, (const Fr*)dkx, (const uint8_t*)dodd, (const uint32_t*)dnonce, (const Fr*)dfp, m, k, (Fr*)dsig, (Fr*)dcall, dok);
-        BZK_HIP(ctx, hipMemcpyAsync(sig + off * 96, dsig, m * 96, hipMemcpyDeviceToHost, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(calldata + off * 32, dcall, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-        BZK_HIP(ctx, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, ctx->stream));
-        if (fp_out) BZK_HIP(ctx, hipMemcpyAsync(fp_out + off * 32, dfp, m * 32, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    BZK_HIP(ctx, hipMemsetAsync(dkeys, 0, cap * 128, ctx->stream));  // the staged keys do not outlive the call
-    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    wipe.armed = false;
-    return BZK_OK;
+        return BZK_OK;
+    });
 }
 // the same per-lane function on host threads
 int32_t mpn_withdraws_sign_host(int threads, const WdSoA& t, const uint8_t* keys, uint64_t n, uint8_t* sig, uint8_t* calldata, uint8_t* ok,

@@ -21,6 +21,7 @@
 
 #include "bzk_curve.cuh"
 #include "bzk_internal.h"
+#include "bzk_rekey.h"
 #include "host_fp64.h"
 #include "host_r1cs.h"  // DeferData / witfill_run_dev: witness values the device fills in (bzk_groth16_prove_r1cs)
 namespace bzk { void r1cs_assignment(const bzk_r1cs* r, bzk_assignment* a, const DeferData** dd, uint64_t* n_in); }  // mpn.hip
@@ -988,3 +989,31 @@ void bzk_params_buffers_internal(bzk_params* p, void** h, void** l, void** a, vo
     *h = p->crs->h; *l = p->crs->l; *a = p->crs->a; *b_g1 = p->crs->b_g1; *b_g2 = p->crs->b_g2;
 }
 void bzk_params_set_vk_internal(bzk_params* p, const uint8_t vk[870]) { memcpy(p->crs->vk, vk, 870); }
+
+// the hook of rekey.hip (bzk_rekey.h): an unfilled handle of src's shape - the densities are rebuilt from src's dense-variable indices - with src's vk
+namespace bzk {
+int32_t params_clone_shape(bzk_ctx* ctx, const bzk_params* src, bzk_params** out, void* dev[5], const void* src_dev[5], uint64_t n[5]) {
+    const CrsShared* c = src->crs;
+    if (c->device != ctx->device) return BZK_E_ARG;
+    (void)hipSetDevice(ctx->device);
+    const uint64_t nv = (uint64_t)c->n_in + c->n_aux;
+    std::vector<uint32_t> ia(c->n_a), ib(c->n_b);
+    if (c->n_a) BZK_HIP(ctx, hipMemcpyAsync(ia.data(), c->a_idx, ia.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (c->n_b) BZK_HIP(ctx, hipMemcpyAsync(ib.data(), c->b_idx, ib.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    BZK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<uint8_t> a_d(nv, 0), b_d(nv, 0);
+    for (uint32_t v : ia) if (v < nv) a_d[v] = 1;
+    for (uint32_t v : ib) if (v < nv) b_d[v] = 1;
+    bzk_params_desc d;
+    memset(&d, 0, sizeof d);
+    d.n_in = c->n_in; d.n_aux = c->n_aux; d.log_m = c->log_m; d.n_a = c->n_a; d.n_b = c->n_b;
+    d.vk = c->vk; d.a_density = a_d.data(); d.b_density = b_d.data();
+    BZK_TRY(params_build(ctx, &d, false, out));
+    const CrsShared* q = (*out)->crs;
+    void* nd[5] = {q->h, q->l, q->a, q->b_g1, q->b_g2};
+    const void* sd[5] = {c->h, c->l, c->a, c->b_g1, c->b_g2};
+    const uint64_t cnt[5] = {((uint64_t)1 << c->log_m) - 1, c->n_aux, c->n_a, c->n_b, c->n_b};
+    for (int k = 0; k < 5; ++k) { dev[k] = nd[k]; src_dev[k] = sd[k]; n[k] = cnt[k]; }
+    return BZK_OK;
+}
+}  // namespace bzk

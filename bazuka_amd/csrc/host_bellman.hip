@@ -23,6 +23,7 @@
 
 #include "bzk_curve.cuh"
 #include "bzk_internal.h"
+#include "bzk_rekey.h"
 
 using namespace bzk;
 
@@ -400,6 +401,78 @@ int32_t bzk_bellman_params_check(bzk_ctx* ctx, const uint8_t* bytes, uint64_t le
     const int32_t st = queries_in_subgroup(ctx, "bzk_bellman_params_check", q, false, D.L, report, &pass);
     if (st != BZK_OK) return st;
     return pass ? 1 : 0;
+}
+
+// The phase-2 step on a blob: h and l times d^-1 (bzk_g1_scale_batch's rounds: on the device with a context, on host threads without), the two deltas
+// times d on the host, everything else as it was
+int32_t bzk_bellman_params_rekey(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len, const uint8_t d[32], uint8_t* out, uint64_t cap,
+                                 uint64_t* size_out) {
+    Layout L;
+    if (!bytes || !d || !layout_of(bytes, len, L)) return BZK_E_ARG;
+    uint8_t dinv[32];
+    BZK_TRY(rekey_scalars(d, dinv));
+    if (size_out) *size_out = L.total;
+    if (!out) { wipe_host(dinv, sizeof dinv); return BZK_OK; }
+    if (cap < L.total) { wipe_host(dinv, sizeof dinv); return BZK_E_ARG; }
+    Decoded D;
+    D.L = L;
+    D.vk.resize(870); D.ic.resize(97 * L.n_ic); D.h.resize(96 * L.n_h); D.l.resize(96 * L.n_l); D.a.resize(96 * L.n_a);
+    D.b1.resize(96 * L.n_b1); D.b2.resize(192 * L.n_b2);
+    int32_t st = L.n_b1 != L.n_b2 ? BZK_E_ARG
+                                  : bzk_bellman_params_decode(bytes, len, D.vk.data(), D.ic.data(), D.h.data(), D.l.data(), D.a.data(), D.b1.data(), D.b2.data(), 0);
+    if (st == BZK_OK) st = g1_scale_run(ctx, "bzk_bellman_params_rekey", D.h.data(), false, L.n_h, dinv, D.h.data(), nullptr);
+    if (st == BZK_OK) st = g1_scale_run(ctx, "bzk_bellman_params_rekey", D.l.data(), false, L.n_l, dinv, D.l.data(), nullptr);
+    wipe_host(dinv, sizeof dinv);
+    if (st != BZK_OK) return st;
+    rekey_vk_head(D.vk.data(), d);
+    return bzk_bellman_params_encode(D.vk.data(), D.ic.data(), L.n_ic, D.h.data(), L.n_h, D.l.data(), L.n_l, D.a.data(), L.n_a, D.b1.data(), D.b2.data(),
+                                     L.n_b1, out, cap, nullptr);
+}
+
+// Is `after` a re-key of `before`?  The order of the tests is the order of bzk.h's description; report names the first that fails
+int32_t bzk_bellman_params_rekey_check(bzk_ctx* ctx, const uint8_t* before, uint64_t before_len, const uint8_t* after, uint64_t after_len,
+                                       const uint8_t seed[32], uint64_t report[4]) {
+    if (!before || !after || !seed || !report) return BZK_E_ARG;
+    report[0] = report[1] = report[2] = report[3] = 0;
+    Decoded B, A;
+    uint64_t where[4];  // a blob that does not decode is array 7 here, whichever record it was
+    if (!decode_located(before, before_len, B, where) || !decode_located(after, after_len, A, where)) return fail_at(report, 7, 0, 2), 0;
+    const Layout &LB = B.L, &LA = A.L;
+    if (LB.n_ic != LA.n_ic || LB.n_h != LA.n_h || LB.n_l != LA.n_l || LB.n_a != LA.n_a || LB.n_b1 != LA.n_b1 || LB.n_b2 != LA.n_b2)
+        return fail_at(report, 7, 0, 2), 0;
+    // what a re-key leaves alone: alpha_g1, beta_g1, beta_g2, gamma_g2 (head points 0 .. 3), ic, a, b_g1, b_g2
+    for (uint64_t k = 0; k < 4; ++k)
+        if (memcmp(B.vk.data() + HEAD[k].dst, A.vk.data() + HEAD[k].dst, HEAD[k].g2 ? 193 : 97)) return fail_at(report, 0, k, 0), 0;
+    struct Same { const std::vector<uint8_t>*b, *a; uint64_t sz, array; };
+    const Same same[4] = {{&B.ic, &A.ic, 97, 1}, {&B.a, &A.a, 96, 4}, {&B.b1, &A.b1, 96, 5}, {&B.b2, &A.b2, 192, 6}};
+    for (const Same& s : same)
+        for (uint64_t i = 0; i * s.sz < s.b->size(); ++i)
+            if (memcmp(s.b->data() + i * s.sz, s.a->data() + i * s.sz, s.sz)) return fail_at(report, s.array, i, 0), 0;
+    // after's delta_g1, delta_g2, h, l in the order-r subgroup
+    for (uint64_t k = 4; k < 6; ++k) {
+        const uint8_t* p = A.vk.data() + HEAD[k].dst;
+        if (p[HEAD[k].g2 ? 192 : 96]) return fail_at(report, 0, k, 2), 0;  // an identity delta is no key
+        const uint8_t v = sg_host_one(HEAD[k].g2, p);
+        if (v != 1) return fail_at(report, 0, k, v), 0;
+    }
+    const uint8_t* q[2] = {A.h.data(), A.l.data()};
+    const uint64_t cnt[2] = {LA.n_h, LA.n_l};
+    for (int k = 0; k < 2; ++k) {
+        uint64_t idx = 0;
+        uint8_t code = 1;
+        BZK_TRY(sg_first_bad(ctx, "bzk_bellman_params_rekey_check", false, q[k], false, cnt[k], &idx, &code));
+        if (idx < cnt[k]) return fail_at(report, 2 + k, idx, code), 0;
+    }
+    // delta the same multiple in both groups, before and after
+    if (!rekey_delta_consistent(B.vk.data()) || !rekey_delta_consistent(A.vk.data())) return fail_at(report, 0, 5, 0), 0;
+    // the ratio, over h and over l
+    const uint8_t* qb[2] = {B.h.data(), B.l.data()};
+    for (int k = 0; k < 2; ++k) {
+        bool holds = false;
+        BZK_TRY(rekey_ratio(ctx, (uint8_t)(2 + k), qb[k], q[k], cnt[k], seed, B.vk.data(), A.vk.data(), &holds));
+        if (!holds) return fail_at(report, 2 + k, 0, 0), 0;
+    }
+    return 1;
 }
 
 }  // extern "C"

@@ -1,12 +1,11 @@
 // Batched subgroup checks (bzk_g1_subgroup_check_batch[_dev], bzk_g2_subgroup_check_batch[_dev]): the third check of bls12_381's
 // `from_uncompressed` - canonical, on the curve, of order r - for n raw Montgomery points, one lane per point.  The arithmetic is
-// bzk_subgroup.cuh's g1_verdict / g2_verdict; this file holds the two kernels, the host field's policy for the ctx = NULL path, the
-// rounds and the entry points.  No lane waits for another (no LDS, no barrier).  A flagged or invalid record ends its lane before the ladders (the
+// bzk_subgroup.cuh's g1_verdict / g2_verdict; this file holds the two kernels, the rounds and the entry points (the host field's policy for the
+// ctx = NULL path: bzk_subgroup_host.h).  No lane waits for another (no LDS, no barrier).  A flagged or invalid record ends its lane before the ladders (the
 // only divergence: those lanes leave, the others run on); every lane that enters a ladder runs the same steps whatever its point.
 #include "bzk_internal.h"
 #include "bzk_stage.h"
-#include "bzk_subgroup.cuh"
-#include "host_fp64.h"
+#include "bzk_subgroup_host.h"
 #include "host_threads.h"
 
 namespace bzk {
@@ -38,32 +37,6 @@ __global__ void __launch_bounds__(SG_BLOCK) sg_g2_kernel(const uint32_t* __restr
     const uint8_t v = sg::g2_verdict<sg::SgFp28>(pts + (size_t)48 * SG_BLOCK * blockIdx.x);
     ok[(size_t)blockIdx.x * SG_BLOCK + sg::lane_now()] = v;
 }
-
-// the host's base field under the policy interface of bzk_subgroup.cuh (values canonical, so is_zero is a limb test)
-struct SgHFp {
-    typedef HFp T;
-    static T zero() { return HFpOps::zero(); }
-    static T one() { return HFpOps::one(); }
-    static bool is_zero(const T& a) { return HFpOps::is_zero(a); }
-    static T add(const T& a, const T& b) { return HFpOps::add(a, b); }
-    static T sub(const T& a, const T& b) { return HFpOps::sub(a, b); }
-    static T mul(const T& a, const T& b) { return HFpOps::mul(a, b); }
-    static T sqr(const T& a) { return HFpOps::mul(a, a); }
-    static T mul12(const T& a) {
-        const T a3 = HFpOps::add(HFpOps::dbl(a), a);
-        return HFpOps::dbl(HFpOps::dbl(a3));
-    }
-    static T cst(const fp28::Consts& c) {  // the 28-bit Montgomery-2^392 constant as canonical Montgomery-2^384 limbs
-        const Fp f = fp28::from28(fp28::consts_as_fp28(c));
-        T r;
-        memcpy(r.l, f.l, 48);
-        return r;
-    }
-    static bool load(const uint32_t* w, T& out) {
-        memcpy(out.l, w, 48);
-        return !hfp::geq_p(out.l, hfp::consts().p);
-    }
-};
 
 void host_run(bool g2, const uint8_t* pts, const uint8_t* inf, uint64_t n, uint8_t* ok) {
     const size_t sz = g2 ? 192 : 96;

@@ -144,6 +144,11 @@ SIGNATURES = {
     "bzk_g2_subgroup_check_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _vp]),
     "bzk_params_read": (_i32, [_vp, _vp, _i32, _vp, _u64, C.POINTER(_u64)]),
     "bzk_groth16_setup": (_i32, [_vp, _vp, _vp, _vp, _u32, _u32, _vp, C.POINTER(_vp), _vp, _u64]),
+    "bzk_g1_scale_batch": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "bzk_g1_scale_batch_dev": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "bzk_params_rekey": (_i32, [_vp, _vp, _vp, C.POINTER(_vp), _vp]),
+    "bzk_bellman_params_rekey": (_i32, [_vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "bzk_bellman_params_rekey_check": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, C.POINTER(_u64)]),
     "bzk_groth16_h_dev": (_i32, [_vp, _vp, _vp, _vp, _u32]),
     "bzk_mpn_create": (_i32, [_u32, _u32, C.POINTER(_vp)]),
     "bzk_mpn_destroy": (None, [_vp]),
@@ -1021,6 +1026,26 @@ class Bzk:
         self._ck(self.lib.bzk_groth16_setup(self.h, C.byref(descs[0]), C.byref(descs[1]), C.byref(descs[2]), n_in, n_aux,
                                             _ptr(toxic), C.byref(h), vk, len(vk)), "groth16_setup")
         return h, vk.raw
+
+    # ---- the phase-2 step of a ceremony: delta times d (include/bzk.h)
+    def g1_scale_batch(self, pts: bytes, k: bytes):
+        """(out, inf): k times each raw 96-byte G1 point, one lane per point; k one Montgomery Fr scalar"""
+        return g1_scale_batch(self, pts, k)
+
+    def g1_scale_batch_dev(self, pts, n: int, k: bytes, out, inf=None):
+        """device buffers: pts and out n x 96 (out may be pts), inf n flag bytes or None; synchronises"""
+        self._ck(self.lib.bzk_g1_scale_batch_dev(self.h, _ptr(pts), n, _ptr(k), _ptr(out), _ptr(inf) if inf is not None else None),
+                 "g1_scale_batch_dev")
+
+    def params_rekey(self, ph, d: bytes):
+        """(new params handle, its 870-byte vk head): the resident key `ph` with delta times d; `ph` is left as it was"""
+        return params_rekey(self, ph, d)
+
+    def bellman_params_rekey(self, blob: bytes, d: bytes) -> bytes:
+        return bellman_params_rekey(self, blob, d)
+
+    def bellman_params_rekey_check(self, before: bytes, after: bytes, seed: bytes):
+        return bellman_params_rekey_check(self, before, after, seed)
 
     def groth16_h_dev(self, a, b, c, log_m: int):
         self._ck(self.lib.bzk_groth16_h_dev(self.h, _ptr(a), _ptr(b), _ptr(c), log_m), "groth16_h_dev")
@@ -2021,6 +2046,53 @@ def _bellman_params_check(ctx_handle, blob: bytes):
     st = load_library().bzk_bellman_params_check(ctx_handle, _ptr(blob), len(blob), report)
     if st < 0:
         _st(st, "bellman_params_check")
+    return st, tuple(report)
+
+
+def _h(ctx):
+    return ctx.h if ctx is not None else None
+
+
+def g1_scale_batch(ctx, pts: bytes, k: bytes):
+    """(out, inf): out[i] = k * pts[i] for raw 96-byte G1 points of the order-r subgroup, k one 32-byte Montgomery Fr scalar; an identity result is 96
+    zero bytes with inf[i] = 1.  ctx: a Bzk (one GPU lane per point) or None (host threads)"""
+    n = len(pts) // 96
+    if len(pts) != 96 * n or len(k) != 32:
+        raise BzkError("g1_scale_batch: pts must hold 96 bytes per point and k 32 bytes")
+    out, inf = C.create_string_buffer(max(96 * n, 1)), C.create_string_buffer(max(n, 1))
+    _st(load_library().bzk_g1_scale_batch(_h(ctx), _ptr(pts) if n else None, n, _ptr(k), out, inf), "g1_scale_batch")
+    return out.raw[: 96 * n], inf.raw[:n]
+
+
+def params_rekey(ctx, ph, d: bytes):
+    """(new params handle, its 870-byte vk head): bzk_params_rekey - needs a context"""
+    if len(d) != 32:
+        raise BzkError("params_rekey: d must hold 32 bytes")
+    h, vk = C.c_void_p(), C.create_string_buffer(870)
+    _st(load_library().bzk_params_rekey(_h(ctx), ph, _ptr(d), C.byref(h), vk), "params_rekey")
+    return h, vk.raw
+
+
+def bellman_params_rekey(ctx, blob: bytes, d: bytes) -> bytes:
+    """the bellman `Parameters` blob with delta times d (h and l times 1 / d); ctx None: host threads - the same bytes either way"""
+    if len(d) != 32:
+        raise BzkError("bellman_params_rekey: d must hold 32 bytes")
+    lib, n = load_library(), _u64()
+    _st(lib.bzk_bellman_params_rekey(_h(ctx), _ptr(blob), len(blob), _ptr(d), None, 0, C.byref(n)), "bellman_params_rekey")
+    out = C.create_string_buffer(max(n.value, 1))
+    _st(lib.bzk_bellman_params_rekey(_h(ctx), _ptr(blob), len(blob), _ptr(d), out, n.value, None), "bellman_params_rekey")
+    return out.raw[: n.value]
+
+
+def bellman_params_rekey_check(ctx, before: bytes, after: bytes, seed: bytes):
+    """(verdict, report): is `after` a re-key of `before` by some d - 1 or 0 with report = (array, index, code, 0) of the first failure.  The verdict
+    is only as good as the secrecy of `seed` (32 bytes) from whoever made `after`"""
+    if len(seed) != 32:
+        raise BzkError("bellman_params_rekey_check: seed must hold 32 bytes")
+    report = (C.c_uint64 * 4)()
+    st = load_library().bzk_bellman_params_rekey_check(_h(ctx), _ptr(before), len(before), _ptr(after), len(after), _ptr(seed), report)
+    if st < 0:
+        _st(st, "bellman_params_rekey_check")
     return st, tuple(report)
 
 

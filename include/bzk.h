@@ -661,6 +661,44 @@ typedef struct {
 int32_t bzk_groth16_setup(bzk_ctx* ctx, const bzk_csr* A, const bzk_csr* B, const bzk_csr* C, uint32_t n_in, uint32_t n_aux,
                           const uint8_t toxic[160], bzk_params** out_params, uint8_t* vk_out, uint64_t vk_cap);
 
+/* n G1 points times ONE scalar, one GPU lane per point: out[i] = k * pts[i].  pts and out are raw 96-byte records (little-endian Montgomery
+ * x | y: what bzk_bellman_params_decode emits and bzk_g1_subgroup_check_batch takes), out in canonical affine; k is one Montgomery Fr scalar
+ * (as r and s of bzk_groth16_prove).  An identity result is 96 zero bytes with inf_out[i] = 1 (inf_out: n bytes, may be NULL; 0 for a finite
+ * result); a record of 96 zero bytes is read as the identity.  k = 0 is legal: n identities.  The contract covers points of the order-r
+ * subgroup - what a checked CRS holds: the scalar is split through the endomorphism X^2 (x, y) = (BETA x, -y), which is multiplication by
+ * X^2 only there.  For any other input (outside the subgroup, off the curve, limbs >= p) the output is unspecified; nothing faults, the
+ * formulas are the complete ones of the subgroup check and no step depends on the point.  The scalar is recoded once per call on the host
+ * and treated as a secret: its host and device copies are overwritten before the call returns.  BZK_E_ARG, nothing written: limbs of k not
+ * below r, null pts or out with n > 0.  n = 0: BZK_OK.  ctx = NULL runs the same per-point function over the host field on the host's
+ * threads.  With a context the records are staged in rounds of 2^18 points (the workspace holds one round).  The _dev form takes device
+ * pointers (4-byte aligned), may run in place (out_dev == pts_dev) and needs a context.  Synchronises. */
+int32_t bzk_g1_scale_batch(bzk_ctx* ctx, const uint8_t* pts, uint64_t n, const uint8_t k[32], uint8_t* out, uint8_t* inf_out);
+int32_t bzk_g1_scale_batch_dev(bzk_ctx* ctx, const void* pts_dev, uint64_t n, const uint8_t k[32], void* out_dev, void* inf_out_dev);
+/* The phase-2 step of a ceremony on a resident key: a NEW handle whose delta is d times the source's.  h' = d^-1 h and l' = d^-1 l by
+ * bzk_g1_scale_batch_dev on the source's arrays, a, b_g1 and b_g2 copied device to device, delta_g1' = d delta_g1 and delta_g2' = d delta_g2 on
+ * the host; alpha, beta, gamma (and ic, which no handle holds) do not change.  d: one Montgomery Fr scalar, not zero, limbs below r (else
+ * BZK_E_ARG); d and d^-1 are overwritten in host and device memory before the call returns.  vk870_out (optional): the new 870-byte head.
+ * The source handle, its slots, resident forms and h table are untouched; the new handle builds its own on its first proof.  A device
+ * failure frees the new handle (*out NULL).  The result equals bzk_groth16_setup with delta * d byte for byte.
+ * This re-keys delta ALONE and is no ceremony: whoever knows tau of a dev-mode CRS recovers (1 / delta') G1 from h'[0] and forges at will. */
+int32_t bzk_params_rekey(bzk_ctx* ctx, const bzk_params* params, const uint8_t d[32], bzk_params** out, uint8_t vk870_out[870]);
+/* The same step on a bellman `Parameters` blob: decode, re-key, encode.  out NULL: size query (*size_out = the input's consumed length, which is
+ * also the output's).  ctx = NULL: host threads; with a context the h and l queries run on the device - the same bytes either way.
+ * BZK_E_ARG: d zero or not below r, cap too small, a blob bzk_bellman_params_decode refuses.
+ * bzk_bellman_params_rekey_check: is `after` a re-key of `before` by SOME d?  Returns 1, 0, or a negative status as bzk_bellman_params_check,
+ * report = {array, index, code, 0} with the same array codes (0 vk head, 1 ic, 2 h, 3 l, 4 a, 5 b_g1, 6 b_g2, 7 lengths).  1 exactly when:
+ * both blobs decode and all array lengths agree (else array 7); alpha_g1, beta_g1, beta_g2, gamma_g2, ic, a, b_g1, b_g2 are byte-equal (else
+ * the first differing element, code 0); every point of after's h, l, delta_g1, delta_g2 is in the order-r subgroup (else that point and its
+ * verdict code - a cofactor component vanishes under the pairing, so the ratio test alone would accept h'_i + T_i); delta is one multiple in
+ * both groups, e(delta_g1, G2) = e(G1, delta_g2), before and after (else array 0, index 4 or 5); and e(S(h'), delta_g2') = e(S(h), delta_g2)
+ * with S(q) = sum_i rho_i q_i, likewise for l (else array 2 or 3, index 0, code 0).  rho_i = the low 16 bytes of SHA3-256(seed | array code
+ * as one byte | LE64(i)) as an integer.  The four sums are device MSMs with a context, host sums without.  The verdict is only as good as
+ * the secrecy of seed from whoever made `after`: with seed known, h' can be chosen to cancel inside S. */
+int32_t bzk_bellman_params_rekey(bzk_ctx* ctx, const uint8_t* bytes, uint64_t len, const uint8_t d[32], uint8_t* out, uint64_t cap,
+                                 uint64_t* size_out);
+int32_t bzk_bellman_params_rekey_check(bzk_ctx* ctx, const uint8_t* before, uint64_t before_len, const uint8_t* after, uint64_t after_len,
+                                       const uint8_t seed[32], uint64_t report[4]);
+
 /* h-polynomial stage alone (7 NTTs + pointwise), device resident: a,b,c hold az,bz,cz zero-padded to
  * m scalars on entry; on return a[0 .. m-1) holds the h coefficients.  Exposed for parity tests. */
 int32_t bzk_groth16_h_dev(bzk_ctx* ctx, void* a_dev, void* b_dev, void* c_dev, uint32_t log_m);

@@ -604,6 +604,41 @@ impl Gpu {
         Ok(ok)
     }
 
+    /// `k * P` for many raw G1 points of the order-r subgroup and ONE scalar (32-byte Montgomery limbs), one device lane per point: the points
+    /// in canonical affine, and per point whether the product is the identity (its record is 96 zero bytes then).
+    pub fn g1_scale_batch(&self, pts: &[[u8; 96]], k: &[u8; 32]) -> Result<(Vec<[u8; 96]>, Vec<bool>), GpuError> {
+        let (mut out, mut inf) = (vec![[0u8; 96]; pts.len()], vec![0u8; pts.len()]);
+        check(self.0, unsafe {
+            sys::bzk_g1_scale_batch(self.0, pts.as_ptr() as *const u8, pts.len() as u64, k.as_ptr(), out.as_mut_ptr() as *mut u8, inf.as_mut_ptr())
+        })?;
+        Ok((out, inf.into_iter().map(|b| b != 0).collect()))
+    }
+
+    /// The phase-2 step of a ceremony on a bellman `Parameters` file: delta times `d` (h and l times 1 / d on the device).  This re-keys delta
+    /// alone: it is one contribution, not a ceremony.
+    pub fn bellman_params_rekey(&self, params: &[u8], d: &[u8; 32]) -> Result<Vec<u8>, GpuError> {
+        let mut size = 0u64;
+        check(self.0, unsafe { sys::bzk_bellman_params_rekey(self.0, params.as_ptr(), params.len() as u64, d.as_ptr(), ptr::null_mut(), 0, &mut size) })?;
+        let mut out = vec![0u8; size as usize];
+        check(self.0, unsafe {
+            sys::bzk_bellman_params_rekey(self.0, params.as_ptr(), params.len() as u64, d.as_ptr(), out.as_mut_ptr(), size, ptr::null_mut())
+        })?;
+        Ok(out)
+    }
+
+    /// Is `after` a re-key of `before` by some scalar?  `Ok(None)`: yes; `Ok(Some((array, index, code)))`: the first failure (arrays as
+    /// bzk_bellman_params_check names them).  The verdict is only as good as the secrecy of `seed` from whoever made `after`.
+    pub fn bellman_params_rekey_check(&self, before: &[u8], after: &[u8], seed: &[u8; 32]) -> Result<Option<(u64, u64, u64)>, GpuError> {
+        let mut report = [0u64; 4];
+        let st = unsafe {
+            sys::bzk_bellman_params_rekey_check(self.0, before.as_ptr(), before.len() as u64, after.as_ptr(), after.len() as u64, seed.as_ptr(), report.as_mut_ptr())
+        };
+        if st < 0 {
+            check(self.0, st)?;
+        }
+        Ok(if st == 1 { None } else { Some((report[0], report[1], report[2])) })
+    }
+
     /// SHA-512 per message, one device lane each
     pub fn sha512_batch(&self, msgs: &[&[u8]]) -> Result<Vec<[u8; 64]>, GpuError> {
         let mut off = Vec::with_capacity(msgs.len() + 1);
@@ -874,6 +909,17 @@ impl ProvingParams {
             sys::bzk_params_load_bellman_checked(gpu.0, bytes.as_ptr(), bytes.len() as u64, n_in, n_aux, a_density.as_ptr(), b_density.as_ptr(),
                                                  &mut params, vk.as_mut_ptr(), vk.len() as u64, report.as_mut_ptr())
         })?;
+        Ok(ProvingParams { gpu, params, vk_bincode: vk })
+    }
+
+    /// The phase-2 step of a ceremony on these resident parameters: NEW parameters whose delta is `d` times this one's (h and l times 1 / d
+    /// on the device, a / b_g1 / b_g2 copied there).  `self` is left as it was; `device` is the device both live on (the new parameters own a
+    /// context of their own, as every `ProvingParams` does).  This re-keys delta alone: it is one contribution, not a ceremony.
+    pub fn rekey(&self, device: i32, d: &[u8; 32]) -> Result<Self, GpuError> {
+        let gpu = Gpu::new(device)?;
+        let mut params = ptr::null_mut();
+        let mut vk = self.vk_bincode.clone();
+        check(gpu.0, unsafe { sys::bzk_params_rekey(gpu.0, self.params, d.as_ptr(), &mut params, vk.as_mut_ptr()) })?;
         Ok(ProvingParams { gpu, params, vk_bincode: vk })
     }
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "bzk_internal.h"
+#include "bzk_pmul.h"
 #include "bzk_rekey.h"
 #include "bzk_scale.cuh"
 #include "bzk_stage.h"
@@ -88,6 +89,10 @@ Fp fp_hex(const char* hex) {  // 96 hex digits, big-endian, canonical -> Montgom
     }
     return fe_to_mont<FpParams>(c);
 }
+
+}  // namespace
+
+// shared with ptau.hip (bzk_pmul.h)
 hp::G1A g1_gen() {
     return {hp::to_h(fp_hex("17f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb")),
             hp::to_h(fp_hex("08b3f481e3aaa0f1a09e30ed741d8ae4fcf5e095d5d00af600db18cb2c04b3edd03cc744a2888ae40caa232946c5e7e1")), false};
@@ -109,17 +114,6 @@ bool pairings_equal(const hp::G1A& a, const hp::G2A& q1, const hp::G1A& b, const
     return !degenerate && hp::e12_is_one(hp::final_exp(f));
 }
 
-// k P on the host for a 256-bit canonical k, generic XYZZ (a handful of points per call: the head's delta_g2, the terms of a host sum)
-template <class F>
-XyzzT<F> host_mul(const AffineT<F>& p, const uint32_t* k, int bits) {
-    XyzzT<F> r = xyzz_identity<F>();
-    for (int i = bits - 1; i >= 0; --i) {
-        r = xyzz_dbl<F>(r);
-        if ((k[i >> 5] >> (i & 31)) & 1) xyzz_add_mixed<F>(r, p);
-    }
-    return r;
-}
-
 void rho_of(const uint8_t seed[32], uint8_t code, uint64_t i, uint8_t out32[32]) {  // the low 16 bytes of the digest, as a canonical 32-byte integer
     uint8_t msg[41], h[32];
     memcpy(msg, seed, 32);
@@ -130,30 +124,13 @@ void rho_of(const uint8_t seed[32], uint8_t code, uint64_t i, uint8_t out32[32])
     memset(out32 + 16, 0, 16);
 }
 
-// S = sum_i rho_i q_i on host threads: every chunk its own running sum, the chunks' sums added at the end
+namespace {
+
+// S = sum_i rho_i q_i on host threads (bzk_pmul.h host_seeded_sum)
 hp::G1A host_sum(const uint8_t* q, uint64_t n, const uint8_t seed[32], uint8_t code) {
-    typedef XyzzT<HFpOps> Pt;
-    const uint64_t chunk = 256, n_chunks = (n + chunk - 1) / chunk;
-    std::vector<Pt> part(n_chunks, xyzz_identity<HFpOps>());
-    host_for_each(n_chunks, host_default_threads(), [&](uint64_t c) {
-        Pt acc = xyzz_identity<HFpOps>();
-        for (uint64_t i = c * chunk; i < n && i < (c + 1) * chunk; ++i) {
-            uint8_t rho[32];
-            uint32_t k[8];
-            rho_of(seed, code, i, rho);
-            memcpy(k, rho, 32);
-            AffineT<HFpOps> p;
-            memcpy(p.x.l, q + 96 * i, 48);
-            memcpy(p.y.l, q + 96 * i + 48, 48);
-            xyzz_add<HFpOps>(acc, host_mul<HFpOps>(p, k, 128));
-        }
-        part[c] = acc;
-    });
-    Pt s = xyzz_identity<HFpOps>();
-    for (const Pt& p : part) xyzz_add<HFpOps>(s, p);
     AffineT<HFpOps> a;
     hp::G1A r;
-    r.inf = !xyzz_to_affine<HFpOps>(s, a);
+    r.inf = !host_seeded_sum<HFpOps>(q, n, seed, code, a);
     r.x = a.x;
     r.y = a.y;
     return r;

@@ -149,6 +149,18 @@ SIGNATURES = {
     "bzk_params_rekey": (_i32, [_vp, _vp, _vp, C.POINTER(_vp), _vp]),
     "bzk_bellman_params_rekey": (_i32, [_vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(_u64)]),
     "bzk_bellman_params_rekey_check": (_i32, [_vp, _vp, _u64, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "bzk_g1_mul_batch": (_i32, [_vp, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "bzk_g1_mul_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "bzk_g2_mul_batch": (_i32, [_vp, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "bzk_g2_mul_batch_dev": (_i32, [_vp, _vp, _vp, _u64, _u32, _vp, _vp]),
+    "bzk_g1_mul_powers": (_i32, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_g1_mul_powers_dev": (_i32, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_g2_mul_powers": (_i32, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_g2_mul_powers_dev": (_i32, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
+    "bzk_ptau_size": (_u64, [_u32]),
+    "bzk_ptau_init": (_i32, [_u32, _vp, _u64]),
+    "bzk_ptau_contribute": (_i32, [_vp, _vp, _u64, _vp, _vp, _u64, _vp]),
+    "bzk_ptau_check": (_i32, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "bzk_groth16_h_dev": (_i32, [_vp, _vp, _vp, _vp, _u32]),
     "bzk_mpn_create": (_i32, [_u32, _u32, C.POINTER(_vp)]),
     "bzk_mpn_destroy": (None, [_vp]),
@@ -1046,6 +1058,32 @@ class Bzk:
 
     def bellman_params_rekey_check(self, before: bytes, after: bytes, seed: bytes):
         return bellman_params_rekey_check(self, before, after, seed)
+
+    # ---- n points times n scalars, the powers form and the powers-of-tau accumulator (include/bzk.h)
+    def mul_batch(self, group: str, pts: bytes, scalars: bytes, canonical: bool = False):
+        """(out, inf): scalars[i] times each raw G1 / G2 point, one lane per point"""
+        return mul_batch(self, group, pts, scalars, canonical)
+
+    def mul_batch_dev(self, group: str, pts, scalars, n: int, out, inf=None, canonical: bool = False):
+        """device buffers: pts and out n records (out may be pts), scalars n x 32, inf n flag bytes or None; synchronises"""
+        fn = {"g1": self.lib.bzk_g1_mul_batch_dev, "g2": self.lib.bzk_g2_mul_batch_dev}[group]
+        self._ck(fn(self.h, _ptr(pts), _ptr(scalars), n, BZK_F_CANONICAL if canonical else 0, _ptr(out), _ptr(inf) if inf is not None else None),
+                 "mul_batch_dev")
+
+    def mul_powers(self, group: str, pts: bytes, c: bytes, s: bytes, start: int = 0):
+        """(out, inf): c s^(start + i) times point i; c, s Montgomery Fr scalars"""
+        return mul_powers(self, group, pts, c, s, start)
+
+    def mul_powers_dev(self, group: str, pts, n: int, c: bytes, s: bytes, start: int, out, inf=None):
+        fn = {"g1": self.lib.bzk_g1_mul_powers_dev, "g2": self.lib.bzk_g2_mul_powers_dev}[group]
+        self._ck(fn(self.h, _ptr(pts), n, _ptr(c), _ptr(s), start, _ptr(out), _ptr(inf) if inf is not None else None), "mul_powers_dev")
+
+    def ptau_contribute(self, blob: bytes, secrets: bytes):
+        """(new accumulator, 576-byte key): the five arrays' powers calls on the device"""
+        return ptau_contribute(self, blob, secrets)
+
+    def ptau_check(self, before, key, after: bytes, seed: bytes):
+        return ptau_check(self, before, key, after, seed)
 
     def groth16_h_dev(self, a, b, c, log_m: int):
         self._ck(self.lib.bzk_groth16_h_dev(self.h, _ptr(a), _ptr(b), _ptr(c), log_m), "groth16_h_dev")
@@ -2093,6 +2131,73 @@ def bellman_params_rekey_check(ctx, before: bytes, after: bytes, seed: bytes):
     st = load_library().bzk_bellman_params_rekey_check(_h(ctx), _ptr(before), len(before), _ptr(after), len(after), _ptr(seed), report)
     if st < 0:
         _st(st, "bellman_params_rekey_check")
+    return st, tuple(report)
+
+
+_POINT_BYTES = {"g1": 96, "g2": 192}
+
+
+def mul_batch(ctx, group: str, pts: bytes, scalars: bytes, canonical: bool = False):
+    """(out, inf): out[i] = scalars[i] * pts[i] for raw G1 (96-byte) or G2 (192-byte) points of the order-r subgroup; scalars 32 bytes each, Montgomery
+    limbs or, with canonical, plain integers; an identity result is zero bytes with inf[i] = 1.  ctx: a Bzk (one GPU lane per point) or None (host threads)"""
+    size = _POINT_BYTES[group]
+    n = len(pts) // size
+    if len(pts) != size * n or len(scalars) != 32 * n:
+        raise BzkError("mul_batch: pts must hold %d bytes per point and scalars 32" % size)
+    lib = load_library()
+    fn = {"g1": lib.bzk_g1_mul_batch, "g2": lib.bzk_g2_mul_batch}[group]
+    out, inf = C.create_string_buffer(max(size * n, 1)), C.create_string_buffer(max(n, 1))
+    _st(fn(_h(ctx), _ptr(pts) if n else None, _ptr(scalars) if n else None, n, BZK_F_CANONICAL if canonical else 0, out, inf), "mul_batch")
+    return out.raw[: size * n], inf.raw[:n]
+
+
+def mul_powers(ctx, group: str, pts: bytes, c: bytes, s: bytes, start: int = 0):
+    """(out, inf): out[i] = c * s^(start + i) * pts[i]; c and s 32-byte Montgomery Fr scalars, treated as secrets by the library"""
+    size = _POINT_BYTES[group]
+    n = len(pts) // size
+    if len(pts) != size * n or len(c) != 32 or len(s) != 32:
+        raise BzkError("mul_powers: pts must hold %d bytes per point, c and s 32 bytes" % size)
+    lib = load_library()
+    fn = {"g1": lib.bzk_g1_mul_powers, "g2": lib.bzk_g2_mul_powers}[group]
+    out, inf = C.create_string_buffer(max(size * n, 1)), C.create_string_buffer(max(n, 1))
+    _st(fn(_h(ctx), _ptr(pts) if n else None, n, _ptr(c), _ptr(s), start, out, inf), "mul_powers")
+    return out.raw[: size * n], inf.raw[:n]
+
+
+def ptau_size(log_m: int) -> int:
+    return load_library().bzk_ptau_size(log_m)
+
+
+def ptau_init(log_m: int) -> bytes:
+    """the trivial powers-of-tau accumulator for m = 2^log_m: every entry its group's generator"""
+    n = ptau_size(log_m)
+    if n == 0:
+        raise BzkError("ptau_init: log_m must be 1 .. 24")
+    out = C.create_string_buffer(n)
+    _st(load_library().bzk_ptau_init(log_m, out, n), "ptau_init")
+    return out.raw
+
+
+def ptau_contribute(ctx, blob: bytes, secrets: bytes):
+    """(new accumulator, key): `blob` with tau, alpha, beta multiplied by secrets = tau | alpha | beta (3 x 32 bytes Montgomery, none zero); key = tau G2 |
+    alpha G2 | beta G2 (576 bytes).  ctx None: host threads - the same bytes either way"""
+    if len(secrets) != 96:
+        raise BzkError("ptau_contribute: secrets must hold 96 bytes")
+    out, key = C.create_string_buffer(max(len(blob), 1)), C.create_string_buffer(576)
+    _st(load_library().bzk_ptau_contribute(_h(ctx), _ptr(blob), len(blob), _ptr(secrets), out, len(blob), key), "ptau_contribute")
+    return out.raw[: len(blob)], key.raw
+
+
+def ptau_check(ctx, before, key, after: bytes, seed: bytes):
+    """(verdict, report): is `after` a well-formed accumulator and, with before and key (both or neither), one contribution on top of `before` - 1 or 0
+    with report = (array, index, code, 0) of the first failure.  The verdict is only as good as the secrecy of `seed` (32 bytes) from whoever made `after`"""
+    if len(seed) != 32 or (before is None) != (key is None) or (key is not None and len(key) != 576):
+        raise BzkError("ptau_check: seed must hold 32 bytes, key 576; before and key come together")
+    report = (C.c_uint64 * 4)()
+    st = load_library().bzk_ptau_check(_h(ctx), _ptr(before) if before is not None else None, len(before) if before is not None else 0,
+                                       _ptr(key) if key is not None else None, _ptr(after), len(after), _ptr(seed), report)
+    if st < 0:
+        _st(st, "ptau_check")
     return st, tuple(report)
 
 

@@ -699,6 +699,62 @@ int32_t bzk_bellman_params_rekey(bzk_ctx* ctx, const uint8_t* bytes, uint64_t le
 int32_t bzk_bellman_params_rekey_check(bzk_ctx* ctx, const uint8_t* before, uint64_t before_len, const uint8_t* after, uint64_t after_len,
                                        const uint8_t seed[32], uint64_t report[4]);
 
+/* n points times n DIFFERENT scalars, one GPU lane per point: out[i] = scalars[i] * pts[i], on G1 (raw 96-byte records x | y) and on G2 (raw
+ * 192-byte records x.c0 | x.c1 | y.c0 | y.c1), little-endian Montgomery limbs in, canonical affine out - the records the subgroup checks and
+ * the one-scalar call above take.  scalars: n x 32 bytes, Montgomery limbs, or plain integers with BZK_F_CANONICAL in flags (other flag bits
+ * are ignored).  An identity result is zero bytes with inf_out[i] = 1 (inf_out: n bytes, may be NULL; 0 for a finite result); a record of zero
+ * bytes is read as the identity; a zero scalar gives the identity.  The contract covers points of the order-r subgroup (the scalar is split
+ * through X^2 (x, y) = (c x, -y), which is multiplication by X^2 only there); for any other input the output is unspecified and nothing faults:
+ * the formulas are the complete ones of the subgroup check, every lane runs the same 128 steps and no step depends on the point's value.
+ * BZK_E_ARG, nothing written: a scalar whose limbs are not below r (all n are tested first), null pts, scalars or out with n > 0.  n = 0:
+ * BZK_OK.  ctx = NULL runs the same per-point function over the host field on the host's threads.  With a context, host records are staged in
+ * rounds of 2^18 points.  The _dev forms take device pointers (4-byte aligned, scalars too), may run in place (out_dev == pts_dev) and need a
+ * context.  Synchronises.
+ * The powers forms: out[i] = c * s^(start + i) * pts[i], the scalars made on the device from a table of s^(2^j) (start + n must not pass
+ * 2^64).  c and s are Montgomery scalars with limbs below r (else BZK_E_ARG) and are treated as secrets: the table, and the recoded scalars of
+ * every round, are overwritten in host and device memory before the call returns.
+ * A throughput implementation: the multiplier is not hardened against timing (lanes skip the additions of their zero bits). */
+int32_t bzk_g1_mul_batch(bzk_ctx* ctx, const uint8_t* pts, const uint8_t* scalars, uint64_t n, uint32_t flags, uint8_t* out, uint8_t* inf_out);
+int32_t bzk_g1_mul_batch_dev(bzk_ctx* ctx, const void* pts_dev, const void* scalars_dev, uint64_t n, uint32_t flags, void* out_dev,
+                             void* inf_out_dev);
+int32_t bzk_g2_mul_batch(bzk_ctx* ctx, const uint8_t* pts, const uint8_t* scalars, uint64_t n, uint32_t flags, uint8_t* out, uint8_t* inf_out);
+int32_t bzk_g2_mul_batch_dev(bzk_ctx* ctx, const void* pts_dev, const void* scalars_dev, uint64_t n, uint32_t flags, void* out_dev,
+                             void* inf_out_dev);
+int32_t bzk_g1_mul_powers(bzk_ctx* ctx, const uint8_t* pts, uint64_t n, const uint8_t c[32], const uint8_t s[32], uint64_t start, uint8_t* out,
+                          uint8_t* inf_out);
+int32_t bzk_g1_mul_powers_dev(bzk_ctx* ctx, const void* pts_dev, uint64_t n, const uint8_t c[32], const uint8_t s[32], uint64_t start,
+                              void* out_dev, void* inf_out_dev);
+int32_t bzk_g2_mul_powers(bzk_ctx* ctx, const uint8_t* pts, uint64_t n, const uint8_t c[32], const uint8_t s[32], uint64_t start, uint8_t* out,
+                          uint8_t* inf_out);
+int32_t bzk_g2_mul_powers_dev(bzk_ctx* ctx, const void* pts_dev, uint64_t n, const uint8_t c[32], const uint8_t s[32], uint64_t start,
+                              void* out_dev, void* inf_out_dev);
+/* A powers-of-tau accumulator (phase 1 of a ceremony) as one flat blob of this library's raw records (no other tool's file format):
+ *   "BZKPTAU1" | u32 log_m | u32 0 | tau_g1[2m - 1] | tau_g2[m] | alpha_g1[m] | beta_g1[m] | beta_g2,   m = 2^log_m, log_m in 1 .. 24
+ * with tau_g1[i] = tau^i G1, tau_g2[i] = tau^i G2, alpha_g1[i] = alpha tau^i G1, beta_g1[i] = beta tau^i G1, beta_g2 = beta G2.
+ * bzk_ptau_size: the blob's length (0 for a log_m outside 1 .. 24).  bzk_ptau_init: the trivial accumulator, every entry its group's generator
+ * (BZK_E_ARG: out NULL, bad log_m, cap too small).
+ * bzk_ptau_contribute: out = in with tau, alpha, beta multiplied by the three secrets (tau | alpha | beta, Montgomery, limbs below r, none
+ * zero - else BZK_E_ARG, as for a blob that does not parse or a cap below its size; nothing written): five calls of the powers form above, on
+ * the device with a context, on host threads without; beta_g2 and key_out = tau G2 | alpha G2 | beta G2 (raw records, the public key of this
+ * contribution) on the host.  out may be in.  The secrets are the caller's to overwrite; every copy this call makes is overwritten.
+ * bzk_ptau_check: returns 1, 0 or a negative status; report = {array, index, code, 0} names the first failure (zeros on success), array =
+ * 0 header or lengths (index 1: of before), 1 tau_g1, 2 tau_g2, 3 alpha_g1, 4 beta_g1, 5 beta_g2, 6 key.  1 exactly when, in this order: after
+ * parses (and before, with the same log_m); every point of after passes the subgroup check above, the identity refused (else that point and its
+ * verdict code); tau_g1[0] and tau_g2[0] are the generators byte for byte; with rho_i as in the re-key check (array code as the code byte)
+ * e(S1, G2) = e(S0, tau_g2[1]) for S0 = sum_i rho_i q[i], S1 = sum_i rho_i q[i + 1] over q = tau_g1, then e(tau_g1[1], T0) = e(G1, T1) for the
+ * same sums over tau_g2, then the first form over alpha_g1 and over beta_g1 (else that array, index 0); e(beta_g1[0], G2) = e(G1, beta_g2)
+ * (else array 5); and, with before (key NULL exactly when before is, else BZK_E_ARG), for k = tau, alpha, beta: the key point is in the G2
+ * subgroup and e(after.x, G2) = e(before.x, key_k) for x = tau_g1[1], alpha_g1[0], beta_g1[0] (else array 6, index k).  The sums are device
+ * MSMs with a context, host sums without.
+ * The verdict is only as good as the secrecy of seed from whoever made `after`.  There is no proof of knowledge of the key's exponents, no
+ * transcript hash and no hardening of the multiplier against timing: a throughput implementation of the arithmetic, not a ceremony client. */
+uint64_t bzk_ptau_size(uint32_t log_m);
+int32_t bzk_ptau_init(uint32_t log_m, uint8_t* out, uint64_t cap);
+int32_t bzk_ptau_contribute(bzk_ctx* ctx, const uint8_t* in, uint64_t len, const uint8_t secrets[96], uint8_t* out, uint64_t cap,
+                            uint8_t key_out[576]);
+int32_t bzk_ptau_check(bzk_ctx* ctx, const uint8_t* before, uint64_t before_len, const uint8_t key[576], const uint8_t* after, uint64_t after_len,
+                       const uint8_t seed[32], uint64_t report[4]);
+
 /* h-polynomial stage alone (7 NTTs + pointwise), device resident: a,b,c hold az,bz,cz zero-padded to
  * m scalars on entry; on return a[0 .. m-1) holds the h coefficients.  Exposed for parity tests. */
 int32_t bzk_groth16_h_dev(bzk_ctx* ctx, void* a_dev, void* b_dev, void* c_dev, uint32_t log_m);

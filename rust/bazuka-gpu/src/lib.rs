@@ -639,6 +639,72 @@ impl Gpu {
         Ok(if st == 1 { None } else { Some((report[0], report[1], report[2])) })
     }
 
+    /// `k_i * P_i` for raw G1 points of the order-r subgroup and one scalar PER point (32-byte Montgomery limbs), one device lane per point:
+    /// the points in canonical affine, and per point whether the product is the identity (its record is zero bytes then).
+    pub fn g1_mul_batch(&self, pts: &[[u8; 96]], scalars: &[[u8; 32]]) -> Result<(Vec<[u8; 96]>, Vec<bool>), GpuError> {
+        assert_eq!(pts.len(), scalars.len());
+        let (mut out, mut inf) = (vec![[0u8; 96]; pts.len()], vec![0u8; pts.len()]);
+        check(self.0, unsafe {
+            sys::bzk_g1_mul_batch(self.0, pts.as_ptr() as *const u8, scalars.as_ptr() as *const u8, pts.len() as u64, 0, out.as_mut_ptr() as *mut u8, inf.as_mut_ptr())
+        })?;
+        Ok((out, inf.into_iter().map(|b| b != 0).collect()))
+    }
+
+    /// The same on G2 (x.c0 | x.c1 | y.c0 | y.c1).
+    pub fn g2_mul_batch(&self, pts: &[[u8; 192]], scalars: &[[u8; 32]]) -> Result<(Vec<[u8; 192]>, Vec<bool>), GpuError> {
+        assert_eq!(pts.len(), scalars.len());
+        let (mut out, mut inf) = (vec![[0u8; 192]; pts.len()], vec![0u8; pts.len()]);
+        check(self.0, unsafe {
+            sys::bzk_g2_mul_batch(self.0, pts.as_ptr() as *const u8, scalars.as_ptr() as *const u8, pts.len() as u64, 0, out.as_mut_ptr() as *mut u8, inf.as_mut_ptr())
+        })?;
+        Ok((out, inf.into_iter().map(|b| b != 0).collect()))
+    }
+
+    /// `c * s^(start + i) * P_i`, the scalars made on the device; `c` and `s` are treated as secrets by the library (its copies are overwritten).
+    pub fn g1_mul_powers(&self, pts: &[[u8; 96]], c: &[u8; 32], s: &[u8; 32], start: u64) -> Result<(Vec<[u8; 96]>, Vec<bool>), GpuError> {
+        let (mut out, mut inf) = (vec![[0u8; 96]; pts.len()], vec![0u8; pts.len()]);
+        check(self.0, unsafe {
+            sys::bzk_g1_mul_powers(self.0, pts.as_ptr() as *const u8, pts.len() as u64, c.as_ptr(), s.as_ptr(), start, out.as_mut_ptr() as *mut u8, inf.as_mut_ptr())
+        })?;
+        Ok((out, inf.into_iter().map(|b| b != 0).collect()))
+    }
+
+    /// The same on G2.
+    pub fn g2_mul_powers(&self, pts: &[[u8; 192]], c: &[u8; 32], s: &[u8; 32], start: u64) -> Result<(Vec<[u8; 192]>, Vec<bool>), GpuError> {
+        let (mut out, mut inf) = (vec![[0u8; 192]; pts.len()], vec![0u8; pts.len()]);
+        check(self.0, unsafe {
+            sys::bzk_g2_mul_powers(self.0, pts.as_ptr() as *const u8, pts.len() as u64, c.as_ptr(), s.as_ptr(), start, out.as_mut_ptr() as *mut u8, inf.as_mut_ptr())
+        })?;
+        Ok((out, inf.into_iter().map(|b| b != 0).collect()))
+    }
+
+    /// One contribution to a powers-of-tau accumulator (the flat blob of include/bzk.h): tau, alpha, beta multiplied by `secrets` =
+    /// tau | alpha | beta (Montgomery, none zero).  Returns the new accumulator and the contribution's key tau G2 | alpha G2 | beta G2.
+    /// The arithmetic of a contribution, not a ceremony client: no proof of knowledge, no transcript.
+    pub fn ptau_contribute(&self, acc: &[u8], secrets: &[u8; 96]) -> Result<(Vec<u8>, [u8; 576]), GpuError> {
+        let (mut out, mut key) = (vec![0u8; acc.len()], [0u8; 576]);
+        check(self.0, unsafe {
+            sys::bzk_ptau_contribute(self.0, acc.as_ptr(), acc.len() as u64, secrets.as_ptr(), out.as_mut_ptr(), out.len() as u64, key.as_mut_ptr())
+        })?;
+        Ok((out, key))
+    }
+
+    /// Is `after` a well-formed accumulator and, with `step` = (before, key), one contribution on top of `before`?  `Ok(None)`: yes;
+    /// `Ok(Some((array, index, code)))`: the first failure (0 header or lengths, 1 tau_g1, 2 tau_g2, 3 alpha_g1, 4 beta_g1, 5 beta_g2, 6 key).
+    /// The verdict is only as good as the secrecy of `seed` from whoever made `after`.
+    pub fn ptau_check(&self, step: Option<(&[u8], &[u8; 576])>, after: &[u8], seed: &[u8; 32]) -> Result<Option<(u64, u64, u64)>, GpuError> {
+        let mut report = [0u64; 4];
+        let (before, before_len, key) = match step {
+            Some((b, k)) => (b.as_ptr(), b.len() as u64, k.as_ptr()),
+            None => (ptr::null(), 0, ptr::null()),
+        };
+        let st = unsafe { sys::bzk_ptau_check(self.0, before, before_len, key, after.as_ptr(), after.len() as u64, seed.as_ptr(), report.as_mut_ptr()) };
+        if st < 0 {
+            check(self.0, st)?;
+        }
+        Ok(if st == 1 { None } else { Some((report[0], report[1], report[2])) })
+    }
+
     /// SHA-512 per message, one device lane each
     pub fn sha512_batch(&self, msgs: &[&[u8]]) -> Result<Vec<[u8; 64]>, GpuError> {
         let mut off = Vec::with_capacity(msgs.len() + 1);
@@ -865,6 +931,16 @@ impl GpuPoseidonHasher {
 /// `ZkStateModel::compress` through the shared context (drop-in for `model.compress::<PoseidonHasher>(&data)`)
 pub fn compress(model: &ZkStateModel, data: &ZkDataPairs) -> Result<ZkCompressedState, DeviceStateError> {
     shared_gpu().lock().unwrap().compress(model, data)
+}
+
+/// The trivial powers-of-tau accumulator for m = 2^log_m (every entry its group's generator); `None` for a log_m outside 1 .. 24.  No device.
+pub fn ptau_init(log_m: u32) -> Option<Vec<u8>> {
+    let size = unsafe { sys::bzk_ptau_size(log_m) };
+    if size == 0 {
+        return None;
+    }
+    let mut out = vec![0u8; size as usize];
+    (unsafe { sys::bzk_ptau_init(log_m, out.as_mut_ptr(), size) } == sys::BZK_OK).then(|| out)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
